@@ -21,7 +21,9 @@ Order of a run (rank 0, N = 1: first a child process `rocprofv3 --pmc ... -- pyt
 counters of the same launches -> roofline.traffic): one step on the fresh input (its 8/N roots are kept and compared with the
 CPU oracle's -> `root_match`), W - 1 more warm-up steps, barrier, K timed steps from idle clocks (`ms_per_step_cold`: what a
 prover that commits a handful of trees sees), spin-up steps until the part has been under load for --spinup-ms (its clocks
-need 40-75 ms to settle; `spinup_steps` in the line), barrier, K timed steps (`ms_per_step`, `value`), barrier.
+need 40-75 ms to settle; `spinup_steps` in the line), the fresh input copied back into the columns (a device copy kept since
+the upload), barrier, K timed steps (`ms_per_step`, `value`), barrier.  So the headline's last step computes the same outputs on
+every run with the same arguments; --dump-outputs DIR writes them (samples of the large arrays, see dump_outputs).
 
 Rank 0 prints ONE JSON line:  value = (all ranks' columns * 2^22 elements * K) / max-over-ranks time.
 `roofline` prices the dominant kernel (the CFFT pass kernels) against the 8 TB/s HBM roofline with the
@@ -56,6 +58,9 @@ VALU_PEAK_DUAL_MEASURED = 60.3e12         # the butterfly's 11 instructions issu
 SPINUP_MS = 200.0                         # load the part must have seen before the headline timed region: it needs ~40-75 ms
                                           # before its clocks settle (tools/cfft_time.py --series: 560 -> 487 us per transform)
 HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_SEED = 0x5EED              # --dump-outputs: the rows / nodes sampled from arrays larger than their share of the 64 MB
+DUMP_EVAL_BYTES = 48 << 20      # evaluations.npy + evaluation_rows.npy
+DUMP_NODE_BYTES = 8 << 20       # merkle_nodes.npy + merkle_node_index.npy (roots.npy: 64 bytes per tree beside them)
 
 
 def splitmix_column(seed: int, n: int) -> np.ndarray:
@@ -268,6 +273,41 @@ def pmc_traffic(n: int, n_cols: int, timeout_s: float = 240.0):
     return pj.get("hbm_bytes_per_launch"), src
 
 
+def all_gather_rows(dist, a: np.ndarray) -> np.ndarray:
+    """The ranks' arrays (equal shapes) stacked along axis 0 in rank order, on every rank (gloo, host memory)."""
+    import torch
+    mine = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64).ravel())
+    out = torch.zeros(mine.numel() * dist.get_world_size(), dtype=torch.int64)
+    dist.all_gather_into_tensor(out, mine)
+    return out.numpy().reshape((-1,) + a.shape[1:])
+
+
+def dump_outputs(out_dir: str, roots: bytes, dev_cols: list, layers: list, total_cols: int, total_trees: int, N: int, rank: int,
+                 gather) -> None:
+    """--dump-outputs DIR: what the last timed step handed its caller, as float64 .npy files (M31 values and LE32 digest words are
+    exact in float64).  Columns and trees are gathered over the ranks in trace order, so the files do not depend on the GPU count.
+      roots.npy              (trees, 8)          every tree's Merkle root, LE32 words (the all-gathered roots at N > 1)
+      evaluations.npy        (columns, R)        every column's evaluation at R rows: all of them, or a fixed seeded sample
+      evaluation_rows.npy    (R,)                those rows
+      merkle_nodes.npy       (trees, M, 8)       every tree's layers (tstwo_merkle_commit layout, root first) at M nodes, same rule
+      merkle_node_index.npy  (M,)                those nodes
+    Every rank takes part (gather); rank 0 writes."""
+    rng = np.random.default_rng(DUMP_SEED)
+    n_rows = min(N, DUMP_EVAL_BYTES // (8 * (total_cols + 1)))
+    rows = np.arange(N) if n_rows == N else np.sort(rng.choice(N, n_rows, replace=False))
+    n_nodes = min(2 * N - 1, DUMP_NODE_BYTES // (64 * total_trees + 8))
+    nodes = np.arange(2 * N - 1) if n_nodes == 2 * N - 1 else np.sort(rng.choice(2 * N - 1, n_nodes, replace=False))
+    evals = gather(np.stack([b.download(np.uint32, N)[rows] for b in dev_cols]))
+    tree_nodes = gather(np.stack([l.download(np.uint32, 8 * (2 * N - 1)).reshape(-1, 8)[nodes] for l in layers]))
+    if rank != 0:
+        return
+    out = {"roots": np.frombuffer(roots, dtype="<u4").reshape(-1, 8), "evaluations": evals, "evaluation_rows": rows,
+           "merkle_nodes": tree_nodes, "merkle_node_index": nodes}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -287,10 +327,14 @@ def main():
     ap.add_argument("--no-host-boundary", action="store_true", help="skip the from-host legs (registered-memory upload rate, pipelined upload + step)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the child rocprofv3 --pmc passes (roofline.traffic = null)")
     ap.add_argument("--pmc-json", default=None, help="tools/pmc_summary.py output of an earlier --pmc run of THIS build, instead of the child passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, seeded samples of the large arrays)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around this process: be the launcher (nothing above imported torch or the GPU library)
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -455,6 +499,11 @@ def main():
             dt = float(t.item())
         return dt
 
+    # a device copy of the fresh input, copied back in front of the headline steps (allocated after every buffer the step uses)
+    fresh_cols = [L.DeviceBuffer(4 * N) for _ in dev_cols]
+    for f, b in zip(fresh_cols, dev_cols):
+        L.call("tstwo_copy", C.c_void_p(f.ptr), C.c_void_p(b.ptr), 4 * N)
+
     # Correctness of the measured workload: the first (untimed) step runs on the fresh synthetic input; its roots are
     # compared below with the CPU oracle's roots of the same columns (cpu_baseline.roots) -> "root_match".
     step(None)
@@ -468,7 +517,14 @@ def main():
     spin = int(np.ceil(need_ms / (cold * 1e3 / args.steps))) if need_ms > 0 else 0
     for _ in range(spin):
         step(None)
+    # the headline starts from the fresh input again: each step transforms the previous one's output and the spin-up's step count
+    # follows the clock, so without this the last step's outputs would differ from run to run (one device copy, before the barrier)
+    for f, b in zip(fresh_cols, dev_cols):
+        L.call("tstwo_copy", C.c_void_p(b.ptr), C.c_void_p(f.ptr), 4 * N)
     elapsed = timed(args.steps, evs)               # the headline: EXACTLY K steps between two barriers, max over ranks
+    for f in fresh_cols:
+        f.free()
+    del fresh_cols
     t_cfft = sum(e[0].elapsed_ms(e[1]) for e in evs)
     t_merkle = sum(e[1].elapsed_ms(e[2]) for e in evs)
 
@@ -484,8 +540,14 @@ def main():
         allfirst = torch.zeros(rec * world, dtype=torch.uint8)
         dist.all_gather_into_tensor(allfirst, first)
         tree_roots_first = bytes(allfirst.numpy().tobytes())
+        roots_last = bytes(got.tobytes())
     else:
         tree_roots_first = gpu_roots_first
+        roots_last = my_roots()
+
+    if args.dump_outputs:      # before the from-host legs below overwrite the columns and the trees
+        dump_outputs(args.dump_outputs, roots_last, dev_cols, layers, total_cols, total_cols // tree_cols, N, rank,
+                     gather=lambda a: all_gather_rows(dist, a) if use_dist else a)
 
     # ---- the host boundary (never in `value`): what a caller pays who hands the trace over from HOST memory.
     #  (i) page-locked source (the caller's arrays registered with tstwo_host_register) -> tstwo_upload_async: one DMA per column;

@@ -298,8 +298,14 @@ def test_combine_subtree_roots_and_shard_rows():
 
 
 def test_allgather_roots_single_process():
-    from tstwo_amd.distributed import allgather_roots
-    assert allgather_roots(b"\x01" * 32) == [b"\x01" * 32]
+    """In a fresh interpreter: allgather_roots imports torch, and torch imported after libtstwo_hip.so maps its own HIP runtime
+    and RCCL beside the library's.  The library's communicator would then take that RCCL, and the -m gpu tests that run later
+    in the same session (test_c_abi_collective_world_of_one) would fail in ncclCommInitRank."""
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from tstwo_amd.distributed import allgather_roots\n"
+            "assert allgather_roots(b'\\x01' * 32) == [b'\\x01' * 32]\n" % ROOT)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
 
 
 def test_blake2s_channel_mirror():
@@ -505,6 +511,13 @@ def test_bench_refuses_a_gpu_count_that_is_not_the_world_size():
     assert p.returncode != 0 and "WORLD_SIZE=2" in p.stderr and p.stdout.strip() == ""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "0"], capture_output=True, text=True, timeout=120)
     assert p.returncode != 0 and p.stdout.strip() == ""
+
+
+def test_bench_refuses_fewer_than_one_timed_step():
+    """--steps K is the number of timed steps the line reports per step over: K = 0 must fail before anything touches the GPU."""
+    import subprocess
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert p.returncode != 0 and "--steps" in p.stderr and p.stdout.strip() == ""
 
 
 def test_bench_launcher_relays_rank_failure(tmp_path):

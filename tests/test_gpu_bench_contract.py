@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -78,3 +79,48 @@ def test_bench_rccl_collective_path_at_world_size_one():
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)
     assert d["n_gpus"] == 1 and d["root_match"] is True and d["host_boundary"]["roots_match_resident_step"] is True
+
+
+def test_bench_dump_outputs_repeat_and_do_not_depend_on_the_gpu_count(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float .npy files of at most 64 MB in all.  The headline's K steps start
+    from the fresh input whatever the spin-up ran (its step count follows the clock), so the evaluations are the oracle's CFFT
+    applied K times to the input, and the files are the same on every run with the same arguments and at every GPU count.
+    With --steps 1 the last timed step is the first step, whose roots the run checked against the oracle."""
+    from bench import splitmix_column
+    from oracle import oracle as orc
+
+    def run(out, extra=(), env=None):
+        args = SMALL + ["--spinup-ms", "20", "--dump-outputs", str(out)] + list(extra)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+        assert p.returncode == 0, p.stderr[-2000:]
+        files = sorted(os.listdir(out))
+        assert files == ["evaluation_rows.npy", "evaluations.npy", "merkle_node_index.npy", "merkle_nodes.npy", "roots.npy"]
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        arrays = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        return _line(p.stdout), arrays
+
+    _, a = run(tmp_path / "a", ["--no-cpu"])                     # SMALL: --steps 3
+    _, b = run(tmp_path / "b", ["--no-cpu"])
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["TSTWO_BENCH_COLLECTIVE"] = "gloo"
+    _, c = run(tmp_path / "c", ["--no-cpu", "--gpus", "2"], env=env)
+    assert a["roots"].shape == (2, 8) and a["evaluations"].shape == (64, 1 << 14) and a["merkle_nodes"].shape == (2, (2 << 14) - 1, 8)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+        assert np.array_equal(a[k], c[k]), k
+    assert np.array_equal(a["merkle_nodes"][:, 0, :], a["roots"])   # node 0 of the layers buffer is the root
+
+    d, one = run(tmp_path / "d", ["--steps", "1"])
+    assert d["root_match"] is True
+    assert [bytes(r.astype("<u4").tobytes()).hex() for r in one["roots"]] == d["gpu_roots"]
+    n = 14
+    half = orc.lib().orc_half_odds_initial(n - 1)
+    tw, _ = orc.precompute_twiddles(half, n - 1, inverse=False)
+    for col in range(64):
+        want = splitmix_column(100 + col, 1 << n)
+        for k in range(3):
+            want = orc.cfft_evaluate(want, n, half, tw, n - 1)
+            if k == 0:
+                assert np.array_equal(one["evaluations"][col], want.astype(np.float64)), col
+        assert np.array_equal(a["evaluations"][col], want.astype(np.float64)), col

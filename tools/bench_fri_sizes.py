@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """FRI commit across sizes: host transcript, device transcript, and hipGraph replay of the device-transcript loop."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import tstwo_amd as T
 from tstwo_amd import _lib as L

@@ -3,7 +3,7 @@
 smaller group keep a layer's digests in the 256 MB memory-side cache for the launch that reads them?"""
 import ctypes as C
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from tstwo_amd import _lib as L
 L.init(0)

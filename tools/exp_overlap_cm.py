@@ -4,7 +4,7 @@ beside the CFFT of group g+1 — the transform is HBM-bound, the hashing VALU-bo
 (one evaluate call + one commit_many on one stream) and for groups of 32 / 64 / 128 columns on two streams."""
 import ctypes as C
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from tstwo_amd import _lib as L
 from tstwo_amd.backend import HipBackend

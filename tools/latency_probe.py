@@ -1,5 +1,5 @@
 import ctypes as C, time, sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from tstwo_amd import _lib as L
 L.init(0)

@@ -1,5 +1,5 @@
 import os, sys, cProfile, pstats
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import tstwo_amd as T
 from tstwo_amd import _lib as L

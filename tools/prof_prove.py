@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """cProfile of CommitmentSchemeProver.prove_values (32 polys log 20, blowup 2, 40 queries): host time by function."""
 import cProfile, pstats, os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import tstwo_amd as T
 from tstwo_amd import _lib as L

@@ -3,7 +3,7 @@
 sit far below the 5-6 TB/s the part gives to plain kernels of the same shape)."""
 import ctypes as C
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from tstwo_amd import _lib as L
 L.init(0)

@@ -2,7 +2,7 @@
 """Target for `rocprofv3 --kernel-trace`: FriProver.commit (tstwo_fri_commit_layers) of one size, repeated; and, with
 --timeline DIR, the kernel sequence of the LAST commit in a finished trace: start offset, duration, gap to the previous kernel."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def timeline(root, n_last):

@@ -2,7 +2,7 @@
 """Target for `rocprofv3 --kernel-trace`: CommitmentSchemeProver commit + prove_values of 32 polynomials of log 20 (blowup 2),
 repeated; tools/trace_fri_commit.py --timeline prints the kernel sequence of the last proof."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import tstwo_amd as T
 from tstwo_amd import _lib as L
