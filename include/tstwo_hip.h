@@ -44,6 +44,7 @@ extern "C" {
 #define TSTWO_ERR_BAD_ARG 7
 #define TSTWO_ERR_LOG_SIZE 8       /* "log size too small"                    backend/cpu/circle.ts:72 */
 #define TSTWO_ERR_COMM 9           /* RCCL missing or failing (text has the ncclResult string) */
+#define TSTWO_ERR_ZERO_VARIABLES 10 /* "Number of variables must not be zero" backend/cpu/lookups/gkr.ts:155 */
 
 /* ---------------------------------------------------------------- lifecycle / plumbing */
 int tstwo_init(int device);                 /* select GPU `device`, create the stream; idempotent */
@@ -410,6 +411,45 @@ int tstwo_allgather(const void *send_dev, void *recv_dev, size_t bytes_per_rank)
  * collective; tstwo_sync() after it covers both. */
 int tstwo_allgather_async(const void *send_dev, void *recv_dev, size_t bytes_per_rank);
 int tstwo_comm_wait(void);
+
+/* ---------------------------------------------------------------- GkrOps / MleOps (lookups, LogUp-GKR)
+ * backend/index.ts:93-95 (GkrOps), backend/cpu/lookups/gkr.ts:84-358, backend/cpu/lookups/mle.ts:60-130.
+ * An Mle<SecureField> is 4 SoA columns (SecureColumnByCoords layout), an Mle<BaseField> one column, of 2^log_n values; the
+ * first variable is the most significant bit of the index.  Scalars (y entries, v, lambda, r) are QM31 as 4 host words.
+ * Layer kinds (gkr_prover.ts Layer) for the `kind` arguments: */
+#define TSTWO_GKR_GRAND_PRODUCT 0
+#define TSTWO_GKR_LOGUP_GENERIC 1          /* secure numerators */
+#define TSTWO_GKR_LOGUP_MULTIPLICITIES 2   /* base numerators: only num[0] is read */
+#define TSTWO_GKR_LOGUP_SINGLES 3          /* numerators are 1: num is not read (may hold NULLs) */
+/* GkrOps.genEqEvals (gkr.ts:90-104): out[x] = v * eq(x, y) for x in {0,1}^n_y, y = n_y QM31 values (4 words each, host),
+ * n_y <= 28. */
+int tstwo_gkr_gen_eq_evals(const uint32_t *y, uint32_t n_y, const uint32_t v[4], uint32_t *const out[4]);
+/* GkrOps.nextLayer (gkr.ts:109-137, 317-358), log_n >= 1: out[i] from in[2i], in[2i+1].  Grand product: the QM31 product.
+ * LogUp (kind 1-3): fraction addition (n0 d1 + n1 d0, d0 d1) into secure out_num / out_den — every LogUp kind yields
+ * LogUpGeneric; nothing is inverted, zero denominators are legal. */
+int tstwo_gkr_next_layer_grand_product(const uint32_t *const in[4], uint32_t log_n, uint32_t *const out[4]);
+int tstwo_gkr_next_layer_logup(uint32_t kind, const uint32_t *const num[4], const uint32_t *const den[4], uint32_t log_n,
+                               uint32_t *const out_num[4], uint32_t *const out_den[4]);
+/* GkrOps.sumAsPolyInFirstVariable before its eq_fixed_var_correction and correct_sum_as_poly_in_first_variable steps (the
+ * evalGrandProductSum / evalLogupSum / evalLogupSinglesSum loops of gkr.ts:185-311): out = (f(0), f(2)) as 8 words, f summed
+ * over n_terms = 2^(n_vars-1) terms of a layer of 2^(n_vars+1) values (grand product: the layer is `den`), reading
+ * eq[0 .. n_terms).  n_vars == 0 fails with TSTWO_ERR_ZERO_VARIABLES.  The synchronous form writes host memory; the async form
+ * writes 8 words of device memory and returns with the launch enqueued. */
+int tstwo_gkr_sum_poly(uint32_t kind, const uint32_t *const eq[4], const uint32_t *const num[4], const uint32_t *const den[4],
+                       uint32_t n_vars, const uint32_t lambda[4], uint32_t out[8]);
+int tstwo_gkr_sum_poly_async(uint32_t kind, const uint32_t *const eq[4], const uint32_t *const num[4], const uint32_t *const den[4],
+                             uint32_t n_vars, const uint32_t lambda[4], uint32_t *out_dev);
+/* One round of the batched sumcheck of prove_batch (gkr_prover.ts:313-336 fixFirstVariable, then sumAsPolyInFirstVariable) in
+ * one launch: the layer num / den (2^(n_vars+2) values) has its first variable fixed to r, written to out_num / out_den (in place
+ * when they are num / den; base numerators go to a separate secure out_num), and the (f(0), f(2)) of the folded layer with
+ * n_vars variables goes to out_dev as in the async sum above. */
+int tstwo_gkr_round(uint32_t kind, const uint32_t *const eq[4], const uint32_t *const num[4], const uint32_t *const den[4],
+                    uint32_t *const out_num[4], uint32_t *const out_den[4], uint32_t n_vars, const uint32_t r[4],
+                    const uint32_t lambda[4], uint32_t *out_dev);
+/* MleOps.fixFirstVariable (mle.ts:68-130, lookups/utils.ts:256 foldMleEvals): out[i] = in[i] + r (in[i + n/2] - in[i]),
+ * 2^(log_n-1) secure outputs.  The secure form may run in place (out == in). */
+int tstwo_mle_fix_first_variable_base(const uint32_t *in, uint32_t log_n, const uint32_t r[4], uint32_t *const out[4]);
+int tstwo_mle_fix_first_variable_secure(const uint32_t *const in[4], uint32_t log_n, const uint32_t r[4], uint32_t *const out[4]);
 
 #ifdef __cplusplus
 }

@@ -101,6 +101,14 @@ const lib = dlopen(process.env.TSTWO_HIP_LIB ?? "libtstwo_hip.so", {
   tstwo_quotients_accumulate: { args: [u32, u32, P, u64, u64, P, P, P, P, P, P, P, P, P], returns: i32 },
   tstwo_quotients_accumulate_samples_async: { args: [u32, u32, P, u64, u64, P, P, P, P, P, P], returns: i32 },
   tstwo_quotients_accumulate_async: { args: [u32, u32, P, u64, u64, P, P, P, P, P, P, P, P, P], returns: i32 },
+  tstwo_gkr_gen_eq_evals: { args: [P, u32, P, P], returns: i32 },
+  tstwo_gkr_next_layer_grand_product: { args: [P, u32, P], returns: i32 },
+  tstwo_gkr_next_layer_logup: { args: [u32, P, P, u32, P, P], returns: i32 },
+  tstwo_gkr_sum_poly: { args: [u32, P, P, P, u32, P, P], returns: i32 },
+  tstwo_gkr_sum_poly_async: { args: [u32, P, P, P, u32, P, u64], returns: i32 },
+  tstwo_gkr_round: { args: [u32, P, P, P, P, P, u32, P, P, u64], returns: i32 },
+  tstwo_mle_fix_first_variable_base: { args: [u64, u32, P, P], returns: i32 },
+  tstwo_mle_fix_first_variable_secure: { args: [P, u32, P, P], returns: i32 },
 });
 
 export const hip = lib.symbols;

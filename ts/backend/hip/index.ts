@@ -112,6 +112,53 @@ export class HipBackend implements Backend {
   accumulateQuotients = accumulateQuotients;
   accumulate = accumulate;
   generate_secure_powers = generate_secure_powers;
+  // GkrOps / MleOps (backend/index.ts:93-95; backend/cpu/lookups/{gkr,mle}.ts).  The protocol around them (EqEvals, oracle, prove_batch)
+  // is the reference's lookups/*.ts; tstwo_amd/gkr.py shows the device-resident driver.
+  /** eq(x, y) * v for x in {0,1}^|y|, first variable = most significant bit of x. */
+  genEqEvals(y: readonly QM31[], v: QM31): HipSecureColumn {
+    const out = HipSecureColumn.uninitialized(1 << y.length);
+    const words = new Uint32Array(Math.max(4 * y.length, 4));
+    y.forEach((yi, k) => words.set(q4(yi), 4 * k));
+    check(hip.tstwo_gkr_gen_eq_evals(ptr(words), y.length, ptr(q4(v)), ptr(out.ptrs())));
+    return out;
+  }
+  /** next_layer of a layer of 2^logN values: GrandProduct when `num` is undefined and `kind` is 0, else LogUp (kind 1 secure, 2 base,
+   *  3 singles numerators) into secure (numerators, denominators). */
+  nextLayer(kind: GkrLayerKind, num: HipSecureColumn | HipColumn | undefined, den: HipSecureColumn, logN: number): [HipSecureColumn | undefined, HipSecureColumn] {
+    const n = 1 << (logN - 1);
+    const outDen = HipSecureColumn.uninitialized(n);
+    if (kind === GkrLayerKind.GrandProduct) {
+      check(hip.tstwo_gkr_next_layer_grand_product(ptr(den.ptrs()), logN, ptr(outDen.ptrs())));
+      return [undefined, outDen];
+    }
+    const outNum = HipSecureColumn.uninitialized(n);
+    check(hip.tstwo_gkr_next_layer_logup(kind, ptr(numPtrs(num)), ptr(den.ptrs()), logN, ptr(outNum.ptrs()), ptr(outDen.ptrs())));
+    return [outNum, outDen];
+  }
+  /** (f(0), f(2)) of the round sum over a layer with nVars + 1 variables, before the eq correction (gkr.ts:142-178);
+   *  throws "Number of variables must not be zero". */
+  sumAsPolyInFirstVariable(kind: GkrLayerKind, eqEvals: HipSecureColumn, num: HipSecureColumn | HipColumn | undefined, den: HipSecureColumn,
+                           nVars: number, lambda: QM31): [QM31, QM31] {
+    const out = new Uint32Array(8);
+    check(hip.tstwo_gkr_sum_poly(kind, ptr(eqEvals.ptrs()), ptr(numPtrs(num)), ptr(den.ptrs()), nVars, ptr(q4(lambda)), ptr(out)));
+    return [QM31.from_u32_unchecked(out[0]!, out[1]!, out[2]!, out[3]!), QM31.from_u32_unchecked(out[4]!, out[5]!, out[6]!, out[7]!)];
+  }
+  /** MleOps.fixFirstVariable (mle.ts:68-130): a new secure MLE of half the length. */
+  fixFirstVariable(mle: HipSecureColumn | HipColumn, assignment: QM31): HipSecureColumn {
+    const out = HipSecureColumn.uninitialized(mle.len() / 2);
+    const logN = Math.log2(mle.len());
+    if (mle instanceof HipColumn) check(hip.tstwo_mle_fix_first_variable_base(mle.dev, logN, ptr(q4(assignment)), ptr(out.ptrs())));
+    else check(hip.tstwo_mle_fix_first_variable_secure(ptr(mle.ptrs()), logN, ptr(q4(assignment)), ptr(out.ptrs())));
+    return out;
+  }
+}
+
+/** Layer kinds of the GKR entry points (TSTWO_GKR_* in include/tstwo_hip.h; gkr_prover.ts Layer). */
+export enum GkrLayerKind { GrandProduct = 0, LogUpGeneric = 1, LogUpMultiplicities = 2, LogUpSingles = 3 }
+
+function numPtrs(num: HipSecureColumn | HipColumn | undefined): BigUint64Array {
+  if (num === undefined) return new BigUint64Array(4);
+  return num instanceof HipColumn ? ptrs([num.dev, num.dev, num.dev, num.dev]) : num.ptrs();
 }
 
 /** accumulateQuotients (backend/cpu/quotients.ts:52-75) on device columns.  The per-batch constants come from the reference's OWN

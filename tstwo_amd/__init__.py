@@ -14,6 +14,11 @@ from .fri_prover import (FriCommitPlan, FriConfig, FriLayerProof, FriProof, FriP
                          compute_decommitment_positions_and_witness_evals)
 from .fri_verifier import (CirclePolyDegreeBound, FriVerificationError, FriVerifier, LinePolyDegreeBound,  # noqa: F401
                            SparseEvaluation, accumulate_line, compute_decommitment_positions_and_rebuild_evals)
+from .gkr import (EqEvals, GkrMultivariatePolyOracle, HipGkrOps, HipMleOps, Layer, Mle,  # noqa: F401
+                  prove_batch as gkr_prove_batch)
+from .gkr_verifier import (Gate, GkrArtifact, GkrBatchProof, GkrError, GkrErrorType, GkrMask,  # noqa: F401
+                           partially_verify_batch)
+from .sumcheck import SumcheckError, SumcheckProof, UnivariatePoly  # noqa: F401
 from .queries import Queries, get_query_positions_by_log_size  # noqa: F401
 from .fri_sharded import ShardedFriLayer, fri_commit_row_sharded  # noqa: F401
 from .fri import HipFriOps, decompose, fold_circle_into_line, fold_line  # noqa: F401

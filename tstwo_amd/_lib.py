@@ -146,6 +146,14 @@ _SIGS = {
     "tstwo_quotients_accumulate_samples_async": [C.c_uint32, C.c_uint32, C.POINTER(vp), C.c_size_t, C.c_size_t, u32p, u32p, u32p, u32p, u32p, P4],
     "tstwo_quotients_accumulate_async": [C.c_uint32, C.c_uint32, C.POINTER(vp), C.c_size_t, C.c_size_t, u32p, u32p, u32p,
                                          u32p, u32p, u32p, u32p, u32p, P4],
+    "tstwo_gkr_gen_eq_evals": [u32p, C.c_uint32, u32p, P4],
+    "tstwo_gkr_next_layer_grand_product": [P4, C.c_uint32, P4],
+    "tstwo_gkr_next_layer_logup": [C.c_uint32, P4, P4, C.c_uint32, P4, P4],
+    "tstwo_gkr_sum_poly": [C.c_uint32, P4, P4, P4, C.c_uint32, u32p, u32p],
+    "tstwo_gkr_sum_poly_async": [C.c_uint32, P4, P4, P4, C.c_uint32, u32p, vp],
+    "tstwo_gkr_round": [C.c_uint32, P4, P4, P4, P4, P4, C.c_uint32, u32p, u32p, vp],
+    "tstwo_mle_fix_first_variable_base": [vp, C.c_uint32, u32p, P4],
+    "tstwo_mle_fix_first_variable_secure": [P4, C.c_uint32, u32p, P4],
 }
 ALLOC_POOL, ALLOC_DIRECT, ALLOC_ASYNC, ALLOC_POISON = 0, 1, 2, 0x10
 # c_void_p arguments above are DEVICE addresses, except these (host memory of any element type)

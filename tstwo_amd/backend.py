@@ -206,6 +206,23 @@ class HipBackend:
         L.call("tstwo_qm31_mul", a.ptrs(), b.ptrs(), out.ptrs(), a.len())
         return out
 
+    # --- GkrOps / MleOps (backend/index.ts:93-95; lookups: tstwo_amd/gkr.py)
+    def genEqEvals(self, y, v):
+        from .gkr import HipGkrOps
+        return HipGkrOps.genEqEvals(y, v)
+
+    def nextLayer(self, layer):
+        from .gkr import HipGkrOps
+        return HipGkrOps.nextLayer(layer)
+
+    def sumAsPolyInFirstVariable(self, h, claim):
+        from .gkr import HipGkrOps
+        return HipGkrOps.sumAsPolyInFirstVariable(h, claim)
+
+    def fixFirstVariable(self, mle, assignment):
+        from .gkr import HipMleOps
+        return HipMleOps.fixFirstVariable(mle, assignment)
+
     # --- helpers used by bench / drivers
     @staticmethod
     def canonic_half_coset_initial(log_size: int) -> int:
