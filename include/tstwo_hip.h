@@ -354,6 +354,35 @@ int tstwo_gather_words(const void *const *srcs, const uint64_t *idx, uint32_t wo
  * as a little-endian u128).  The reference's sequential loop returns the same (first) nonce.  Synchronises. */
 int tstwo_grind_blake2s(const uint8_t digest[32], uint32_t pow_bits, uint64_t start_nonce, uint64_t *nonce_out);
 
+/* ---------------------------------------------------------------- Poseidon252 Merkle channel
+ * The second MerkleChannel of the reference (vcs/poseidon252_merkle.ts, channel/poseidon.ts, backend/cpu/poseidon252.ts):
+ * Starknet's Poseidon over F_p, p = 2^251 + 17*2^192 + 1 (Hades permutation, width 3, 8 full + 83 partial rounds).
+ * An element (FieldElement252) in device memory and across this ABI is 8 little-endian uint32 limbs, least significant first,
+ * canonical (< p): 32 bytes, the size of a Blake2s digest.  A Poseidon tree therefore has exactly the tstwo_merkle_commit layout
+ * (layer k at byte 32*(2^k - 1), root first), and tstwo_merkle_decommit[_many], tstwo_gather_words and tstwo_fri_decommit work
+ * on its buffer unchanged: they only gather (the hash witness comes back as 32-byte limb records).
+ * hash_many(v) = poseidonHashMany (@scure/starknet, used by poseidon252_merkle.ts:52 and poseidon.ts:246,283): append 1, then
+ * 0 if the length is odd; from s = (0,0,0), per pair (x, y): s0 += x, s1 += y, permute; result s0.
+ * hashNode (vcs/poseidon252_merkle.ts:22-58): hash_many([left, right (if children)] + blocks), one block per 8 columns
+ * (zero-padded): sum of v_k * 2^(31*(7-k)), the first column most significant.
+ * tstwo_poseidon252_hash_many: message i = in[i*felts_per_msg .. (i+1)*felts_per_msg) (elements of 8 words, device, each
+ * canonical — not checked), out[i] = hash_many(message i) (device, 8 words each).  Asynchronous. */
+int tstwo_poseidon252_hash_many(const uint32_t *in, size_t n_msgs, uint32_t felts_per_msg, uint32_t *out);
+/* CpuPoseidon252MerkleOps.commitOnLayer (backend/cpu/poseidon252.ts:44-78): node i = hashNode((prev[2i], prev[2i+1]) or none,
+ * cols[..][i]), i < 2^log_size.  prev = NULL for the bottom layer.  out: 2^log_size * 32 bytes (device).  Asynchronous. */
+int tstwo_poseidon252_merkle_commit_layer(uint32_t log_size, const uint8_t *prev, const uint32_t *const *cols,
+                                          size_t n_cols, uint8_t *out);
+/* MerkleProver.commit (vcs/prover.ts:13-30) over Poseidon252: the contract of tstwo_merkle_commit (mixed sizes join at their
+ * layer, input order kept within a size class, layers buffer of tstwo_merkle_layers_bytes(max log) bytes, root (host, 32 bytes:
+ * the 8 limbs) may be NULL); n_cols == 0 gives hashNode(None, []) = hash_many([]). */
+int tstwo_poseidon252_merkle_commit(const uint32_t *const *cols, const uint32_t *log_sizes, size_t n_cols,
+                                    uint8_t *layers, uint8_t root[32]);
+/* GrindOps over Poseidon252Channel (backend/cpu/grind.ts:31-42): smallest nonce >= start_nonce such that mix_u64(nonce)
+ * (= mix_u32s([0,0,0,0,0,hi,lo]), channel/poseidon.ts:294-307: hash_many([digest, nonce])) gives a digest with at least
+ * pow_bits trailing zeros as channel/poseidon.ts:209-229 counts them: the first 16 bytes of the big-endian encoding read as a
+ * little-endian u128, so counting starts at bit 248 of the element.  digest: host, 8 limbs, canonical.  Synchronises. */
+int tstwo_grind_poseidon252(const uint32_t digest[8], uint32_t pow_bits, uint64_t start_nonce, uint64_t *nonce_out);
+
 /* ---------------------------------------------------------------- QuotientOps
  * accumulateQuotients row loop (backend/cpu/quotients.ts:52-116,160-178) with the per-batch constants
  * computed by the wrapper (quotientConstants, quotients.ts:124-191; constraints.ts:117-128):

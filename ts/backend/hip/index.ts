@@ -7,6 +7,8 @@ import { QM31 } from "../../fields/qm31";
 import type { Backend, Column } from "../index";
 import type { MerkleOps } from "../../vcs/ops";
 import { Blake2sHash } from "../../vcs/blake2_hash";
+import { FieldElement252, Poseidon252Channel } from "../../channel/poseidon";
+import type { Blake2sChannel } from "../../channel/blake2";
 import { quotientConstants, type ColumnSampleBatch } from "../cpu/quotients";
 import { CirclePoint, Coset } from "../../circle";
 import type { CircleDomain } from "../../poly/circle/domain";
@@ -421,6 +423,82 @@ export class HipMerkleProver {
         columnWitness: Array.from(colWit.subarray(0, nw), (v) => M31.from_u32_unchecked(v)) },
     ];
   }
+}
+
+/** FieldElement252 <-> the 8 little-endian u32 limbs (32 bytes) a Poseidon252 node has in device memory and across the C ABI. */
+function feltToLimbBytes(f: FieldElement252, out: Uint8Array, off: number): void {
+  let v = f.toBigInt();
+  for (let i = 0; i < 32; i++) { out[off + i] = Number(v & 0xffn); v >>= 8n; }
+}
+function feltFromLimbBytes(b: Uint8Array, off: number): FieldElement252 {
+  let v = 0n;
+  for (let i = 31; i >= 0; i--) v = (v << 8n) | BigInt(b[off + i]!);
+  return FieldElement252.from(v);
+}
+
+/** MerkleOps<FieldElement252> (backend/cpu/poseidon252.ts:44-78, CpuPoseidon252MerkleOps.commitOnLayer) as vcs/ops.ts declares it:
+ *  one layer per call, hashNode semantics of vcs/poseidon252_merkle.ts:22-58 (children, then one element per 8 columns). */
+export class HipPoseidon252MerkleOps implements MerkleOps<FieldElement252> {
+  commitOnLayer(logSize: number, prevLayer: readonly FieldElement252[] | undefined, columns: readonly (readonly M31[])[]): FieldElement252[] {
+    const n = 1 << logSize;
+    const devCols = columns.map((c) => ((c as unknown) instanceof HipColumn ? (c as unknown as HipColumn) : HipColumn.fromArray(c)));
+    devCols.forEach((c) => { if (c.len() !== n) throw new Error("column length does not match the layer size"); });
+    let prev: DeviceBuffer | undefined;
+    if (prevLayer !== undefined) {
+      if (prevLayer.length !== 2 * n) throw new Error("previous layer must have twice as many hashes");
+      const bytes = new Uint8Array(64 * n);
+      prevLayer.forEach((h, i) => feltToLimbBytes(h, bytes, 32 * i));
+      prev = new DeviceBuffer(64 * n);
+      prev.upload(bytes);
+    }
+    const out = new DeviceBuffer(32 << logSize);
+    check(hip.tstwo_poseidon252_merkle_commit_layer(logSize, prev ? prev.dev : 0n, ptr(ptrs(devCols.map((c) => c.dev))), BigInt(devCols.length), out.dev));
+    const flat = out.downloadBytes(32 * n);
+    return Array.from({ length: n }, (_, i) => feltFromLimbBytes(flat, 32 * i));
+  }
+}
+
+/** MerkleProver<FieldElement252> on the device (vcs/prover.ts over Poseidon252MerkleChannel): the tree has the layout of a Blake2s
+ *  tree (32-byte nodes, layer k at byte 32*(2^k-1)), so decommit reuses tstwo_merkle_decommit through HipMerkleProver and only
+ *  re-reads the 32-byte records as field elements. */
+export class HipPoseidon252MerkleProver {
+  private constructor(private readonly tree: HipMerkleProver, private readonly rootFelt: FieldElement252) {}
+  static commit(columns: readonly HipColumn[]): HipPoseidon252MerkleProver {
+    const logs = columns.map((c) => {
+      const lg = Math.log2(c.len());
+      if (!Number.isInteger(lg)) throw new Error("length is not power of two");
+      return lg;
+    });
+    const maxLog = columns.length ? Math.max(...logs) : 0;
+    const layers = new DeviceBuffer(32 * ((2 << maxLog) - 1)), root = new Uint8Array(32);
+    check(hip.tstwo_poseidon252_merkle_commit(ptr(ptrs(columns.map((c) => c.dev))), ptr(u32s(logs)), BigInt(columns.length), layers.dev, ptr(root)));
+    return new HipPoseidon252MerkleProver(HipMerkleProver.adopt(layers, maxLog), feltFromLimbBytes(root, 0));
+  }
+  static commitMany(columnSets: readonly (readonly HipColumn[])[]): HipPoseidon252MerkleProver[] {
+    return columnSets.map((cols) => HipPoseidon252MerkleProver.commit(cols));
+  }
+  root(): FieldElement252 { return this.rootFelt; }
+  rootDev(): bigint { return this.tree.rootDev(); }
+  get layers(): DeviceBuffer { return this.tree.layers; }
+  decommit(queriesPerLogSize: ReadonlyMap<number, number[]>, columns: readonly HipColumn[]):
+      [M31[], { hashWitness: FieldElement252[]; columnWitness: M31[] }] {
+    const [values, dec] = this.tree.decommit(queriesPerLogSize, columns);
+    return [values, { hashWitness: dec.hashWitness.map((h) => feltFromLimbBytes(h.bytes, 0)), columnWitness: dec.columnWitness }];
+  }
+}
+
+/** GrindOps.grind (backend/cpu/grind.ts:31-42) on the device, dispatched on the channel: the first nonce the sequential loop finds. */
+export function grind(channel: Blake2sChannel | Poseidon252Channel, powBits: number): number {
+  ensureInit();
+  const out = new BigUint64Array(1);
+  if (channel instanceof Poseidon252Channel) {
+    const limbs = new Uint8Array(32);
+    feltToLimbBytes(channel.digest(), limbs, 0);
+    check(hip.tstwo_grind_poseidon252(ptr(new Uint32Array(limbs.buffer)), powBits, 0n, ptr(out)));
+  } else {
+    check(hip.tstwo_grind_blake2s(ptr(channel.digest().bytes), powBits, 0n, ptr(out)));
+  }
+  return Number(out[0]);
 }
 
 /** One committed FRI layer as tstwo_fri_decommit sees it: the tree and the evaluations under it (first layer: the circle

@@ -31,8 +31,10 @@ from .poly import (CosetSubEvaluation, HipCircleEvaluation, HipCirclePoly, LineE
                    evaluate_polynomials, interpolate_columns, precompute_twiddles)
 from .quotients import (ColumnSampleBatch, accumulate, accumulateQuotients, generate_secure_powers,  # noqa: F401
                         quotientConstants)
-from .vcs import (Blake2sMerkleHasher, DeviceHashLayer, HipMerkleOps, MerkleDecommitment, MerkleProver,  # noqa: F401
-                  MerkleVerifier)
+from .vcs import (Blake2sMerkleChannel, Blake2sMerkleHasher, DeviceHashLayer, HipMerkleOps, MerkleDecommitment,  # noqa: F401
+                  MerkleProver, MerkleVerifier)
+from .poseidon import (DeviceFeltLayer, FieldElement252, HipPoseidon252MerkleOps, Poseidon252Channel,  # noqa: F401
+                       Poseidon252MerkleChannel, Poseidon252MerkleHasher, Poseidon252MerkleProver)
 
 __all__ = [n for n in dir() if not n.startswith("_")]
 from .semantics import get_semantics, set_semantics  # noqa: F401,E402

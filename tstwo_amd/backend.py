@@ -223,6 +223,17 @@ class HipBackend:
         from .gkr import HipMleOps
         return HipMleOps.fixFirstVariable(mle, assignment)
 
+    # --- MerkleOps<FieldElement252> (backend/cpu/poseidon252.ts: CpuBackend.poseidon252MerkleOps) and GrindOps
+    @property
+    def poseidon252MerkleOps(self):
+        from .poseidon import HipPoseidon252MerkleOps
+        return HipPoseidon252MerkleOps
+
+    def grind(self, channel, pow_bits: int) -> int:
+        """GrindOps.grind (backend/cpu/grind.ts:31-42) over a Blake2s or Poseidon252 channel."""
+        from .channel import HipGrindOps
+        return HipGrindOps.grind(channel, pow_bits)
+
     # --- helpers used by bench / drivers
     @staticmethod
     def canonic_half_coset_initial(log_size: int) -> int:

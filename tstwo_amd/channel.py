@@ -145,12 +145,16 @@ class HipGrindOps:
     sequential reference loop returns the same first nonce."""
 
     @staticmethod
-    def grind(channel: Blake2sChannel, pow_bits: int) -> int:
+    def grind(channel, pow_bits: int) -> int:
+        """Dispatches on the channel: Blake2sChannel (tstwo_grind_blake2s) or Poseidon252Channel (tstwo_grind_poseidon252)."""
         import ctypes as C
 
         import numpy as np
 
         from . import _lib as L
+        from .poseidon import Poseidon252Channel, grind_poseidon252
+        if isinstance(channel, Poseidon252Channel):
+            return grind_poseidon252(channel, pow_bits)
         L.ensure_init()
         d = np.frombuffer(channel.digest(), dtype=np.uint8).copy()
         out = C.c_uint64(0)
@@ -158,5 +162,5 @@ class HipGrindOps:
         return out.value
 
 
-def grind(channel: Blake2sChannel, pow_bits: int) -> int:
+def grind(channel, pow_bits: int) -> int:
     return HipGrindOps.grind(channel, pow_bits)

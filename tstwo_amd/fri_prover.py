@@ -17,7 +17,7 @@ from .queries import Queries, get_query_positions_by_log_size
 from .fields import M31, P, QM31
 from .fri import CIRCLE_TO_LINE_FOLD_STEP, HipFriOps
 from .poly import LineEvaluation, SecureEvaluation, TwiddleTree
-from .vcs import DeviceHashLayer, HashSlices, M31Values, MerkleDecommitment, MerkleProver, TreeLayers
+from .vcs import Blake2sMerkleChannel, DeviceHashLayer, M31Values, MerkleDecommitment, MerkleProver, TreeLayers
 
 FOLD_STEP = 1
 
@@ -282,11 +282,12 @@ FriLayer = FriInnerLayerProver
 
 
 class _HostTranscript:
-    """mix_root / draw_felt on the host channel: one 32-byte root read-back per layer."""
+    """mix_root / draw_felt on the host channel: one 32-byte root read-back per layer.  `prover` commits the layers' trees (the
+    Merkle channel's: Blake2s by default, Poseidon252MerkleProver for a Poseidon252 channel)."""
     sync_root = True
 
-    def __init__(self, channel):
-        self.channel = channel
+    def __init__(self, channel, prover=MerkleProver):
+        self.channel, self.prover = channel, prover
 
     def mix_and_draw(self, tree):
         self.channel.mix_root(tree.root())
@@ -299,6 +300,7 @@ class _HostTranscript:
 class _DeviceTranscript:
     """mix_root / draw_felt by the device channel: alpha k lands in slot k of `alphas`; nothing is read back."""
     sync_root = False
+    prover = MerkleProver
 
     def __init__(self, dch: DeviceChannel, alphas):
         self.dch, self.alphas, self.k = dch, alphas, 0
@@ -318,8 +320,10 @@ class FriProver:
         self.config, self.first_layer, self.inner_layers, self.last_layer_poly = config, first_layer, inner_layers, last_layer_coeffs
 
     @staticmethod
-    def commit(channel, config: FriConfig, columns, twiddles: TwiddleTree, device_channel: bool = True) -> "FriProver":
-        """columns: SecureEvaluation list, canonic domains, strictly decreasing sizes (fri.ts:644-674)."""
+    def commit(channel, config: FriConfig, columns, twiddles: TwiddleTree, device_channel: bool = True, merkle_channel=None) -> "FriProver":
+        """columns: SecureEvaluation list, canonic domains, strictly decreasing sizes (fri.ts:644-674).  merkle_channel: the
+        Merkle channel of the layer trees (default Blake2sMerkleChannel; Poseidon252MerkleChannel keeps the transcript on the
+        host: the device channel and tstwo_fri_commit_layers are Blake2s only)."""
         if not columns:
             raise ValueError("no columns")
         if not all(c.domain.isCanonic() for c in columns):
@@ -330,7 +334,8 @@ class FriProver:
         # Device transcript: when every fold can take its twiddles from the tree and the channel has Rust semantics, the whole
         # commit loop is one launch sequence — roots are mixed and alphas drawn by the device channel, nothing is read back
         # until the last layer.  Otherwise: the host channel, one 32-byte read-back per layer.
-        on_device = (device_channel and not getattr(channel, "ts_compat", False) and hasattr(channel, "_digest")
+        prover = (merkle_channel or Blake2sMerkleChannel).prover
+        on_device = (device_channel and prover is MerkleProver and not getattr(channel, "ts_compat", False) and hasattr(channel, "_digest")
                      and FriProver._device_capable(columns, twiddles))
         if device_channel and getattr(channel, "ts_compat", False):
             # the device channel implements Rust's draw_felt only: say so instead of silently taking the slower path
@@ -349,7 +354,7 @@ class FriProver:
                 first_layer, inner, layer_eval = FriProver._commit_layers_in_library(config, columns, twiddles, dch, alphas)
             prefetched = FriProver._fetch_end_of_commit(dch, layer_eval, twiddles)
         else:
-            first_layer, inner, layer_eval = FriProver._commit_layers(config, columns, twiddles, _HostTranscript(channel))
+            first_layer, inner, layer_eval = FriProver._commit_layers(config, columns, twiddles, _HostTranscript(channel, prover))
             prefetched = None
         last = FriProver._commit_last_layer(channel, config, layer_eval, twiddles, prefetched)
         return FriProver(config, first_layer, inner, last)
@@ -434,7 +439,7 @@ class FriProver:
         first_log = (folded(columns[0])).bit_length() - 1
         # first layer: one tree over every column's coordinate columns (Rust FriFirstLayerProver::new), root -> channel
         coord_cols = [cc for c in columns for cc in c.values.columns]
-        first_tree = MerkleProver.commit(coord_cols, sync_root=transcript.sync_root)
+        first_tree = transcript.prover.commit(coord_cols, sync_root=transcript.sync_root)
         alpha = transcript.mix_and_draw(first_tree)
         first_layer = FriFirstLayerProver(columns, first_tree)
         layer_eval = LineEvaluation.new_zero(LineDomain(Coset.half_odds(first_log)))
@@ -443,7 +448,7 @@ class FriProver:
         nxt = next(it, None)
         inner = []
         while layer_eval.len() > config.last_layer_domain_size():
-            tree = MerkleProver.commit(layer_eval.values.columns, sync_root=transcript.sync_root)      # FriInnerLayerProver::new
+            tree = transcript.prover.commit(layer_eval.values.columns, sync_root=transcript.sync_root)      # FriInnerLayerProver::new
             alpha = transcript.mix_and_draw(tree)
             layer = FriInnerLayerProver(layer_eval, tree)
             layer_eval = transcript.fold_line(layer_eval, alpha, twiddles)
@@ -532,8 +537,9 @@ class FriProver:
         proofs, e0, h0, w0 = [], 0, 0, 0
         for r, layer in enumerate(layers):
             ne, nh, nw = counts[3 * r], counts[3 * r + 1], counts[3 * r + 2]
-            dec = MerkleDecommitment(HashSlices(hb[32 * h0:32 * (h0 + nh)], nh), M31Values(wl[w0:w0 + nw]))
-            layer.merkle_tree._root = rb[32 * r:32 * r + 32]          # (what root() would read back: 32 bytes per tree)
+            tree = layer.merkle_tree
+            dec = MerkleDecommitment(tree._hashes_of(hb[32 * h0:32 * (h0 + nh)], nh), M31Values(wl[w0:w0 + nw]))
+            tree._root = tree._hash_of(rb[32 * r:32 * r + 32])          # (what root() would read back: 32 bytes per tree)
             proofs.append(FriLayerProof(QM31Rows(ev[e0:e0 + ne]), dec, layer.merkle_tree._root))
             e0, h0, w0 = e0 + ne, h0 + nh, w0 + nw
         return FriProof(proofs[0], proofs[1:], self.last_layer_poly)

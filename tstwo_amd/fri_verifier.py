@@ -14,7 +14,7 @@ from .fields import QM31
 from .fri import CIRCLE_TO_LINE_FOLD_STEP
 from .fri_prover import FOLD_STEP, FriConfig, FriProof
 from .queries import Queries, get_query_positions_by_log_size
-from .vcs import Blake2sMerkleHasher, MerkleVerifier
+from .vcs import Blake2sMerkleChannel, Blake2sMerkleHasher, MerkleVerifier
 
 SECURE_EXTENSION_DEGREE = 4
 
@@ -131,9 +131,9 @@ def _flatten_m31(sparse: SparseEvaluation) -> list:
 
 
 class FriFirstLayerVerifier:
-    def __init__(self, column_bounds, column_commitment_domains, folding_alpha, proof):
+    def __init__(self, column_bounds, column_commitment_domains, folding_alpha, proof, hasher=Blake2sMerkleHasher):
         self.column_bounds, self.column_commitment_domains = column_bounds, column_commitment_domains
-        self.folding_alpha, self.proof = folding_alpha, proof
+        self.folding_alpha, self.proof, self.hasher = folding_alpha, proof, hasher
 
     def verify(self, queries: Queries, query_evals_by_column) -> list:
         max_log = self.column_commitment_domains[0].logSize()
@@ -153,7 +153,7 @@ class FriFirstLayerVerifier:
             sparse_by_column.append(sparse)
         if next(witness, None) is not None:                                     # proof holds too many evaluations
             raise FriVerificationError(FriVerificationError.FirstLayerEvaluationsInvalid)
-        mv = MerkleVerifier(Blake2sMerkleHasher, self.proof.commitment,
+        mv = MerkleVerifier(self.hasher, self.proof.commitment,
                             [d.logSize() for d in self.column_commitment_domains for _ in range(SECURE_EXTENSION_DEGREE)])
         try:
             mv.verify(positions_by_log, values, self.proof.decommitment)
@@ -163,9 +163,9 @@ class FriFirstLayerVerifier:
 
 
 class FriInnerLayerVerifier:
-    def __init__(self, degree_bound, domain: LineDomain, folding_alpha, layer_index: int, proof):
+    def __init__(self, degree_bound, domain: LineDomain, folding_alpha, layer_index: int, proof, hasher=Blake2sMerkleHasher):
         self.degree_bound, self.domain, self.folding_alpha = degree_bound, domain, folding_alpha
-        self.layer_index, self.proof = layer_index, proof
+        self.layer_index, self.proof, self.hasher = layer_index, proof, hasher
 
     def verify_and_fold(self, queries: Queries, evals_at_queries) -> tuple:
         assert queries.log_domain_size == self.domain.logSize()
@@ -176,7 +176,7 @@ class FriInnerLayerVerifier:
             raise FriVerificationError(f"{FriVerificationError.InnerLayerEvaluationsInvalid} {self.layer_index}") from None
         if next(witness, None) is not None:
             raise FriVerificationError(f"{FriVerificationError.InnerLayerEvaluationsInvalid} {self.layer_index}")
-        mv = MerkleVerifier(Blake2sMerkleHasher, self.proof.commitment, [self.domain.logSize()] * SECURE_EXTENSION_DEGREE)
+        mv = MerkleVerifier(self.hasher, self.proof.commitment, [self.domain.logSize()] * SECURE_EXTENSION_DEGREE)
         try:
             mv.verify({self.domain.logSize(): pos}, _flatten_m31(sparse), self.proof.decommitment)
         except ValueError as e:
@@ -195,20 +195,22 @@ class FriVerifier:
         self.queries = None
 
     @staticmethod
-    def commit(channel, config: FriConfig, proof: FriProof, column_bounds) -> "FriVerifier":
+    def commit(channel, config: FriConfig, proof: FriProof, column_bounds, merkle_channel=None) -> "FriVerifier":
+        """merkle_channel: the Merkle channel the layers were committed with (default Blake2sMerkleChannel)."""
+        hasher = (merkle_channel or Blake2sMerkleChannel).hasher
         for a, b in zip(column_bounds, column_bounds[1:]):
             if a.log_degree_bound < b.log_degree_bound:
                 raise FriVerificationError(FriVerificationError.InvalidNumFriLayers)
         channel.mix_root(proof.first_layer.commitment)
         max_bound = column_bounds[0]
         domains = [CanonicCoset(b.log_degree_bound + config.log_blowup_factor).circle_domain() for b in column_bounds]
-        first = FriFirstLayerVerifier(column_bounds, domains, channel.draw_felt(), proof.first_layer)
+        first = FriFirstLayerVerifier(column_bounds, domains, channel.draw_felt(), proof.first_layer, hasher)
         inner = []
         layer_bound = max_bound.fold_to_line()
         layer_domain = LineDomain(Coset.half_odds(layer_bound.log_degree_bound + config.log_blowup_factor))
         for i, lp in enumerate(proof.inner_layers):
             channel.mix_root(lp.commitment)
-            inner.append(FriInnerLayerVerifier(layer_bound, layer_domain, channel.draw_felt(), i, lp))
+            inner.append(FriInnerLayerVerifier(layer_bound, layer_domain, channel.draw_felt(), i, lp, hasher))
             layer_bound = layer_bound.fold(FOLD_STEP)
             if layer_bound is None:
                 raise FriVerificationError(FriVerificationError.InvalidNumFriLayers)

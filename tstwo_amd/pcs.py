@@ -14,7 +14,7 @@ from .fields import QM31
 from .fri_prover import FriConfig, FriProof, FriProver
 from .poly import HipCirclePoly, TwiddleTree, evaluate_polynomials, interpolate_columns
 from .quotients import ColumnSampleBatch, accumulateQuotients
-from .vcs import MerkleProver
+from .vcs import Blake2sMerkleChannel, MerkleProver
 
 
 @dataclass
@@ -85,7 +85,7 @@ class CommitmentTreeProver:
         self.polynomials, self.evaluations, self.commitment = polynomials, evaluations, commitment
 
     @staticmethod
-    def new(polynomials, log_blowup_factor: int, channel, twiddles: TwiddleTree) -> "CommitmentTreeProver":
+    def new(polynomials, log_blowup_factor: int, channel, twiddles: TwiddleTree, prover=MerkleProver) -> "CommitmentTreeProver":
         # "Extension": each poly is evaluated on the canonic domain of log size (poly log size + blowup); polys of one
         # size share a batched launch sequence (PolyOps.evaluatePolynomials)
         by_size = {}
@@ -97,12 +97,12 @@ class CommitmentTreeProver:
             for i, ev in zip(idxs, evaluate_polynomials([polynomials[i] for i in idxs], domain, twiddles)):
                 evaluations[i] = ev
         # "Merkle"
-        tree = MerkleProver.commit([ev.values for ev in evaluations])
+        tree = prover.commit([ev.values for ev in evaluations])
         channel.mix_root(tree.root())
         return CommitmentTreeProver(list(polynomials), evaluations, tree)
 
     @staticmethod
-    def new_many(polynomial_sets, log_blowup_factor: int, channel, twiddles: TwiddleTree) -> list:
+    def new_many(polynomial_sets, log_blowup_factor: int, channel, twiddles: TwiddleTree, prover=MerkleProver) -> list:
         """Several trees committed in ONE protocol phase (stwo's TreeVec: pcs/prover.ts:62-64 pushes a CommitmentTreeProver per
         tree, each mixing its root, :227-228) — the same transcript as new() tree by tree, because nothing is drawn between the
         commits of a phase: the roots are mixed in tree order once they exist.  Every polynomial of every tree goes through one
@@ -122,7 +122,7 @@ class CommitmentTreeProver:
         for ps in polynomial_sets:
             per_tree.append(evaluations[k:k + len(ps)])
             k += len(ps)
-        trees = MerkleProver.commit_many([[ev.values for ev in evs] for evs in per_tree])
+        trees = prover.commit_many([[ev.values for ev in evs] for evs in per_tree])
         for t in trees:
             channel.mix_root(t.root())
         return [CommitmentTreeProver(ps, evs, t) for ps, evs, t in zip(polynomial_sets, per_tree, trees)]
@@ -154,23 +154,25 @@ class TreeBuilder:
 class CommitmentSchemeProver:
     """pcs/prover.ts:26-80 (Rust comment): a list of commitment trees sharing one twiddle tree."""
 
-    def __init__(self, config, twiddles: TwiddleTree):
-        """config: a PcsConfig (as in Rust) or, for commitment-only use, just the log blowup factor."""
+    def __init__(self, config, twiddles: TwiddleTree, merkle_channel=None):
+        """config: a PcsConfig (as in Rust) or, for commitment-only use, just the log blowup factor.  merkle_channel: the Merkle
+        channel of every tree (default Blake2sMerkleChannel; Poseidon252MerkleChannel for a proof verified on Starknet)."""
         if isinstance(config, int):
             config = PcsConfig(fri_config=FriConfig(0, config, 3))
         self.config, self.twiddles, self.trees = config, twiddles, []
+        self.merkle_channel = merkle_channel or Blake2sMerkleChannel
         self.log_blowup_factor = config.fri_config.log_blowup_factor
 
     def tree_builder(self) -> TreeBuilder:
         return TreeBuilder(self)
 
     def commit(self, polynomials, channel) -> None:
-        self.trees.append(CommitmentTreeProver.new(polynomials, self.log_blowup_factor, channel, self.twiddles))
+        self.trees.append(CommitmentTreeProver.new(polynomials, self.log_blowup_factor, channel, self.twiddles, self.merkle_channel.prover))
 
     def commit_many(self, polynomial_sets, channel) -> None:
         """The trees of one phase committed together (CommitmentTreeProver.new_many): same trees, roots and transcript as one
         commit() per set."""
-        self.trees += CommitmentTreeProver.new_many(polynomial_sets, self.log_blowup_factor, channel, self.twiddles)
+        self.trees += CommitmentTreeProver.new_many(polynomial_sets, self.log_blowup_factor, channel, self.twiddles, self.merkle_channel.prover)
 
     def roots(self) -> list:
         return [t.commitment.root() for t in self.trees]
@@ -208,12 +210,12 @@ class CommitmentSchemeProver:
         flat_samples = [col for tree in samples for col in tree]
         quotients = compute_fri_quotients(columns, flat_samples, channel.draw_felt(), self.log_blowup_factor)
         # FRI commitment phase on the quotients
-        fri_prover = FriProver.commit(channel, self.config.fri_config, quotients, self.twiddles)
+        fri_prover = FriProver.commit(channel, self.config.fri_config, quotients, self.twiddles, merkle_channel=self.merkle_channel)
         # proof of work
         proof_of_work = grind(channel, self.config.pow_bits)
         channel.mix_u64(proof_of_work)
         # FRI decommitment phase, then the trace trees on the same queries
         fri_proof, query_positions = fri_prover.decommit(channel)
-        results = MerkleProver.decommit_many([(t.commitment, query_positions, [ev.values for ev in t.evaluations]) for t in self.trees])
+        results = self.merkle_channel.prover.decommit_many([(t.commitment, query_positions, [ev.values for ev in t.evaluations]) for t in self.trees])
         return CommitmentSchemeProof(self.config, self.roots(), sampled_values, [d for _, d in results],
                                      [v for v, _ in results], proof_of_work, fri_proof)

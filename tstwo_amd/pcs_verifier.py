@@ -10,7 +10,7 @@ from .fields import CM31, M31, QM31
 from .fri_verifier import CirclePolyDegreeBound, FriVerifier
 from .pcs import CommitmentSchemeProof, PcsConfig, PointSample, column_sample_batches
 from .quotients import quotientConstants
-from .vcs import Blake2sMerkleHasher, MerkleVerifier
+from .vcs import Blake2sMerkleChannel, MerkleVerifier
 
 
 class VerificationError(Exception):
@@ -87,8 +87,10 @@ def fri_answers(column_log_sizes, samples, random_coeff, query_positions_per_log
 class CommitmentSchemeVerifier:
     """pcs/verifier.ts Rust text :19-124."""
 
-    def __init__(self, config: PcsConfig):
+    def __init__(self, config: PcsConfig, merkle_channel=None):
+        """merkle_channel: the Merkle channel the prover committed with (default Blake2sMerkleChannel)."""
         self.config, self.trees = config, []
+        self.merkle_channel = merkle_channel or Blake2sMerkleChannel
 
     def column_log_sizes(self) -> list:
         return [list(t.columnLogSizes) for t in self.trees]
@@ -96,7 +98,7 @@ class CommitmentSchemeVerifier:
     def commit(self, commitment: bytes, log_sizes, channel) -> None:
         channel.mix_root(commitment)
         ext = [lg + self.config.fri_config.log_blowup_factor for lg in log_sizes]
-        self.trees.append(MerkleVerifier(Blake2sMerkleHasher, commitment, ext))
+        self.trees.append(MerkleVerifier(self.merkle_channel.hasher, commitment, ext))
 
     def verify_values(self, sampled_points, proof: CommitmentSchemeProof, channel) -> None:
         channel.mix_felts([v for tree in proof.sampled_values for col in tree for v in col])
@@ -104,7 +106,7 @@ class CommitmentSchemeVerifier:
         blow = self.config.fri_config.log_blowup_factor
         sizes = sorted({lg for tree in self.column_log_sizes() for lg in tree}, reverse=True)
         bounds = [CirclePolyDegreeBound(lg - blow) for lg in sizes]
-        fri_verifier = FriVerifier.commit(channel, self.config.fri_config, proof.fri_proof, bounds)
+        fri_verifier = FriVerifier.commit(channel, self.config.fri_config, proof.fri_proof, bounds, self.merkle_channel)
         channel.mix_u64(proof.proof_of_work)
         if channel.trailing_zeros() < self.config.pow_bits:
             raise VerificationError(VerificationError.ProofOfWork)

@@ -126,6 +126,11 @@ class TreeLayers(_LazyList):
 class MerkleProver:
     """MerkleProver.commit / root (vcs/prover.ts:13-30,111-113): layers[0] = [root], all layers retained on device."""
 
+    # how a 32-byte node record read back from the device becomes a hash of this tree's kind (Blake2s: the bytes themselves);
+    # Poseidon252MerkleProver (poseidon.py) turns them into FieldElement252
+    _hash_of = staticmethod(bytes)
+    _hashes_of = HashSlices
+
     def __init__(self, layers: list, buf: L.DeviceBuffer, root: bytes):
         self.layers, self._buf, self._root = layers, buf, root
 
@@ -177,7 +182,7 @@ class MerkleProver:
 
     def root(self) -> bytes:
         if self._root is None:                      # committed asynchronously (sync_root=False): fetch the 32 bytes now
-            self._root = self._buf.download(np.uint8, 32).tobytes()
+            self._root = self._hash_of(self._buf.download(np.uint8, 32).tobytes())
         return self._root
 
     def root_ptr(self) -> int:
@@ -208,7 +213,7 @@ class MerkleProver:
                queried.ctypes.data_as(L.u32p), C.byref(n_q), hashes.ctypes.data_as(L.u8p), C.byref(n_h),
                colwit.ctypes.data_as(L.u32p), C.byref(n_w))
         hb = hashes.tobytes()
-        dec = MerkleDecommitment(HashSlices(hb, n_h.value), M31Values(colwit[:n_w.value].tolist()))
+        dec = MerkleDecommitment(self._hashes_of(hb, n_h.value), M31Values(colwit[:n_w.value].tolist()))
         # (FRI layers already hold their queried evaluations: want_queried=False skips the queried values)
         return (M31Values(queried[:n_q.value].tolist()) if want_queried else None), dec
 
@@ -248,7 +253,7 @@ class MerkleProver:
         ql, wl = queried.tolist() if want_queried else None, colwit[:totals[2]].tolist()
         for r in range(len(requests)):
             nq_, nh_, nw_ = counts[3 * r], counts[3 * r + 1], counts[3 * r + 2]
-            dec = MerkleDecommitment(HashSlices(hb[32 * h0:32 * (h0 + nh_)], nh_), M31Values(wl[w0:w0 + nw_]))
+            dec = MerkleDecommitment(requests[r][0]._hashes_of(hb[32 * h0:32 * (h0 + nh_)], nh_), M31Values(wl[w0:w0 + nw_]))
             out.append((M31Values(ql[q0:q0 + nq_]) if want_queried else None, dec))
             q0, h0, w0 = q0 + nq_, h0 + nh_, w0 + nw_
         return out
@@ -261,7 +266,7 @@ class MerkleProver:
         hashes = _gather([(self.layers[lg].ptr, node) for lg, node in hreq], 8)
         vals = _gather([(cols[c].ptr, node) for c, node in qreq + wreq], 1)
         nq = len(qreq)
-        dec = MerkleDecommitment([hashes[8 * i:8 * i + 8].tobytes() for i in range(len(hreq))], [M31(int(v)) for v in vals[nq:]])
+        dec = MerkleDecommitment([self._hash_of(hashes[8 * i:8 * i + 8].tobytes()) for i in range(len(hreq))], [M31(int(v)) for v in vals[nq:]])
         return [M31(int(v)) for v in vals[:nq]], dec
 
 
@@ -364,6 +369,19 @@ class Blake2sMerkleHasher:
         for v in column_values:
             h.update(int(v.value if isinstance(v, M31) else v).to_bytes(4, "little"))
         return h.digest()
+
+
+class Blake2sMerkleChannel:
+    """Blake2sMerkleChannel (vcs/blake2_merkle.ts:26-32), with the hasher and prover of its trees: the default Merkle channel of
+    CommitmentSchemeProver / FriProver and their verifiers (poseidon.py has the other one, Poseidon252MerkleChannel)."""
+    hasher = Blake2sMerkleHasher
+    prover = MerkleProver
+
+    @staticmethod
+    def mix_root(channel, root: bytes) -> None:
+        channel.mix_root(root)
+
+    mixRoot = mix_root
 
 
 class MerkleVerifier:
