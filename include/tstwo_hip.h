@@ -480,6 +480,26 @@ int tstwo_gkr_round(uint32_t kind, const uint32_t *const eq[4], const uint32_t *
 int tstwo_mle_fix_first_variable_base(const uint32_t *in, uint32_t log_n, const uint32_t r[4], uint32_t *const out[4]);
 int tstwo_mle_fix_first_variable_secure(const uint32_t *const in[4], uint32_t log_n, const uint32_t r[4], uint32_t *const out[4]);
 
+/* ---------------------------------------------------------------- AIR (constraint evaluation, composition polynomial)
+ * Rust stwo constraint_framework/component.rs (the reference's constraint_framework/index.ts, air/accumulator.ts,
+ * examples/fibonacci.ts).  Constraints read only their own row (mask offset 0).  Kinds for the `kind` argument: */
+#define TSTWO_AIR_WIDE_FIB 0               /* N >= 3 columns: c_i = x_{i+2} - (x_i^2 + x_{i+1}^2), i < N - 2 (WideFibonacciEval<N>) */
+#define TSTWO_AIR_MUL_ADD 1                /* 3 columns: c_0 = x_0 x_1 + x_0 - x_2 (TestEval of the Rust tutorial's example 05) */
+/* generateTrace (examples/fibonacci.ts; Rust examples/wide_fibonacci generate_trace): cols[0] = a, cols[1] = b,
+ * cols[k] = cols[k-2]^2 + cols[k-1]^2 for k < n_cols; every column 2^log_n words (device), n_cols >= 2.  Column tables beyond
+ * 64 pointers are refused during graph capture. */
+int tstwo_air_wide_fib_trace(const uint32_t *a, const uint32_t *b, uint32_t log_n, uint32_t *const *cols, size_t n_cols);
+/* FrameworkComponent::evaluate_constraint_quotients_on_domain (constraint_framework/component.rs, CPU/SIMD loop): cols = the
+ * component's trace on CanonicCoset(trace_log_size + log_expand).circle_domain(), bit-reversed order (device).  For every row r:
+ *   accum[r] += (sum_i coeffs_i c_i(r)) * denom_inv[r >> trace_log_size]
+ * coeffs: n_constraints QM31 values (4 host words each, n_constraints <= 128); denom_inv: 2^log_expand M31 host words
+ * (log_expand <= 4), the bit-reversed 1 / coset_vanishing(trace coset, eval_domain.at(j)); accum: SecureColumnByCoords of
+ * 2^(trace_log_size + log_expand) values, added to (not overwritten).  Column tables beyond 64 pointers are refused during graph
+ * capture. */
+int tstwo_air_constraint_quotients(uint32_t kind, const uint32_t *const *cols, size_t n_cols, uint32_t trace_log_size,
+                                   uint32_t log_expand, const uint32_t *coeffs, size_t n_constraints, const uint32_t *denom_inv,
+                                   uint32_t *const accum[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,7 +153,26 @@ export class HipBackend implements Backend {
     else check(hip.tstwo_mle_fix_first_variable_secure(ptr(mle.ptrs()), logN, ptr(q4(assignment)), ptr(out.ptrs())));
     return out;
   }
+  // AIR (constraint_framework/index.ts, examples/fibonacci.ts; the prover around them: tstwo_amd/air.py and tstwo_amd/prover.py)
+  /** generateTrace of wide Fibonacci on the device: x_0 = a, x_1 = b, x_k = x_{k-2}^2 + x_{k-1}^2, nColumns columns of a.len(). */
+  generateWideFibTrace(a: HipColumn, b: HipColumn, nColumns: number): HipColumn[] {
+    const out = Array.from({ length: nColumns }, () => HipColumn.uninitialized(a.len()));
+    check(hip.tstwo_air_wide_fib_trace(a.dev, b.dev, Math.log2(a.len()), ptr(ptrs(out.map((c) => c.dev))), BigInt(nColumns)));
+    return out;
+  }
+  /** evaluate_constraint_quotients_on_domain of one component: accum[r] += sum_i coeffs[i] c_i(r) * denomInv[r >> traceLogSize], over
+   *  the trace on the evaluation domain of log size traceLogSize + log2(denomInv.length) (bit-reversed). */
+  evaluateConstraintQuotients(kind: AirKind, trace: readonly HipColumn[], traceLogSize: number, coeffs: readonly QM31[],
+                              denomInv: readonly M31[], accum: HipSecureColumn): void {
+    const words = new Uint32Array(Math.max(4 * coeffs.length, 4));
+    coeffs.forEach((c, i) => words.set(q4(c), 4 * i));
+    check(hip.tstwo_air_constraint_quotients(kind, ptr(ptrs(trace.map((c) => c.dev))), BigInt(trace.length), traceLogSize,
+      Math.log2(denomInv.length), ptr(words), BigInt(coeffs.length), ptr(u32s(denomInv.map((d) => d.value))), ptr(accum.ptrs())));
+  }
 }
+
+/** Constraint kinds of tstwo_air_constraint_quotients (TSTWO_AIR_* in include/tstwo_hip.h). */
+export enum AirKind { WideFibonacci = 0, MulAdd = 1 }
 
 /** Layer kinds of the GKR entry points (TSTWO_GKR_* in include/tstwo_hip.h; gkr_prover.ts Layer). */
 export enum GkrLayerKind { GrandProduct = 0, LogUpGeneric = 1, LogUpMultiplicities = 2, LogUpSingles = 3 }

@@ -35,6 +35,10 @@ from .vcs import (Blake2sMerkleChannel, Blake2sMerkleHasher, DeviceHashLayer, Hi
                   MerkleProver, MerkleVerifier)
 from .poseidon import (DeviceFeltLayer, FieldElement252, HipPoseidon252MerkleOps, Poseidon252Channel,  # noqa: F401
                        Poseidon252MerkleChannel, Poseidon252MerkleHasher, Poseidon252MerkleProver)
+from .air import (ColumnAccumulator, ComponentProvers, Components, DomainEvaluationAccumulator, FrameworkComponent,  # noqa: F401
+                  MulAddComponent, PointEvaluationAccumulator, Trace, TraceLocationAllocator, WideFibonacciComponent,
+                  coset_vanishing, generate_wide_fib_trace)
+from .prover import ConstraintsNotSatisfied, InvalidStructure, OodsNotMatching, StarkProof, prove, verify  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]
 from .semantics import get_semantics, set_semantics  # noqa: F401,E402
