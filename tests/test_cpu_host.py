@@ -553,10 +553,10 @@ def test_bench_launcher_relays_rank_failure(tmp_path):
     assert p.returncode == 7 and time.time() - t0 < 40 and "rank 1 exited with 7" in p.stderr
 
 
-def test_shipped_library_has_no_experiment_switches():
+def test_libraries_read_only_the_kept_switches():
     """The drop-in .so must not change results or kernel plans because of its caller's environment (round 3: 36 TSTWO_* variables,
-    one of which skipped a CFFT pass).  The shipped build keeps the loader / allocator variables and nothing else; the tuning and
-    A/B switches exist only in the experiments build (-DTSTWO_EXPERIMENTS), where they are read once."""
+    one of which skipped a CFFT pass).  The shipped build keeps the loader / allocator variables and nothing else; the launch-shape
+    parameters of plan sweeps exist only in the experiments build (-DTSTWO_EXPERIMENTS), where they are read once."""
     import re
     from tstwo_amd import _lib as L
     allowed = {"TSTWO_ALLOC", "TSTWO_NO_POOL", "TSTWO_POISON", "TSTWO_ALLOW_UNSAFE_ASYNC_ALLOC", "TSTWO_ASYNC_RELEASE", "TSTWO_RCCL_LIB"}
@@ -564,7 +564,17 @@ def test_shipped_library_has_no_experiment_switches():
     shipped = {n for n in names(L.LIB_PATH) if not n.startswith(("TSTWO_ERR_", "TSTWO_ALLOC_"))}
     assert shipped <= allowed, sorted(shipped - allowed)
     if os.path.exists(L.LIB_EXP_PATH):
-        assert {"TSTWO_CFFT_GENERIC", "TSTWO_MERKLE_SUBTREE", "TSTWO_FRI_NO_TAIL"} <= names(L.LIB_EXP_PATH)
+        assert {"TSTWO_CFFT_KB", "TSTWO_CFFT_KA", "TSTWO_MERKLE_CAP", "TSTWO_FOLD_CAP"} <= names(L.LIB_EXP_PATH)
+    # the A/B switches of kernel variants that lost their measurement were removed with the variants: neither build reads them
+    removed = {"TSTWO_CFFT_B8", "TSTWO_CFFT_AV", "TSTWO_CFFT_GENERIC", "TSTWO_CFFT_GROUP", "TSTWO_CFFT_NO_OOP", "TSTWO_CFFT_NO_FUSED_EXTEND",
+               "TSTWO_MERKLE_UP_ONELANE", "TSTWO_MERKLE_UP_SMALLWG", "TSTWO_MERKLE_UP_NARROW_FIRST", "TSTWO_MERKLE_UP_LOG",
+               "TSTWO_MERKLE_SUBTREE", "TSTWO_MERKLE_SUBTREE_LANE_STRIDE", "TSTWO_MERKLE_GENERIC", "TSTWO_MERKLE_NO_FUSED_LEAF4",
+               "TSTWO_MERKLE_NO_BATCH", "TSTWO_FRI_NO_TAIL", "TSTWO_FRI_NO_FOLD_FUSION", "TSTWO_FOLD1", "TSTWO_QINV_MONTGOMERY",
+               "TSTWO_QINV_K", "TSTWO_QUOT_NO_LAZY", "TSTWO_QUOT_NO_PAIR", "TSTWO_QUOT_NO_ROWPAIR", "TSTWO_QUOT_NO_TRIPLE",
+               "TSTWO_DEVICE_FLAG", "TSTWO_NO_FAST_WAIT"}
+    for path in (L.LIB_PATH, L.LIB_EXP_PATH):
+        if os.path.exists(path):
+            assert not names(path) & removed, (path, sorted(names(path) & removed))
     # and in the sources: no getenv outside context.hip's allocator / comm.hip's loader and the #ifdef TSTWO_EXPERIMENTS block
     csrc = os.path.join(ROOT, "tstwo_amd", "csrc")
     outside = 0

@@ -398,38 +398,6 @@ def test_qm31_mul_edge_grid():
         assert (host(do[k], n) == exp[k]).all()
 
 
-_SUBTREE_SCRIPT = r"""
-import hashlib, sys
-sys.path[:0] = [{root!r}, {tests!r}]
-from test_gpu_capi import rand_column, merkle_commit
-log = 19
-cols = [rand_column(900 + c, 1 << log) for c in range(4)]
-layers, root = merkle_commit(cols, [log] * 4)
-print(bytes(root).hex(), hashlib.blake2s(b"".join(l.tobytes() for l in layers)).hexdigest())
-"""
-
-
-@pytest.mark.parametrize("levels", ["0", "3", "4", "2-lane-stride"])
-def test_merkle_subtree_levels_agree(levels):
-    """TSTWO_MERKLE_SUBTREE (experiments build only; read once per process): every setting (layer per launch, 3 and 4 layers per
-    in-lane subtree; 2 is the default the other tests run) must give the oracle's tree."""
-    import os
-    import subprocess
-    import sys
-    log = 19
-    cols = [rand_column(900 + c, 1 << log) for c in range(4)]
-    olayers, oroot = orc.merkle_commit(cols, [log] * 4)
-    want = bytes(oroot).hex() + " " + hashlib.blake2s(b"".join(l.tobytes() for l in olayers)).hexdigest()
-    tests_dir = os.path.dirname(os.path.abspath(__file__))
-    script = _SUBTREE_SCRIPT.format(root=os.path.dirname(tests_dir), tests=tests_dir)
-    env = dict(os.environ, TSTWO_MERKLE_SUBTREE=levels, TSTWO_HIP_LIB=L.LIB_EXP_PATH)
-    if levels == "2-lane-stride":         # round 3's two-level kernel (lane-strided accesses) instead of the coalesced k_merkle_subtree2c
-        env.update(TSTWO_MERKLE_SUBTREE="2", TSTWO_MERKLE_SUBTREE_LANE_STRIDE="1")
-    out = subprocess.run([sys.executable, "-c", script], env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.strip().splitlines()[-1] == want
-
-
 def test_merkle_golden(golden):
     for e in golden["merkle"]:
         cols = [column(e["seed_base"] + i, 1 << lg) for i, lg in enumerate(e["log_sizes"])]
@@ -935,46 +903,45 @@ import sys
 sys.path[:0] = [{root!r}, {tests!r}]
 import numpy as np
 from test_gpu_capi import rand_column, dev, dev_empty, host, ptrs, half_odds, vp, L
-n = 15
+import ctypes as C
+n = 17
 cols = [dev(rand_column(4200 + c, 1 << n)) for c in range(3)]
 tw = dev_empty(1 << (n - 1))
 L.call("tstwo_twiddles_build", half_odds(n - 1), n - 1, vp(tw), vp(None))
 L.call("tstwo_cfft_evaluate", ptrs(cols), 3, n, half_odds(n - 1), vp(tw), n - 1)
+passes = C.c_uint32(0)
+L.call("tstwo_cfft_plan_passes", n, 3, C.byref(passes))
 import hashlib
-print(L.version(), hashlib.blake2s(b"".join(host(c, 1 << n).tobytes() for c in cols)).hexdigest())
+print(L.version(), passes.value, hashlib.blake2s(b"".join(host(c, 1 << n).tobytes() for c in cols)).hexdigest())
 """
 
 
-def test_shipped_library_ignores_the_experiment_knobs():
-    """TSTWO_CFFT_GENERIC=4 SKIPS the bottom pass — in the experiments build.  The shipped library must not let its caller's
-    environment change a result: with the variable set it still gives the oracle's evaluations, while the experiments build,
-    given the same variable, demonstrably does not (so the test would notice if the switch stopped meaning anything)."""
+def test_shipped_library_ignores_the_cfft_plan_knob():
+    """TSTWO_CFFT_KA=1 caps the strided passes of the CFFT plan at one layer each — in the experiments build.  The shipped library
+    must not let its caller's environment change a plan or a result: with the variable set it still plans its default two passes
+    for 3 columns of 2^17 (a 13-layer bottom pass and one strided pass) and gives the oracle's evaluations.  The experiments build,
+    given the same variable, demonstrably reads it (13 + 1 + 1 + 1 + 1: five passes), so the test would notice if the switch
+    stopped meaning anything, and its evaluations are still the oracle's."""
     import hashlib
     import os
     import subprocess
     import sys
-    n = 15
+    n = 17
     otw = orc.precompute_twiddles(half_odds(n - 1), n - 1)[0]
     want = hashlib.blake2s(b"".join(orc.cfft_evaluate(rand_column(4200 + c, 1 << n), n, half_odds(n - 1), otw, n - 1).tobytes()
                                     for c in range(3))).hexdigest()
     tests_dir = os.path.dirname(os.path.abspath(__file__))
     script = _KNOB_SCRIPT.format(root=os.path.dirname(tests_dir), tests=tests_dir)
-    knobs = dict(TSTWO_CFFT_GENERIC="4", TSTWO_CFFT_KB="12", TSTWO_MERKLE_GENERIC="1", TSTWO_CFFT_ROUNDS="3")
+    knobs = dict(TSTWO_CFFT_KA="1", TSTWO_CFFT_ROUNDS="3")
     env = {k: v for k, v in os.environ.items() if k != "TSTWO_HIP_LIB"}
     out = subprocess.run([sys.executable, "-c", script], env=dict(env, **knobs), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
-    ver, digest = out.stdout.strip().splitlines()[-1].rsplit(" ", 1)
-    assert "experiments" not in ver and digest == want
+    ver, passes, digest = out.stdout.strip().splitlines()[-1].rsplit(" ", 2)
+    assert "experiments" not in ver and passes == "2" and digest == want
     out = subprocess.run([sys.executable, "-c", script], env=dict(env, TSTWO_HIP_LIB=L.LIB_EXP_PATH, **knobs), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
-    ver, digest = out.stdout.strip().splitlines()[-1].rsplit(" ", 1)
-    assert "experiments" in ver and digest != want
-    out = subprocess.run([sys.executable, "-c", script], env=dict(env, TSTWO_HIP_LIB=L.LIB_EXP_PATH, TSTWO_CFFT_KB="12"), capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.strip().splitlines()[-1].rsplit(" ", 1)[1] == want          # a plan-changing knob alone: same results
-    out = subprocess.run([sys.executable, "-c", script], env=dict(env, TSTWO_HIP_LIB=L.LIB_EXP_PATH, TSTWO_CFFT_B8="1"), capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.strip().splitlines()[-1].rsplit(" ", 1)[1] == want          # the 8-words-per-lane bottom pass (measured, not shipped): same results
+    ver, passes, digest = out.stdout.strip().splitlines()[-1].rsplit(" ", 2)
+    assert "experiments" in ver and passes == "5" and digest == want
 
 
 @pytest.mark.parametrize("shape", [(4, 32, 17), (8, 32, 18), (3, 16, 19), (2, 64, 17), (5, 48, 17), (2, 32, 12), (1, 32, 17), (3, 20, 17)], ids=str)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times accumulate_quotients of C columns x 2^n opened at k points each (k sample batches over ONE column list) through
 tstwo_quotients_accumulate_samples_async (HIP events); prints one line per k.
-    python tools/quot_k_time.py [--cols 32] [--log 22] [--kmax 5]      (TSTWO_HIP_LIB = experiments build + TSTWO_QUOT_NO_TRIPLE / NO_PAIR for A/B)"""
+    python tools/quot_k_time.py [--cols 32] [--log 22] [--kmax 5]      (TSTWO_HIP_LIB: another build of the library)"""
 import argparse, ctypes as C, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -50,6 +50,6 @@ for k in range(1, a.kmax + 1):
     e1.record()
     ms = e0.elapsed_ms(e1) / a.reps
     byt = (4.0 * a.cols + 16.0) * N
-    print(f"{os.environ.get('TSTWO_HIP_LIB', 'shipped').split('/')[-1]} NO_TRIPLE={os.environ.get('TSTWO_QUOT_NO_TRIPLE')} NO_PAIR={os.environ.get('TSTWO_QUOT_NO_PAIR')} "
+    print(f"{os.environ.get('TSTWO_HIP_LIB', 'shipped').split('/')[-1]} "
           f"{a.cols} cols x 2^{n}, k = {k}: {ms * 1e3:.1f} us  ({byt / ms / 1e6:.0f} GB/s of one column sweep)", flush=True)
     L.call("tstwo_check_zero_flag")

@@ -2,9 +2,9 @@
 
     python -m tstwo_amd.build [--force] [--verbose] [--experiments]
 
---experiments builds the SECOND library, libtstwo_hip_exp.so (-DTSTWO_EXPERIMENTS): the same sources with the TSTWO_* tuning and
-A/B switches of DESIGN.md §8 read from the environment (once).  The shipped library has them compiled out; tools/ and the few
-tests that pin a non-default branch load the experiments build through TSTWO_HIP_LIB.
+--experiments builds the SECOND library, libtstwo_hip_exp.so (-DTSTWO_EXPERIMENTS): the same sources with the TSTWO_* launch-shape
+parameters of DESIGN.md §8 read from the environment (once).  The shipped library has them compiled out; tools/ load the
+experiments build through TSTWO_HIP_LIB.
 
 hipcc cross-compiles for gfx950 without a GPU, so this also runs in the GPU-less build container.
 The shared library lands next to this file (git-ignored, but it travels to the GPU box with gpurun).

@@ -221,7 +221,7 @@ __device__ __forceinline__ int plan_stages(const PassParams &pp, int *g_out) {
 // in LDS and reused for every column; the next column's tile is prefetched into registers while
 // the current one is transformed, so HBM latency overlaps the butterflies inside the workgroup.
 template <bool INV, int THREADS>
-// (512 lanes = the strided passes of the generic route, which only the experiments build's TSTWO_CFFT_GENERIC reaches: asked for 2
+// (512 lanes = the strided passes of the generic route, which no plan takes while every size with a strided pass is tiled: asked for 2
 // waves per SIMD it keeps its radix-32 stage in registers; at 4 it spilled 120-132 bytes per lane at 128 VGPRs)
 __global__ void __launch_bounds__(THREADS, (THREADS == 512 ? 2 : 3)) k_cfft_pass(ColPtrs cols, u32 n_cols, PassParams pp) {
     extern __shared__ __attribute__((aligned(16))) u32 lds[];
@@ -558,13 +558,7 @@ int launch_fast(u32 *const *cols, size_t n_cols, u32 n, const Pass &ps, const u3
         const size_t lds = (((size_t)1 << ps.k) + ((size_t)1 << (ps.k - 5)) + ((size_t)1 << (ps.k - 4))) * sizeof(u32);
         switch (ps.k) {
             case 14: return launch_fast_kernel(fast::k_cfft_b<INV, 14>, 1024, lds, tiles, cols, n_cols, n, tw_end, scale);
-            case 13:
-#ifdef TSTWO_EXPERIMENTS      // TSTWO_CFFT_B8=1: the 8-words-per-lane bottom pass (1024 lanes, 8 waves per SIMD)
-                if (knobs().cfft_b8)
-                    return launch_fast_kernel(fast::k_cfft_b8<INV, 13>, 1024, (((size_t)1 << 13) + ((size_t)1 << 8) + ((size_t)1 << 10)) * sizeof(u32), tiles, cols,
-                                              n_cols, n, tw_end, scale);
-#endif
-                return launch_fast_kernel(fast::k_cfft_b<INV, 13>, 512, lds, tiles, cols, n_cols, n, tw_end, scale);
+            case 13: return launch_fast_kernel(fast::k_cfft_b<INV, 13>, 512, lds, tiles, cols, n_cols, n, tw_end, scale);
             case 12: return launch_fast_kernel(fast::k_cfft_b<INV, 12>, 256, lds, tiles, cols, n_cols, n, tw_end, scale);
             case 11: return launch_fast_kernel(fast::k_cfft_b<INV, 11>, 128, lds, tiles, cols, n_cols, n, tw_end, scale);
             default: return set_error(TSTWO_ERR_BAD_ARG, "cfft: unsupported bottom pass");
@@ -597,10 +591,6 @@ int launch_fast(u32 *const *cols, size_t n_cols, u32 n, const Pass &ps, const u3
         }
     }
     if (logta != 14) return set_error(TSTWO_ERR_BAD_ARG, "cfft: unsupported pass shape");
-#ifdef TSTWO_EXPERIMENTS      // TSTWO_CFFT_AV=2: the 2^14 tile on 512 lanes x 32 words, two workgroups per CU (measured slower: 3.86 against 3.75 ms)
-    if (knobs().cfft_av == 2 && (ps.k == 8 || ps.k == 9))
-        return ps.k == 9 ? launch_a<INV, 9, 14, 2>(cols, n_cols, n, ps.lo, tw_end, scale) : launch_a<INV, 8, 14, 2>(cols, n_cols, n, ps.lo, tw_end, scale);
-#endif
     switch (ps.k) {
         case 1: return launch_a<INV, 1>(cols, n_cols, n, ps.lo, tw_end, scale);
         case 2: return launch_a<INV, 2>(cols, n_cols, n, ps.lo, tw_end, scale);
@@ -682,38 +672,27 @@ int cfft(u32 *const *cols, size_t n_cols, u32 n, u32 half_initial, const u32 *tw
     Pass passes[8];
     u32 kb, ka_max, logta;
     choose_plan(n, n_cols, kb, ka_max, logta);
-    const Knobs &kn = knobs();
     int np = n >= kMaxLogTileB ? plan_passes(n, passes, kb, ka_max, logta) : plan_passes(n, passes);
     for (size_t i = 0; i < n_cols; i++)
         if (((uintptr_t)cols[i]) & 15) return set_error(TSTWO_ERR_BAD_ARG, "cfft: columns must be 16-byte aligned");
     if (((uintptr_t)tw) & 15) return set_error(TSTWO_ERR_BAD_ARG, "cfft: twiddle buffer must be 16-byte aligned");
     const u32 *tw_end = tw + ((size_t)1 << tw_log);
     const bool fast_path = n >= kMaxLogTileB && n <= kMaxLogSize;
-    const int dbg_generic = kn.cfft_generic;      // experiments build only: 1 = generic kernel for the bottom pass, 2 = for strided passes, 4 = skip the bottom pass
     // All columns go through a pass in one launch.  (Measured on MI355X, 32 x 2^22: running the passes back to back
     // on Infinity-Cache-sized column groups is slower — 688 us ungrouped vs 724/771/879 us for groups of 16/8/4 —
-    // the extra launch tails cost more than MALL residency of the intermediate returns.  TSTWO_CFFT_GROUP=k re-enables it.)
-    size_t group = n_cols;
-    if (np > 1 && kn.cfft_group > 0 && (size_t)kn.cfft_group < n_cols) group = (size_t)kn.cfft_group;
-    for (size_t g0 = 0; g0 < n_cols; g0 += group) {
-        const size_t gc = n_cols - g0 < group ? n_cols - g0 : group;
-        u32 *const *gcols = cols + g0;
-        if (!INV) {
-            for (int s = np - 1; s >= 0; s--) {
-                if ((dbg_generic & 4) && passes[s].lo == 0) continue;
-                const bool f = fast_path && !(dbg_generic & (passes[s].lo == 0 ? 1 : 2));
-                int rc = f ? launch_fast<false>(gcols, gc, n, passes[s], tw_end, 0)
-                           : launch_pass<false>(gcols, gc, n, passes[s], tw, tw_log, 0);
-                if (rc) return rc;
-            }
-        } else {
-            for (int s = 0; s < np; s++) {
-                const u32 sc = s == np - 1 ? n_inv : 0;
-                const bool f = fast_path && !(dbg_generic & (passes[s].lo == 0 ? 1 : 2));
-                int rc = f ? launch_fast<true>(gcols, gc, n, passes[s], tw_end, sc)
-                           : launch_pass<true>(gcols, gc, n, passes[s], tw, tw_log, sc);
-                if (rc) return rc;
-            }
+    // the extra launch tails cost more than MALL residency of the intermediate returns.)
+    if (!INV) {
+        for (int s = np - 1; s >= 0; s--) {
+            int rc = fast_path ? launch_fast<false>(cols, n_cols, n, passes[s], tw_end, 0)
+                               : launch_pass<false>(cols, n_cols, n, passes[s], tw, tw_log, 0);
+            if (rc) return rc;
+        }
+    } else {
+        for (int s = 0; s < np; s++) {
+            const u32 sc = s == np - 1 ? n_inv : 0;
+            int rc = fast_path ? launch_fast<true>(cols, n_cols, n, passes[s], tw_end, sc)
+                               : launch_pass<true>(cols, n_cols, n, passes[s], tw, tw_log, sc);
+            if (rc) return rc;
         }
     }
     return TSTWO_OK;
@@ -751,7 +730,7 @@ int tstwo_cfft_interpolate_to(const u32 *const *src, u32 *const *dst, size_t n_c
     TSTWO_REQUIRE_TABLE(src, n_cols); TSTWO_REQUIRE_TABLE(dst, n_cols);
     if (log_size == 0 || log_size > 31) return set_error(TSTWO_ERR_BAD_ARG, "cfft: log_size out of range");
     const Knobs &kn = knobs();
-    const bool tiled = log_size >= kMaxLogTileB && log_size <= kMaxLogSize && !kn.cfft_generic && !kn.cfft_kb && !kn.cfft_ka && !kn.cfft_no_oop;
+    const bool tiled = log_size >= kMaxLogTileB && log_size <= kMaxLogSize && !kn.cfft_kb && !kn.cfft_ka;
     if (tiled) {
         if (!itw) return set_error(TSTWO_ERR_BAD_ARG, "cfft: null twiddle buffer");
         if (tw_log > 31 || ((size_t)1 << (log_size - 1)) > ((size_t)1 << tw_log)) return set_error(TSTWO_ERR_TWIDDLES, "Not enough twiddles!");
@@ -814,7 +793,7 @@ int tstwo_cfft_evaluate_extended(const u32 *const *polys, u32 log_poly, u32 *con
     Pass passes[8];
     int np = 0;
     const Knobs &kn = knobs();
-    const bool tiled = log_size >= kMaxLogTileB && log_size <= kMaxLogSize && !kn.cfft_generic && !kn.cfft_kb && !kn.cfft_ka && !kn.cfft_no_fused_extend;
+    const bool tiled = log_size >= kMaxLogTileB && log_size <= kMaxLogSize && !kn.cfft_kb && !kn.cfft_ka;
     if (tiled) np = log_size == 14 ? plan_passes(log_size, passes, kMaxLogTileB) : plan_default(log_size, n_cols, passes);   // (n = 14: 13 + 1 keeps the fused extension)
     if (tiled && np >= 2 && (ext == 1 || ext == 2) && passes[np - 1].k >= 2) {
         if (!tw) return set_error(TSTWO_ERR_BAD_ARG, "cfft: null twiddle buffer");

@@ -50,11 +50,11 @@ constexpr int kUpSlots = 16;
 constexpr int kCopyStreams = 2;
 constexpr size_t kUpSlotBytes = 16 * 1024;
 
-// Experiment and A/B-timing switches.  The SHIPPED library never takes them from its caller's environment:
-// knobs() is a compile-time constant holding the defaults below, so every branch on a non-default value folds away and a
-// prover's environment can change neither results nor kernel plans.  Built with -DTSTWO_EXPERIMENTS (python -m tstwo_amd.build
-// --experiments -> libtstwo_hip_exp.so; tools/build_variant.sh passes it too) the struct is filled ONCE, at the first use, from
-// the TSTWO_* variables named in the comments (context.hip: read_knobs) — never per call.
+// Launch-shape parameters that plan sweeps vary.  The SHIPPED library never takes them from its caller's
+// environment: knobs() is a compile-time constant holding the defaults below, so a prover's environment can change neither
+// results nor kernel plans.  Built with -DTSTWO_EXPERIMENTS (python -m tstwo_amd.build --experiments -> libtstwo_hip_exp.so;
+// tools/build_variant.sh passes it too) the struct is filled ONCE, at the first use, from the TSTWO_* variables named in the
+// comments (context.hip: read_knobs) — never per call.
 struct Knobs {
     // cfft.hip
     int cfft_rounds = 1;               // TSTWO_CFFT_ROUNDS: workgroups per launch as a multiple of the resident slots
@@ -62,31 +62,11 @@ struct Knobs {
     int cfft_lds_pad = 0;              // TSTWO_CFFT_LDS_PAD: extra dynamic LDS per workgroup (lowers residency)
     int cfft_kb = 0, cfft_ka = 0;      // TSTWO_CFFT_KB (11-15) / TSTWO_CFFT_KA (1-10): bottom tile / strided layer limit (0 = planner)
     int cfft_logta = 0;                // TSTWO_CFFT_LOGTA (12-15): strided tile (0 = planner)
-    bool cfft_b8 = false;              // TSTWO_CFFT_B8: the 8-words-per-lane bottom pass k_cfft_b8 (in-place transforms with a 2^13 bottom tile)
-    int cfft_av = 0;                   // TSTWO_CFFT_AV=2: 2^14-word strided tiles on 512 lanes x 32 words (two workgroups per CU)
-    int cfft_generic = 0;              // TSTWO_CFFT_GENERIC: bit 0 / 1 generic kernel for bottom / strided passes, bit 2 SKIP the bottom pass
-    int cfft_group = 0;                // TSTWO_CFFT_GROUP: Infinity-Cache column grouping
     bool cfft_trace = false, cfft_sync = false;             // TSTWO_CFFT_TRACE / TSTWO_CFFT_SYNC
-    bool cfft_no_oop = false, cfft_no_fused_extend = false; // TSTWO_CFFT_NO_OOP / TSTWO_CFFT_NO_FUSED_EXTEND
     // merkle.hip
     int merkle_cap = 32;               // TSTWO_MERKLE_CAP: workgroups per CU before lanes grid-stride
-    int merkle_up_log = 0;             // TSTWO_MERKLE_UP_LOG: first quad-lane level (0 = default 16; 15 with UP_ONELANE)
-    int merkle_subtree = 2;            // TSTWO_MERKLE_SUBTREE: column-free layers per launch of the in-lane subtree kernel (0, 2-4)
-    bool merkle_generic = false, merkle_up_onelane = false, merkle_up_smallwg = false, merkle_up_narrow_first = false;
-    bool merkle_no_fused_leaf4 = false, merkle_no_batch = false;
-    bool merkle_subtree_lane_stride = false;   // TSTWO_MERKLE_SUBTREE_LANE_STRIDE: round 3's k_merkle_subtree<2> instead of the coalesced k_merkle_subtree2c (A/B)
     // fri.hip
-    bool fri_no_tail = false, fri_no_fold_fusion = false;   // TSTWO_FRI_NO_TAIL / TSTWO_FRI_NO_FOLD_FUSION
     int fold_cap = 64;                 // TSTWO_FOLD_CAP: workgroups per CU of the fold kernels
-    bool fold1 = false;                // TSTWO_FOLD1: circle fold with one output row per lane
-    // field_ops.hip / quotients.hip
-    int qinv_k = 0;                    // TSTWO_QINV_K
-    bool qinv_montgomery = false, quot_no_lazy = false, quot_no_pair = false;
-    bool quot_no_rowpair = false;      // TSTWO_QUOT_NO_ROWPAIR: 3+ batches over one column list through k_quotients8_multi sweeps instead of k_quotients_rp (A/B)
-    bool quot_no_triple = false;       // TSTWO_QUOT_NO_TRIPLE: k batches over one column list as sweeps of 2 (+ 1) instead of 3 / 2 (A/B)
-    // context.hip
-    bool device_flag = false;          // TSTWO_DEVICE_FLAG: zero-inverse flag / result page in device memory
-    bool no_fast_wait = false;         // TSTWO_NO_FAST_WAIT: wait_stream() = hipStreamSynchronize (A/B of the polled sequence word)
 };
 #ifdef TSTWO_EXPERIMENTS
 const Knobs &knobs();
@@ -226,8 +206,7 @@ constexpr int kSecondTableOff = (int)sizeof(ColPtrs);     // kernel signature (C
 // merkle.hip: tstwo_merkle_commit + the channel's mix_root / draw_felt on its root, as one launch sequence without a separate
 // channel launch where the tree's last launch can carry it
 int merkle_commit_then_channel(const u32 *const *cols, const u32 *log_sizes, size_t n_cols, uint8_t *layers, u32 *chan, u32 *felt);
-// merkle.hip: fold_line fused into the next layer's leaf hashing + tree + channel step; returns -1 when an environment override
-// forbids the fusion (the caller then folds and commits separately)
+// merkle.hip: fold_line fused into the next layer's leaf hashing + tree + channel step
 int merkle_commit4_folded(const u32 *const prev[4], u32 log_new, const u32 *inv_x, const u32 *alpha_dev, u32 *const new_cols[4],
                           uint8_t *layers, u32 *chan, u32 *felt);
 // merkle.hip: the FRI commit's last layers (2^log0 <= 2^9 rows and below) in one single-workgroup launch

@@ -29,27 +29,9 @@ static Knobs read_knobs() {
     k.cfft_kb = num("TSTWO_CFFT_KB", 0); if (k.cfft_kb < 11 || k.cfft_kb > 15) k.cfft_kb = 0;
     k.cfft_ka = num("TSTWO_CFFT_KA", 0); if (k.cfft_ka < 1 || k.cfft_ka > 10) k.cfft_ka = 0;
     k.cfft_logta = num("TSTWO_CFFT_LOGTA", 0); if (k.cfft_logta < 12 || k.cfft_logta > 15) k.cfft_logta = 0;
-    k.cfft_av = num("TSTWO_CFFT_AV", 0);
-    k.cfft_b8 = on("TSTWO_CFFT_B8");
-    k.cfft_generic = num("TSTWO_CFFT_GENERIC", 0);
-    k.cfft_group = num("TSTWO_CFFT_GROUP", 0);
     k.cfft_trace = on("TSTWO_CFFT_TRACE"); k.cfft_sync = on("TSTWO_CFFT_SYNC");
-    k.cfft_no_oop = on("TSTWO_CFFT_NO_OOP"); k.cfft_no_fused_extend = on("TSTWO_CFFT_NO_FUSED_EXTEND");
     k.merkle_cap = num("TSTWO_MERKLE_CAP", 32);
-    k.merkle_up_log = num("TSTWO_MERKLE_UP_LOG", 0);
-    k.merkle_subtree = num("TSTWO_MERKLE_SUBTREE", 2); if (k.merkle_subtree > 4) k.merkle_subtree = 4;
-    k.merkle_generic = on("TSTWO_MERKLE_GENERIC"); k.merkle_up_onelane = on("TSTWO_MERKLE_UP_ONELANE");
-    k.merkle_up_smallwg = on("TSTWO_MERKLE_UP_SMALLWG"); k.merkle_up_narrow_first = on("TSTWO_MERKLE_UP_NARROW_FIRST");
-    k.merkle_no_fused_leaf4 = on("TSTWO_MERKLE_NO_FUSED_LEAF4"); k.merkle_no_batch = on("TSTWO_MERKLE_NO_BATCH");
-    k.merkle_subtree_lane_stride = on("TSTWO_MERKLE_SUBTREE_LANE_STRIDE");
-    k.fri_no_tail = on("TSTWO_FRI_NO_TAIL"); k.fri_no_fold_fusion = on("TSTWO_FRI_NO_FOLD_FUSION");
-    k.fold_cap = num("TSTWO_FOLD_CAP", 64); k.fold1 = on("TSTWO_FOLD1");
-    k.qinv_k = num("TSTWO_QINV_K", 0); k.qinv_montgomery = on("TSTWO_QINV_MONTGOMERY");
-    k.quot_no_lazy = on("TSTWO_QUOT_NO_LAZY"); k.quot_no_pair = on("TSTWO_QUOT_NO_PAIR");
-    k.quot_no_triple = on("TSTWO_QUOT_NO_TRIPLE");
-    k.quot_no_rowpair = on("TSTWO_QUOT_NO_ROWPAIR");
-    k.device_flag = on("TSTWO_DEVICE_FLAG");
-    k.no_fast_wait = on("TSTWO_NO_FAST_WAIT");
+    k.fold_cap = num("TSTWO_FOLD_CAP", 64);
     return k;
 }
 const Knobs &knobs() {
@@ -95,7 +77,7 @@ int ensure_scratch(size_t bytes) {
 __global__ void k_signal(u32 *seq, u32 value) { *(volatile TSTWO_GLOBAL u32 *)seq = value; }
 int wait_stream() {
     Context &c = g_ctx;
-    if (!c.seq_host || knobs().no_fast_wait) {
+    if (!c.seq_host) {
         TSTWO_HIP(hipStreamSynchronize(c.stream));
         return TSTWO_OK;
     }
@@ -367,7 +349,7 @@ int tstwo_init(int device) {
     {   // error flag: page-locked host memory mapped into the device (read-back of a status word = 9.5 us of synchronisation instead
         // of 15-18 us with a copy); device memory if the mapping is not available
         void *h = nullptr, *d = nullptr;
-        if (!knobs().device_flag && hipHostMalloc(&h, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess && d) {
+        if (hipHostMalloc(&h, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess && d) {
             memset(h, 0, 64);
             c.flag_host = (u32 *)h;
             c.flag = (u32 *)d;
@@ -381,7 +363,7 @@ int tstwo_init(int device) {
     if (hipHostMalloc(&c.pinned, kPinnedBytes, hipHostMallocDefault) != hipSuccess) { c.pinned = nullptr; (void)hipGetLastError(); }
     {   // result page for tstwo_download_many (same mechanism as the flag)
         void *h = nullptr, *d = nullptr;
-        if (!knobs().device_flag && hipHostMalloc(&h, kResultBytes, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess && d) {
+        if (hipHostMalloc(&h, kResultBytes, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess && d) {
             c.result_host = h;
             c.result_dev = d;
         } else {

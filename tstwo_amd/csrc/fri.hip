@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(256) k_fold_circle(Soa4 dst, CSoa4 src, size_t
 }
 
 // Two consecutive output rows per lane: 16-byte loads of the source, 8-byte accesses of dst (log 24: 94.2 against 96.7 us for the
-// one-row form; needs 16-byte aligned source columns and 8-byte aligned dst columns, tree twiddles).  TSTWO_FOLD1 = the one-row form.
+// one-row form; needs 16-byte aligned source columns and 8-byte aligned dst columns, tree twiddles).
 template <bool ACCUM>
 __global__ void __launch_bounds__(256) k_fold_circle2(Soa4 dst, CSoa4 src, size_t n_out, const u32 *__restrict__ twp,
                                                      qm31 alpha, qm31 alpha_sq, const qm31 *__restrict__ alpha_dev) {
@@ -348,8 +348,7 @@ static void launch_fold_line(const CSoa4 &i4, const Soa4 &o4, size_t n_out, cons
     hipLaunchKernelGGL(k_fold_line, dim3(capped_blocks(n_out, 256)), dim3(256), 0, ctx().stream, i4, o4, n_out, inv_x, alpha, alpha_dev);
 }
 static void launch_fold_circle(bool from_tree, const Soa4 &d4, const CSoa4 &s4, size_t n_out, const u32 *twp, qm31 a, qm31 a2, const qm31 *alpha_dev) {
-    const bool fold1 = knobs().fold1;
-    bool two = from_tree && !fold1 && n_out >= 4;
+    bool two = from_tree && n_out >= 4;
     for (int k = 0; k < 4; k++) two = two && (((uintptr_t)s4.p[k]) & 15) == 0 && (((uintptr_t)d4.p[k]) & 7) == 0;
     if (two)
         hipLaunchKernelGGL(k_fold_circle2<true>, dim3(capped_blocks(n_out / 2, 256)), dim3(256), 0, ctx().stream, d4, s4, n_out, twp, a, a2, alpha_dev);
@@ -563,7 +562,7 @@ int tstwo_fri_commit_layers(const u32 *const *circle_cols, const u32 *col_logs, 
         const u32 *seg1 = itw + ((size_t)1 << tw_log) - ((size_t)1 << (col_logs[0] - 1));
         Soa4 d4 = {{cur[0], cur[1], cur[2], cur[3]}};
         CSoa4 s4 = {{circle_cols[0], circle_cols[1], circle_cols[2], circle_cols[3]}};
-        bool two = cur_log >= 2 && !knobs().fold1;
+        bool two = cur_log >= 2;
         for (int k = 0; k < 4; k++) two = two && (((uintptr_t)s4.p[k]) & 15) == 0 && (((uintptr_t)d4.p[k]) & 7) == 0;
         if (two)
             hipLaunchKernelGGL(k_fold_circle2<false>, dim3(capped_blocks((size_t)1 << (cur_log - 1), 256)), dim3(256), 0, ctx().stream, d4, s4,
@@ -581,26 +580,23 @@ int tstwo_fri_commit_layers(const u32 *const *circle_cols, const u32 *col_logs, 
         return r;
     };
     size_t n = 0;
-    const bool no_tail = knobs().fri_no_tail;      // A/B timing: per-layer launches down to the last layer
     uint8_t *cur_tree = nullptr;         // set: `cur` is already committed into it (its leaves were hashed by the fold that produced it)
                                          // and alpha (n + 1) is drawn
-    uint8_t *spare_tree = nullptr;       // a tree buffer of the current size allocated for a fusion that an override refused
     const u32 *tail_pre[4] = {nullptr, nullptr, nullptr, nullptr};      // set: `cur` is still to be computed — the tail launch folds it
     const u32 *tail_pre_alpha = nullptr;                                // from this evaluation with this alpha (one launch fewer)
     while (cur_log > log_last_layer_size) {
-        if (!cur_tree && !no_tail && cur_log <= 9 && nxt == n_columns) {
+        if (!cur_tree && cur_log <= 9 && nxt == n_columns) {
             // every remaining layer fits one workgroup's LDS: ONE launch does tree / mix / draw / fold for all of them (k_fri_tail)
             const u32 nl = cur_log - log_last_layer_size;
             u32 *ev[11][4];
             uint8_t *trees[10];
             for (int k = 0; k < 4; k++) ev[0][k] = cur[k];
             for (u32 i = 0; i < nl; i++) {
-                void *t = i == 0 ? (void *)spare_tree : nullptr;
-                if (!t && (rc = alloc(&t, tstwo_merkle_layers_bytes(cur_log - i)))) return fail(rc);
+                void *t = nullptr;
+                if ((rc = alloc(&t, tstwo_merkle_layers_bytes(cur_log - i)))) return fail(rc);
                 trees[i] = (uint8_t *)t;
                 if ((rc = alloc_eval(ev[i + 1], cur_log - i - 1))) return fail(rc);
             }
-            spare_tree = nullptr;
             if ((rc = launch_fri_tail(ev, trees, nl, cur_log, itw, tw_log, chan, alphas + 4 * (n + 1), tail_pre_alpha ? tail_pre : nullptr, tail_pre_alpha)))
                 return fail(rc);
             for (u32 i = 0; i < nl; i++) {
@@ -621,9 +617,8 @@ int tstwo_fri_commit_layers(const u32 *const *circle_cols, const u32 *col_logs, 
             o.layers = cur_tree;
             cur_tree = nullptr;
         } else {
-            void *t = spare_tree;
-            spare_tree = nullptr;
-            if (!t && (rc = alloc(&t, tstwo_merkle_layers_bytes(cur_log)))) return fail(rc);
+            void *t = nullptr;
+            if ((rc = alloc(&t, tstwo_merkle_layers_bytes(cur_log)))) return fail(rc);
             o.layers = (uint8_t *)t;
             const u32 lg4[4] = {cur_log, cur_log, cur_log, cur_log};
             if ((rc = merkle_commit_then_channel(cur, lg4, 4, o.layers, chan, alpha))) return fail(rc);      // FriInnerLayerProver::new + mix / draw
@@ -634,17 +629,16 @@ int tstwo_fri_commit_layers(const u32 *const *circle_cols, const u32 *col_logs, 
         u32 *folded[4];
         if ((rc = alloc_eval(folded, next_log))) return fail(rc);
         const bool joins = nxt < n_columns && col_logs[nxt] - 1 == next_log;
-        const bool tail_next = !no_tail && next_log <= 9 && nxt + (joins ? 1 : 0) == n_columns;
+        const bool tail_next = next_log <= 9 && nxt + (joins ? 1 : 0) == n_columns;
         bool fused = false;
         if (next_log > log_last_layer_size && !joins && !tail_next) {
             if (tw_log > 31 || cur_log > tw_log) return fail(set_error(TSTWO_ERR_TWIDDLES, "Not enough twiddles!"));
             void *t = nullptr;
             if ((rc = alloc(&t, tstwo_merkle_layers_bytes(next_log)))) return fail(rc);
             const u32 *seg = itw + ((size_t)1 << tw_log) - ((size_t)1 << cur_log);
-            rc = merkle_commit4_folded(cur, next_log, seg, alpha, folded, (uint8_t *)t, chan, alphas + 4 * (n + 2));
-            if (rc == -1) spare_tree = (uint8_t *)t;          // an environment override keeps 4-column trees off the leaf4 kernels
-            else if (rc) return fail(rc);
-            else { cur_tree = (uint8_t *)t; fused = true; }
+            if ((rc = merkle_commit4_folded(cur, next_log, seg, alpha, folded, (uint8_t *)t, chan, alphas + 4 * (n + 2)))) return fail(rc);
+            cur_tree = (uint8_t *)t;
+            fused = true;
         }
         if (!fused && tail_next && !joins && next_log > log_last_layer_size) {
             for (int k = 0; k < 4; k++) tail_pre[k] = cur[k];          // the tail launch folds this layer on its way in

@@ -357,11 +357,9 @@ __global__ void __launch_bounds__(256) k_merkle_inner_set(TreeSet ts, u32 log_ou
     merkle_inner_body(layers + 2 * (((size_t)1 << (log_out + 1)) - 1), layers + 2 * (((size_t)1 << log_out) - 1), (size_t)1 << log_out);
 }
 
-// (3) LEVELS column-free layers in one launch, no exchange at all: a lane owns 2^LEVELS consecutive nodes of layer
-// `log_child` — a whole subtree — and produces the 2^(LEVELS-1), ..., 1 nodes above them in post-order (left, right, parent),
-// so that a parent's message is the two digests still in registers.  Every lane is busy at every level (a layer-per-launch
-// chain halves the grid each time and ends in launches that are all latency), intermediate layers are written once and
-// never read back, and two or three launches disappear.  All levels are written to their places in the layers buffer
+// (3) Two column-free layers in one launch: the four children of a node of layer `log_child - 2` hash into their two parents
+// and then into that node, so that a parent's message is the two digests still in registers.  The intermediate layer is
+// written once and never read back, and one launch disappears.  Both layers are written to their places in the layers buffer
 // (MerkleProver keeps all layers, vcs/prover.ts:24-29; layer k at byte offset 32*(2^k - 1)).
 struct Digest { u32 w[8]; };
 __device__ __forceinline__ Digest hash_pair(const Digest &l, const Digest &r) {
@@ -370,67 +368,16 @@ __device__ __forceinline__ Digest hash_pair(const Digest &l, const Digest &r) {
     b2s_compress(d.w, m, 64u, true);
     return d;
 }
-__device__ __forceinline__ Digest load_digest(const uint4 *p) {
-    const uint4 a = p[0], b = p[1];
-    return {{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
-}
-__device__ __forceinline__ void store_digest(uint4 *p, const Digest &d) {
-    p[0] = make_uint4(d.w[0], d.w[1], d.w[2], d.w[3]);
-    p[1] = make_uint4(d.w[4], d.w[5], d.w[6], d.w[7]);
-}
-// node `idx` of layer `log_child - LVL` (LVL levels above the children) of the lane's subtree; children read from HBM at LVL == 1.
-// The two sub-subtrees are a rolled loop (one copy of each level's compression in the code: fully inlined, the 7 or 15
-// compressions of a kernel took the compiler tens of minutes).
-template <int LVL>
-__device__ __forceinline__ Digest subtree_node(uint4 *__restrict__ layers, u32 log_child, size_t idx) {
-    Digest l, r;
-    if constexpr (LVL == 1) {
-        const uint4 *c = layers + 2 * ((((size_t)1 << log_child) - 1) + 2 * idx);
-        l = load_digest(c);
-        r = load_digest(c + 2);
-    } else {
-#pragma unroll 1
-        for (int s = 0; s < 2; s++) {
-            const Digest d = subtree_node<LVL - 1>(layers, log_child, 2 * idx + s);
-            if (s == 0) l = d;
-            else r = d;
-        }
-    }
-    const Digest d = hash_pair(l, r);
-    store_digest(layers + 2 * ((((size_t)1 << (log_child - LVL)) - 1) + idx), d);
-    return d;
-}
-template <int LEVELS>
-__global__ void __launch_bounds__(256) k_merkle_subtree(TreeSet ts, u32 log_child) {
-    uint4 *__restrict__ layers = ts.t[blockIdx.y];
-    const size_t top = (size_t)blockIdx.x * blockDim.x + threadIdx.x;         // node index in layer log_child - LEVELS
-    if (top >= ((size_t)1 << (log_child - LEVELS))) return;
-    if constexpr (LEVELS == 2) {
-        // straight-line form of the two-level subtree: all four children are requested before anything is hashed (the rolled
-        // recursion loads a pair, waits, hashes, stores, and waits vmcnt(0) for that store before it loads the next pair), and
-        // every store is followed by a compression or by the end of the wave, so no write latency is ever waited for
-        const uint4 *c = layers + 2 * ((((size_t)1 << log_child) - 1) + 4 * top);
-        const Digest c0 = load_digest(c), c1 = load_digest(c + 2), c2 = load_digest(c + 4), c3 = load_digest(c + 6);
-        uint4 *mid = layers + 2 * ((((size_t)1 << (log_child - 1)) - 1) + 2 * top);
-        const Digest l = hash_pair(c0, c1);
-        store_digest(mid, l);
-        const Digest r = hash_pair(c2, c3);
-        store_digest(mid + 2, r);
-        store_digest(layers + 2 * ((((size_t)1 << (log_child - 2)) - 1) + top), hash_pair(l, r));
-    } else {
-        (void)subtree_node<LEVELS>(layers, log_child, top);
-    }
-}
-
-// The two-level subtree with every global access a 1 KiB-contiguous wave access (round 4).  In k_merkle_subtree<2> a lane reads its
-// four children as eight 16-byte loads at a 128-byte lane stride and writes its digests at 64- and 32-byte lane strides: every
+// The two-level subtree with every global access a 1 KiB-contiguous wave access (round 4).  In round 3's lane-per-subtree form a
+// lane read its four children as eight 16-byte loads at a 128-byte lane stride and wrote its digests at 64- and 32-byte lane strides: every
 // instruction touches 64 lines a piece each, the pieces of a line arrive a compression apart, and with 32 waves per CU the lines
 // do not survive in the caches in between — the counters showed 1.31 x the child bytes fetched and 1.16-1.24 x the digest bytes
 // written (profiles/r03_cfft_pmc.json), on launches that move 4.3 TB/s.  Here a wave loads its 256 children as eight 1 KiB rows,
 // transposes them to "lane owns 128 consecutive bytes" through its OWN 4.5 KiB of LDS (two halves of 4 KiB, one pad slot per
 // 8 chunks: conflict-free both ways; wave-local, so no barrier — the LDS executes a wave's instructions in order), and stores
 // the 128 + 64 digests it produced the same way, all six store instructions back to back at the end of the wave.
-// Needs the top layer (2^(log_child-2) nodes) to be a multiple of 256 nodes: the host falls back to k_merkle_subtree<2> otherwise.
+// Needs the top layer (2^(log_child-2) nodes) to be a multiple of 256 nodes.  Both callers launch it only for top layers of at
+// least 2^kUpLog = 2^16 nodes (everything smaller goes to the quad-lane levels), so that always holds.
 __device__ __forceinline__ u32 xslot(u32 chunk) { return chunk + (chunk >> 3); }
 __global__ void __launch_bounds__(256) k_merkle_subtree2c(TreeSet ts, u32 log_child) {
     __shared__ uint4 xch[4][288];                       // per wave: 256 chunks of 16 bytes + 32 pad slots
@@ -486,46 +433,6 @@ __global__ void __launch_bounds__(256) k_merkle_subtree2c(TreeSet ts, u32 log_ch
     for (int k = 0; k < 4; k++) gstore4(mid, 4u * (64u * k + lane), o[k]);
 #pragma unroll
     for (int k = 0; k < 2; k++) gstore4(up, 4u * (64u * k + lane), o2[k]);
-}
-
-// Several column-free levels per launch: a workgroup of WG lanes owns 2*WG consecutive nodes of layer `log_child`
-// and produces the WG, WG/2, ... nodes above them (LEVELS levels), exchanging digests through LDS.  Every level is
-// still written to its place in the layers buffer (MerkleProver keeps all layers, vcs/prover.ts:24-29).
-// layers: device buffer in tstwo_merkle_commit's layout (layer k at byte offset 32*(2^k - 1)).
-template <int WG>
-__global__ void __launch_bounds__(WG) k_merkle_up(uint4 *__restrict__ layers, u32 log_child, u32 levels) {
-    __shared__ uint4 sh[WG * 2];                                  // digests of the level just produced (2 x uint4 each)
-    const u32 t = threadIdx.x;
-    const uint4 *__restrict__ child = layers + 2 * (((size_t)1 << log_child) - 1);
-    u32 m[16];
-    u32 active = min((u32)WG, 1u << (log_child - 1));             // parents this workgroup produces at the first level
-    if (t < active) {
-        const size_t node = (size_t)blockIdx.x * WG + t;           // parent index in layer log_child-1
-        const uint4 *c = child + 4 * node;
-        uint4 c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
-        m[0] = c0.x; m[1] = c0.y; m[2] = c0.z; m[3] = c0.w; m[4] = c1.x; m[5] = c1.y; m[6] = c1.z; m[7] = c1.w;
-        m[8] = c2.x; m[9] = c2.y; m[10] = c2.z; m[11] = c2.w; m[12] = c3.x; m[13] = c3.y; m[14] = c3.z; m[15] = c3.w;
-    }
-    for (u32 lv = 1; lv <= levels; lv++) {
-        const u32 log_out = log_child - lv;
-        u32 h[8] = {IV0 ^ 0x01010020u, IV1, IV2, IV3, IV4, IV5, IV6, IV7};
-        if (t < active) {
-            b2s_compress(h, m, 64u, true);
-            uint4 *out = layers + 2 * (((size_t)1 << log_out) - 1) + 2 * ((size_t)blockIdx.x * active + t);
-            out[0] = make_uint4(h[0], h[1], h[2], h[3]);
-            out[1] = make_uint4(h[4], h[5], h[6], h[7]);
-            sh[2 * t] = make_uint4(h[0], h[1], h[2], h[3]);
-            sh[2 * t + 1] = make_uint4(h[4], h[5], h[6], h[7]);
-        }
-        __syncthreads();
-        active >>= 1;
-        if (lv < levels && t < active) {
-            uint4 c0 = sh[4 * t], c1 = sh[4 * t + 1], c2 = sh[4 * t + 2], c3 = sh[4 * t + 3];
-            m[0] = c0.x; m[1] = c0.y; m[2] = c0.z; m[3] = c0.w; m[4] = c1.x; m[5] = c1.y; m[6] = c1.z; m[7] = c1.w;
-            m[8] = c2.x; m[9] = c2.y; m[10] = c2.z; m[11] = c2.w; m[12] = c3.x; m[13] = c3.y; m[14] = c3.z; m[15] = c3.w;
-        }
-        __syncthreads();
-    }
 }
 
 // ---- Upper tree, latency path: one compression spread over a QUAD of lanes (lane j of the quad owns column j of the
@@ -773,6 +680,9 @@ thread_local ChanHook g_chan_hook = {nullptr, nullptr};
 // of that tree folds the previous layer into them on the way (FoldSpec) and clears it.
 thread_local FoldSpec g_fold = {};
 thread_local bool g_fold_set = false;
+// Layers below 2^kUpLog nodes are latency-bound: tstwo_merkle_commit builds them with the fused multi-level launches above
+// (k_merkle_upq) instead of one launch per layer.
+constexpr int kUpLog = 16;
 int commit_upper_levels(uint8_t *layers, u32 log_child, u32 log_stop);
 int commit_upper_levels(TreeSet ts, unsigned n_trees, u32 log_child, u32 log_stop) {
     Context &c = ctx();
@@ -783,42 +693,26 @@ int commit_upper_levels(TreeSet ts, unsigned n_trees, u32 log_child, u32 log_sto
         g_chan_hook = none;
         return h;
     };
-    uint8_t *layers = (uint8_t *)ts.t[0];             // (the one-lane scheme kept for A/B timing handles one tree)
-    const bool one_lane = knobs().merkle_up_onelane;     // previous scheme, kept for A/B timing
-    const bool small_wg = knobs().merkle_up_smallwg;     // 256-lane workgroups only (A/B timing)
-    const bool narrow_first = knobs().merkle_up_narrow_first;   // 64-quad workgroups first, one 256-quad workgroup last (A/B timing)
     while (log_child > log_stop) {
         const u32 remaining = log_child - log_stop;
         const u32 parents_log = log_child - 1;
-        if (one_lane && n_trees == 1) {
-            if (parents_log >= 8) {               // >= 256 parents: 256-lane workgroups, up to 5 levels each
-                u32 levels = remaining < 5 ? remaining : 5;
-                hipLaunchKernelGGL(k_merkle_up<256>, dim3(1u << (parents_log - 8)), dim3(256), 0, c.stream, (uint4 *)layers, log_child, levels);
-                log_child -= levels;
-            } else {                              // the top of the tree (< 256 parents): one workgroup finishes it
-                hipLaunchKernelGGL(k_merkle_up<256>, dim3(1), dim3(256), 0, c.stream, (uint4 *)layers, log_child, remaining);
-                log_child -= remaining;
-            }
-        } else if (parents_log >= 9 && remaining >= 9 && remaining <= 16 && !small_wg && !narrow_first) {
+        if (parents_log >= 9 && remaining >= 9 && remaining <= 16) {
             // 256 quads per workgroup, 9 levels each, FIRST: the wide levels (256 and 128 compressions on one CU are the slow
             // part of a single-workgroup tree top) run on 2^(parents_log-8) CUs side by side, and what is left (<= 7 levels)
             // fits one 64-quad workgroup, one wave per SIMD.  (The other order — 64-quad workgroups first, one 256-quad
             // workgroup to finish — put those wide levels on one CU.)
             hipLaunchKernelGGL(k_merkle_upq<1024>, dim3(1u << (parents_log - 8), n_trees), dim3(1024), 0, c.stream, ts, log_child, 9u, none);
             log_child -= 9;
-        } else if (parents_log <= 6 && !narrow_first) {   // <= 64 parents: one 64-quad workgroup finishes the tree
+        } else if (parents_log <= 6) {            // <= 64 parents: one 64-quad workgroup finishes the tree
             hipLaunchKernelGGL(k_merkle_upq<256>, dim3(1, n_trees), dim3(256), 0, c.stream, ts, log_child, remaining, take_hook(log_stop == 0));
             log_child -= remaining;
-        } else if (parents_log <= 8 && !small_wg) {   // <= 256 parents: ONE workgroup of 256 quads finishes the tree (up to 9 levels)
+        } else if (parents_log <= 8) {            // <= 256 parents: ONE workgroup of 256 quads finishes the tree (up to 9 levels)
             hipLaunchKernelGGL(k_merkle_upq<1024>, dim3(1, n_trees), dim3(1024), 0, c.stream, ts, log_child, remaining, take_hook(log_stop == 0));
             log_child -= remaining;
-        } else if (parents_log >= 6) {            // >= 64 parents: 64 quads per workgroup, 64 -> 1 = up to 7 levels each
+        } else {                                  // >= 512 parents: 64 quads per workgroup, 64 -> 1 = up to 7 levels each
             u32 levels = remaining < 7 ? remaining : 7;
             hipLaunchKernelGGL(k_merkle_upq<256>, dim3(1u << (parents_log - 6), n_trees), dim3(256), 0, c.stream, ts, log_child, levels, none);
             log_child -= levels;
-        } else {
-            hipLaunchKernelGGL(k_merkle_upq<256>, dim3(1, n_trees), dim3(256), 0, c.stream, ts, log_child, remaining, take_hook(log_stop == 0));
-            log_child -= remaining;
         }
     }
     TSTWO_LAUNCH_CHECK();
@@ -991,7 +885,7 @@ int commit_layer(u32 log_size, const uint8_t *prev, const u32 *const *cols, size
     const unsigned cap_mult = (unsigned)knobs().merkle_cap;
     const unsigned cap = (unsigned)c.n_cus * cap_mult;     // workgroups per CU before lanes grid-stride over more nodes
     if (blocks > cap) blocks = cap;
-    if (!prev && log_size <= 30 && (n_cols == 16 || n_cols == 32 || n_cols == 48 || n_cols == 64) && !knobs().merkle_generic) {
+    if (!prev && log_size <= 30 && (n_cols == 16 || n_cols == 32 || n_cols == 48 || n_cols == 64)) {
         HashColPtrs hp;
         for (size_t k = 0; k < n_cols; k++) hp.p[k] = cols[k];
         TreeSet one = {};
@@ -1005,7 +899,7 @@ int commit_layer(u32 log_size, const uint8_t *prev, const u32 *const *cols, size
         TSTWO_LAUNCH_CHECK();
         return TSTWO_OK;
     }
-    if (!prev && log_size <= 30 && n_cols == 4 && !knobs().merkle_generic) {
+    if (!prev && log_size <= 30 && n_cols == 4) {
         u32 *w0 = const_cast<u32 *>(cols[0]), *w1 = const_cast<u32 *>(cols[1]), *w2 = const_cast<u32 *>(cols[2]), *w3 = const_cast<u32 *>(cols[3]);
         if (g_fold_set) {
             hipLaunchKernelGGL(k_merkle_leaf4<true>, dim3(blocks), dim3(256), 0, c.stream, w0, w1, w2, w3, (uint4 *)out, n_nodes, g_fold);
@@ -1016,7 +910,7 @@ int commit_layer(u32 log_size, const uint8_t *prev, const u32 *const *cols, size
         TSTWO_LAUNCH_CHECK();
         return TSTWO_OK;
     }
-    if (prev && n_cols == 0 && !knobs().merkle_generic) {
+    if (prev && n_cols == 0) {
         hipLaunchKernelGGL(k_merkle_inner, dim3(blocks), dim3(256), 0, c.stream, (const uint4 *)prev, (uint4 *)out, n_nodes);
         TSTWO_LAUNCH_CHECK();
         return TSTWO_OK;
@@ -1070,16 +964,12 @@ int merkle_commit_then_channel(const u32 *const *cols, const u32 *log_sizes, siz
     if (rc) return rc;
     return pending ? tstwo_channel_mix_root_draw_felt(chan, layers, felt) : TSTWO_OK;
 }
-// fri.hip's commit loop: fold_line of a layer INTO the leaf hashing of the next layer's tree.  new_cols (2^log_new rows each) receive
-// the folded evaluation; `layers` the tree over them; then mix_root + draw_felt as in merkle_commit_then_channel.  Bit-identical to
-// tstwo_fri_fold_line_dev + tstwo_merkle_commit + tstwo_channel_mix_root_draw_felt (which it falls back to when an environment
-// override routes 4-column trees away from the leaf4 kernels).
+// fri.hip's commit loop: fold_line of a layer INTO the leaf hashing of the next layer's tree.  new_cols (2^log_new rows each,
+// 1 <= log_new <= 30) receive the folded evaluation; `layers` the tree over them; then mix_root + draw_felt as in
+// merkle_commit_then_channel.  Bit-identical to tstwo_fri_fold_line_dev + tstwo_merkle_commit + tstwo_channel_mix_root_draw_felt.
 int merkle_commit4_folded(const u32 *const prev[4], u32 log_new, const u32 *inv_x, const u32 *alpha_dev, u32 *const new_cols[4],
                           uint8_t *layers, u32 *chan, u32 *felt) {
-    const bool fusable = !knobs().merkle_generic && !knobs().merkle_no_fused_leaf4 && !knobs().fri_no_fold_fusion && log_new >= 1 &&
-                         log_new <= 30;
     const u32 lg4[4] = {log_new, log_new, log_new, log_new};
-    if (!fusable) return -1;                                     // caller takes the unfused path
     g_fold = {{prev[0], prev[1], prev[2], prev[3]}, inv_x, alpha_dev};
     g_fold_set = true;
     int rc = merkle_commit_then_channel(new_cols, lg4, 4, layers, chan, felt);
@@ -1434,12 +1324,10 @@ int tstwo_merkle_commit(const u32 *const *cols, const u32 *log_sizes, size_t n_c
         if (log_sizes[i] > 31) return set_error(TSTWO_ERR_BAD_ARG, "merkle: log size out of range");
         if (log_sizes[i] > max_log) max_log = log_sizes[i];
     }
-    // layers below 2^up_log nodes are latency-bound: fused multi-level launches (k_merkle_upq) instead of one per level
-    const int up_log = knobs().merkle_up_log ? knobs().merkle_up_log : (knobs().merkle_up_onelane ? 15 : 16);
-    // a tree of exactly 4 equally long columns with at most 2^up_log rows (every FRI layer but the first few): leaves and the
+    // a tree of exactly 4 equally long columns with at most 2^kUpLog rows (every FRI layer but the first few): leaves and the
     // first 7 (or all, below 2^10 rows) levels in one launch
-    if (n_cols == 4 && max_log >= 1 && (int)max_log <= up_log && log_sizes[0] == max_log && log_sizes[1] == max_log && log_sizes[2] == max_log &&
-        log_sizes[3] == max_log && !knobs().merkle_no_fused_leaf4) {
+    if (n_cols == 4 && max_log >= 1 && (int)max_log <= kUpLog && log_sizes[0] == max_log && log_sizes[1] == max_log && log_sizes[2] == max_log &&
+        log_sizes[3] == max_log) {
         Context &c = ctx();
         u32 log_child = max_log;
         u32 *w0 = const_cast<u32 *>(cols[0]), *w1 = const_cast<u32 *>(cols[1]), *w2 = const_cast<u32 *>(cols[2]), *w3 = const_cast<u32 *>(cols[3]);
@@ -1462,7 +1350,6 @@ int tstwo_merkle_commit(const u32 *const *cols, const u32 *log_sizes, size_t n_c
         if (root) return small_d2h(root, layers, 32);
         return TSTWO_OK;
     }
-    const int sub_levels = knobs().merkle_subtree;   // measured: 2 (0.308 ms) < off (0.313) < 3 (0.326) < 4 (0.332) for 32 x 2^22
     const u32 **lc = n_cols ? new const u32 *[n_cols] : nullptr;
     const uint8_t *prev = nullptr;
     int rc = TSTWO_OK;
@@ -1473,7 +1360,7 @@ int tstwo_merkle_commit(const u32 *const *cols, const u32 *log_sizes, size_t n_c
             if (log_sizes[i] == (u32)lg) lc[k++] = cols[i];
         uint8_t *dst = layers + 32 * (((size_t)1 << lg) - 1);
         // layer k starts at 32*(2^k-1): 16-byte aligned for every k >= 0 when `layers` is
-        if (k == 0 && prev != nullptr && lg < up_log) {
+        if (k == 0 && prev != nullptr && lg < kUpLog) {
             // a run of column-free layers below lg+1: fuse them (stop above the next layer that has columns)
             int stop = lg;
             while (stop > 0) {
@@ -1487,31 +1374,19 @@ int tstwo_merkle_commit(const u32 *const *cols, const u32 *log_sizes, size_t n_c
             lg = stop - 1;
             continue;
         }
-        if (k == 0 && prev != nullptr && sub_levels >= 2) {
-            // a run of column-free layers at or above 2^up_log nodes: in-lane subtrees, up to sub_levels layers per launch
-            int run = 1;
-            while (run < sub_levels && lg - run >= up_log && lg - run >= 0) {
-                bool has = false;
-                for (size_t i = 0; i < n_cols; i++) has = has || log_sizes[i] == (u32)(lg - run);
-                if (has) break;
-                run++;
-            }
-            if (run >= 2) {
-                const size_t tops = (size_t)1 << (lg - run + 1);
-                const unsigned blocks = ceil_div(tops, 256);
+        if (k == 0 && prev != nullptr) {
+            // two column-free layers at or above 2^kUpLog nodes: one in-lane subtree launch for both (measured for 32 x 2^22:
+            // 0.308 ms, against 0.313 for one launch per layer and 0.326 / 0.332 for runs of 3 / 4 layers)
+            bool pair = lg - 1 >= kUpLog;
+            for (size_t i = 0; i < n_cols; i++) pair = pair && log_sizes[i] != (u32)(lg - 1);
+            if (pair) {
+                const size_t tops = (size_t)1 << (lg - 1);          // >= 2^kUpLog nodes: whole k_merkle_subtree2c workgroups
                 Context &c = ctx();
                 TreeSet one = {};
                 one.t[0] = (uint4 *)layers;
-                switch (run) {
-                    case 2:
-                        if (tops % 256 == 0 && !knobs().merkle_subtree_lane_stride) hipLaunchKernelGGL(k_merkle_subtree2c, dim3(blocks), dim3(256), 0, c.stream, one, (u32)lg + 1);
-                        else hipLaunchKernelGGL(k_merkle_subtree<2>, dim3(blocks), dim3(256), 0, c.stream, one, (u32)lg + 1);
-                        break;
-                    case 3: hipLaunchKernelGGL(k_merkle_subtree<3>, dim3(blocks), dim3(256), 0, c.stream, one, (u32)lg + 1); break;
-                    default: hipLaunchKernelGGL(k_merkle_subtree<4>, dim3(blocks), dim3(256), 0, c.stream, one, (u32)lg + 1); break;
-                }
+                hipLaunchKernelGGL(k_merkle_subtree2c, dim3((unsigned)(tops / 256)), dim3(256), 0, c.stream, one, (u32)lg + 1);
                 if (hipGetLastError() != hipSuccess) rc = set_error(TSTWO_ERR_HIP, "merkle: subtree kernel launch failed");
-                lg -= run;
+                lg -= 2;
                 prev = layers + 32 * (((size_t)1 << (lg + 1)) - 1);
                 continue;
             }
@@ -1539,8 +1414,7 @@ int tstwo_merkle_commit(const u32 *const *cols, const u32 *log_sizes, size_t n_c
 int tstwo_merkle_commit_many(const tstwo_commit_request *reqs, size_t n_trees, uint8_t *roots) {
     TSTWO_REQUIRE_READY();
     if (n_trees && !reqs) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null request table");
-    bool uniform = n_trees >= 2 && n_trees <= (size_t)kMaxTrees && !knobs().merkle_generic && !knobs().merkle_no_batch;
-    const int up_log = knobs().merkle_up_log ? knobs().merkle_up_log : 16;
+    bool uniform = n_trees >= 2 && n_trees <= (size_t)kMaxTrees;
     size_t n_cols = n_trees ? reqs[0].n_cols : 0;
     u32 lg = 0;
     for (size_t r = 0; r < n_trees && uniform; r++) {
@@ -1554,7 +1428,7 @@ int tstwo_merkle_commit_many(const tstwo_commit_request *reqs, size_t n_trees, u
             uniform = q.log_sizes[k] == lg;
         }
     }
-    uniform = uniform && lg >= (u32)up_log + 1 && lg <= 30;
+    uniform = uniform && lg >= (u32)kUpLog + 1 && lg <= 30;
     if (!uniform) {
         for (size_t r = 0; r < n_trees; r++) {
             int rc = tstwo_merkle_commit(reqs[r].cols, reqs[r].log_sizes, reqs[r].n_cols, reqs[r].layers, nullptr);
@@ -1581,16 +1455,15 @@ int tstwo_merkle_commit_many(const tstwo_commit_request *reqs, size_t n_trees, u
             case 3: hipLaunchKernelGGL(k_merkle_leaf_static<3>, grid, dim3(256), 0, c.stream, hp, leaf, n_nodes); break;
             default: hipLaunchKernelGGL(k_merkle_leaf_static<4>, grid, dim3(256), 0, c.stream, hp, leaf, n_nodes); break;
         }
-        // column-free layers lg-1 .. up_log two per launch (in-lane subtrees), a single leftover layer on its own, then the
+        // column-free layers lg-1 .. kUpLog two per launch (in-lane subtrees), a single leftover layer on its own, then the
         // quad-lane levels: the launch sequence of tstwo_merkle_commit for a tree whose columns all sit on the leaf layer
         int cur = (int)lg - 1;
-        while (cur - 1 >= up_log) {
+        while (cur - 1 >= kUpLog) {
             const size_t tops = (size_t)1 << (cur - 1);
-            if (tops % 256 == 0 && !knobs().merkle_subtree_lane_stride) hipLaunchKernelGGL(k_merkle_subtree2c, dim3((unsigned)(tops / 256), (unsigned)n_trees), dim3(256), 0, c.stream, ts, (u32)cur + 1);
-            else hipLaunchKernelGGL(k_merkle_subtree<2>, dim3(ceil_div(tops, 256), (unsigned)n_trees), dim3(256), 0, c.stream, ts, (u32)cur + 1);
+            hipLaunchKernelGGL(k_merkle_subtree2c, dim3((unsigned)(tops / 256), (unsigned)n_trees), dim3(256), 0, c.stream, ts, (u32)cur + 1);
             cur -= 2;
         }
-        if (cur >= up_log) {
+        if (cur >= kUpLog) {
             unsigned b1 = ceil_div((size_t)1 << cur, 256);
             if (b1 > cap) b1 = cap ? cap : 1;
             hipLaunchKernelGGL(k_merkle_inner_set, dim3(b1, (unsigned)n_trees), dim3(256), 0, c.stream, ts, (u32)cur);

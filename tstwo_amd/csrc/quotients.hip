@@ -695,7 +695,7 @@ int tstwo_quotients_accumulate_async(u32 half_initial, u32 log_size, const u32 *
     for (size_t j = 0; j < n_entries; j++)
         if (upos[col_idx[j]] < 0) { upos[col_idx[j]] = (int)ulist.size(); ulist.push_back(col_idx[j]); }
     const u32 per = (u32)ulist.size();
-    const bool same_list = n_batches >= 2 && per > 0 && !knobs().quot_no_pair && 10 * n_entries >= 14 * (size_t)per;
+    const bool same_list = n_batches >= 2 && per > 0 && 10 * n_entries >= 14 * (size_t)per;
     const size_t lp_bytes = same_list ? (((size_t)per * sizeof(u32 *) + 63) / 64) * 64 : 0;
     const size_t lc_bytes = same_list ? ((n_batches * (size_t)per * sizeof(qm31) + 63) / 64) * 64 : 0;
     std::vector<unsigned char> blob(ptr_bytes + bc_bytes + en_bytes + lp_bytes + lc_bytes + 64, 0);
@@ -754,8 +754,7 @@ int tstwo_quotients_accumulate_async(u32 half_initial, u32 log_size, const u32 *
         cpoint qb = {qx, qy};
         size_t n_threads = (size_t)1 << (log_size - 3);
         bool lazy = false;               // a batch with more than 4 column entries: fold the numerator sums between groups
-        const bool no_lazy = knobs().quot_no_lazy;          // (measurement knob: reduce after every group of 4)
-        for (size_t b = 0; b < n_batches; b++) lazy = lazy || (!no_lazy && batch_off[b + 1] - batch_off[b] > 4);
+        for (size_t b = 0; b < n_batches; b++) lazy = lazy || batch_off[b + 1] - batch_off[b] > 4;
         const dim3 grid(ceil_div(n_threads, 256));
         // two batches over one column list (same columns in the same order): the column words are loaded once for both
         const bool pair = same_list;
@@ -763,7 +762,7 @@ int tstwo_quotients_accumulate_async(u32 half_initial, u32 log_size, const u32 *
             size_t done = 0;
             // sweeps: 2 batches -> k_quotients8_multi<2>; 3 or 4 -> the row-pair kernel k_quotients_rp<3 | 4> (log_size >= 9);
             // more -> 4 (or 3) at a time, the later sweeps continuing from the rows the earlier ones wrote (5 = 3 + 2, 6 = 3 + 3, 7 = 4 + 3)
-            const bool rp_ok = log_size >= 9 && !knobs().quot_no_rowpair;
+            const bool rp_ok = log_size >= 9;
             u32 q7x, q7y, q8x, q8y;
             host::point(1u << 24, &q7x, &q7y);
             host::point(1u << 23, &q8x, &q8y);
@@ -783,11 +782,11 @@ int tstwo_quotients_accumulate_async(u32 half_initial, u32 log_size, const u32 *
                     done += (size_t)nb;
                     continue;
                 }
-                const int nb = knobs().quot_no_triple ? (left >= 2 ? 2 : 1) : ((left == 2 || left == 4) ? 2 : 3);
+                // (left >= 2 throughout: same_list needs 2 batches, and no sweep above leaves a single one behind)
+                const int nb = (left == 2 || left == 4) ? 2 : 3;
 #define TSTWO_QMULTI(NBV, ACC) hipLaunchKernelGGL((k_quotients8_multi<NBV, ACC>), grid, dim3(256), 0, c.stream, half_initial & 0x7fffffffu, log_size, \
                                                   d_lp, d_b + done, d_lc + done * per, per, o4, c.gen_win, qb, bsel, c.flag)
-                if (nb == 1) TSTWO_QMULTI(1, true);
-                else if (nb == 2 && done == 0) TSTWO_QMULTI(2, false);
+                if (nb == 2 && done == 0) TSTWO_QMULTI(2, false);
                 else if (nb == 2) TSTWO_QMULTI(2, true);
                 else if (done == 0) TSTWO_QMULTI(3, false);
                 else TSTWO_QMULTI(3, true);

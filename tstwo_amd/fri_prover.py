@@ -367,8 +367,7 @@ class FriProver:
         caller); otherwise its inputs (coordinate columns, x^-1 slice of the tree) come back.  Updates the host channel; returns
         what _commit_last_layer takes as `prefetched`."""
         n_last = layer_eval.len()
-        separate = bool(os.environ.get("TSTWO_FRI_SEPARATE_READBACKS"))   # A/B timing: round 3's first form, one tstwo_download per piece
-        if coeff_buf is None and not separate and not os.environ.get("TSTWO_FRI_HOST_LAST_LAYER"):
+        if coeff_buf is None and not os.environ.get("TSTWO_FRI_HOST_LAST_LAYER"):
             coeff_buf = line_interpolate_device(layer_eval, twiddles)
         pieces = [(dch.buf.ptr, 10)]
         uses_tree = _line_interpolate_uses_tree(layer_eval, twiddles)
@@ -378,7 +377,7 @@ class FriProver:
             pieces += [(c.buf.ptr, n_last) for c in layer_eval.values.columns]
             if uses_tree:
                 pieces.append((twiddles.itwiddles.buf.ptr + 4 * (twiddles.itwiddles.len() - n_last), n_last))
-        got = [L.download_many([pc])[0] for pc in pieces] if separate else L.download_many(pieces)
+        got = L.download_many(pieces)
         dch.sync_to_host(got[0])                                         # the host channel continues from the device state
         if coeff_buf is not None:
             return {"coeffs": got[1].reshape(4, n_last)}
