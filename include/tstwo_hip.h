@@ -499,6 +499,39 @@ int tstwo_air_wide_fib_trace(const uint32_t *a, const uint32_t *b, uint32_t log_
 int tstwo_air_constraint_quotients(uint32_t kind, const uint32_t *const *cols, size_t n_cols, uint32_t trace_log_size,
                                    uint32_t log_expand, const uint32_t *coeffs, size_t n_constraints, const uint32_t *denom_inv,
                                    uint32_t *const accum[4]);
+/* User-defined constraints as a straight-line program (tstwo_amd/constraint_framework.py compiles a FrameworkEval into it): the
+ * contract of tstwo_air_constraint_quotients with e_k(r) = the value of the k-th ACC instruction at row r, and loads at row offsets.
+ *   cols: n_cols device columns on CanonicCoset(trace_log_size + log_expand).circle_domain(), bit-reversed order (main-trace
+ *   columns, then preprocessed ones: the program names them by position);  1 <= log_expand <= 4 (the neighbour index needs
+ *   eval > trace);  coeffs: n_constraints QM31 values (4 host words each), coefficient k goes with the k-th ACC;  denom_inv, accum:
+ *   as for tstwo_air_constraint_quotients.
+ * Program: program_len instructions of two host words, w0 = op | dst << 8 | x << 16, w1:
+ *   TSTWO_AIR_OP_LOAD   r[dst] = cols[x][offset_bit_reversed_circle_domain_index(r, trace_log, trace_log + log_expand, (int32_t)w1)]
+ *                       (the row (int32_t)w1 trace steps away; |w1| <= TSTWO_AIR_PROGRAM_MAX_OFFSET, x < n_cols)
+ *   TSTWO_AIR_OP_CONST  r[dst] = w1 (an M31 value < 2^31 - 1)
+ *   TSTWO_AIR_OP_ADD / _SUB / _MUL   r[dst] = r[x] (+ | - | *) r[w1]
+ *   TSTWO_AIR_OP_SQR    r[dst] = r[x]^2            TSTWO_AIR_OP_NEG   r[dst] = -r[x]          (w1 ignored)
+ *   TSTWO_AIR_OP_ACC    constraint k (k counts ACCs from 0) = r[x]; dst, w1 ignored.  There are exactly n_constraints ACCs.
+ * Every register read must have been written by an earlier instruction; registers are < TSTWO_AIR_PROGRAM_MAX_REGS.  The
+ * registers live in LDS (n_regs KiB per 64-lane workgroup, n_regs = the highest register written + 1).  Every limit is checked
+ * (TSTWO_ERR_BAD_ARG, text in tstwo_last_error).  The program and coefficients are uploaded through the small-upload ring:
+ * refused during graph capture.  Asynchronous. */
+#define TSTWO_AIR_OP_LOAD 0
+#define TSTWO_AIR_OP_CONST 1
+#define TSTWO_AIR_OP_ADD 2
+#define TSTWO_AIR_OP_SUB 3
+#define TSTWO_AIR_OP_MUL 4
+#define TSTWO_AIR_OP_SQR 5
+#define TSTWO_AIR_OP_NEG 6
+#define TSTWO_AIR_OP_ACC 7
+#define TSTWO_AIR_PROGRAM_MAX_INSTR 1536
+#define TSTWO_AIR_PROGRAM_MAX_REGS 32
+#define TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS 256
+#define TSTWO_AIR_PROGRAM_MAX_COLS 4096
+#define TSTWO_AIR_PROGRAM_MAX_OFFSET 64
+int tstwo_air_eval_program(const uint32_t *const *cols, size_t n_cols, uint32_t trace_log_size, uint32_t log_expand,
+                           const uint32_t *program, size_t program_len, const uint32_t *coeffs, size_t n_constraints,
+                           const uint32_t *denom_inv, uint32_t *const accum[4]);
 
 #ifdef __cplusplus
 }

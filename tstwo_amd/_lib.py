@@ -161,6 +161,7 @@ _SIGS = {
     "tstwo_grind_poseidon252": [u32p, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)],
     "tstwo_air_wide_fib_trace": [vp, vp, C.c_uint32, C.POINTER(vp), C.c_size_t],
     "tstwo_air_constraint_quotients": [C.c_uint32, C.POINTER(vp), C.c_size_t, C.c_uint32, C.c_uint32, u32p, C.c_size_t, u32p, P4],
+    "tstwo_air_eval_program": [C.POINTER(vp), C.c_size_t, C.c_uint32, C.c_uint32, u32p, C.c_size_t, u32p, C.c_size_t, u32p, P4],
 }
 ALLOC_POOL, ALLOC_DIRECT, ALLOC_ASYNC, ALLOC_POISON = 0, 1, 2, 0x10
 # c_void_p arguments above are DEVICE addresses, except these (host memory of any element type)

@@ -294,10 +294,17 @@ def _concat_cols(trees_list: list) -> list:
 
 
 class Components:
-    """The verifier's view of a set of components."""
+    """The verifier's view of a set of components.  n_preprocessed_columns: the width of the preprocessed tree (tree 0).  Each of
+    its columns that some component names (`preprocessed_column_indices`) is sampled once, at [point], whichever components read
+    it; the others get no sample (Rust air/components.rs)."""
 
-    def __init__(self, components):
+    def __init__(self, components, n_preprocessed_columns: int = 0):
         self.components = list(components)
+        self.n_preprocessed_columns = n_preprocessed_columns
+        for c in self.components:
+            for idx in getattr(c, "preprocessed_column_indices", ()):
+                if not 0 <= idx < n_preprocessed_columns:
+                    raise ValueError(f"preprocessed column {idx} out of range (the preprocessed tree has {n_preprocessed_columns})")
 
     def composition_log_degree_bound(self) -> int:
         return max(c.max_constraint_log_degree_bound() for c in self.components)
@@ -307,12 +314,27 @@ class Components:
         pts = _concat_cols([c.mask_points(point) for c in self.components])
         while len(pts) <= ORIGINAL_TRACE_IDX:
             pts.append([])
+        if self.n_preprocessed_columns or any(getattr(c, "preprocessed_column_indices", ()) for c in self.components):
+            pre = [[] for _ in range(self.n_preprocessed_columns)]
+            for c in self.components:
+                for idx in getattr(c, "preprocessed_column_indices", ()):
+                    pre[idx] = [point]
+            pts[PREPROCESSED_TRACE_IDX] = pre
         return pts
 
     def column_log_sizes(self) -> list:
         sizes = _concat_cols([c.trace_log_degree_bounds() for c in self.components])
         while len(sizes) <= ORIGINAL_TRACE_IDX:
             sizes.append([])
+        if self.n_preprocessed_columns or any(getattr(c, "preprocessed_column_indices", ()) for c in self.components):
+            pre, seen = [0] * self.n_preprocessed_columns, set()
+            for c in self.components:
+                for idx, lg in zip(getattr(c, "preprocessed_column_indices", ()), c.trace_log_degree_bounds()[PREPROCESSED_TRACE_IDX]):
+                    if idx in seen and pre[idx] != lg:
+                        raise ValueError(f"preprocessed column {idx} read with two log sizes ({pre[idx]} and {lg})")
+                    pre[idx] = lg
+                    seen.add(idx)
+            sizes[PREPROCESSED_TRACE_IDX] = pre
         return sizes
 
     def eval_composition_polynomial_at_point(self, point: CirclePoint, mask_values: list, random_coeff: QM31) -> QM31:
@@ -325,11 +347,12 @@ class Components:
 class ComponentProvers:
     """The prover's view: Components plus the composition polynomial on the device."""
 
-    def __init__(self, components):
+    def __init__(self, components, n_preprocessed_columns: int = 0):
         self.component_provers = list(components)
+        self.n_preprocessed_columns = n_preprocessed_columns
 
     def components(self) -> Components:
-        return Components(self.component_provers)
+        return Components(self.component_provers, self.n_preprocessed_columns)
 
     def compute_composition_polynomial(self, random_coeff: QM31, trace: Trace, twiddles: TwiddleTree) -> SecureCirclePoly:
         total = sum(c.n_constraints for c in self.component_provers)

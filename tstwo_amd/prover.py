@@ -75,8 +75,9 @@ def _sample_points(components: Components, oods_point: CirclePoint) -> list:
 def prove(components, channel, commitment_scheme) -> StarkProof:
     """components: FrameworkComponents whose trace trees (preprocessed, then main) are already committed in `commitment_scheme`
     (a CommitmentSchemeProver).  Raises ConstraintsNotSatisfied when the trace breaks a constraint."""
-    provers = ComponentProvers(components)
     trace = Trace.of(commitment_scheme)
+    # the preprocessed tree's width from the commitment scheme (Rust prove; the reference's prover/index.ts:606)
+    provers = ComponentProvers(components, len(trace.polys[0]) if trace.polys else 0)
     random_coeff = channel.draw_felt()
     # composition polynomial, committed as one tree of its 4 coordinate polynomials
     composition = provers.compute_composition_polynomial(random_coeff, trace, commitment_scheme.twiddles)
@@ -95,7 +96,8 @@ def prove(components, channel, commitment_scheme) -> StarkProof:
 def verify(components, channel, commitment_scheme_verifier, proof: StarkProof) -> None:
     """components: the same component descriptions the prover used; commitment_scheme_verifier already holds the trace trees'
     commitments (as the prover's channel saw them).  Raises OodsNotMatching, InvalidStructure or VerificationError."""
-    comps = Components(components)
+    sizes = commitment_scheme_verifier.column_log_sizes()
+    comps = Components(components, len(sizes[0]) if sizes else 0)
     random_coeff = channel.draw_felt()
     if not proof.commitments:
         raise InvalidStructure("no composition commitment")
