@@ -6,6 +6,7 @@ import pytest
 
 import air_model as M
 from tstwo_amd import air as A
+from tstwo_amd import constraint_framework as F
 from tstwo_amd.circle import CanonicCoset, CirclePoint
 from tstwo_amd.fields import M31, QM31
 
@@ -81,10 +82,10 @@ def _components_from(specs, rng, broken=None):
         n = 1 << log
         if kind == M.WIDE_FIB:
             cols = M.wide_fib_trace(rng.integers(0, P, size=n), rng.integers(0, P, size=n), n_cols)
-            host.append(A.WideFibonacciComponent(log, n_cols, alloc))
+            host.append(F.WideFibonacciComponent(log, n_cols, alloc))
         else:
             cols = M.mul_add_trace(rng.integers(0, P, size=n), rng.integers(0, P, size=n))
-            host.append(A.MulAddComponent(log, alloc))
+            host.append(F.MulAddComponent(log, alloc))
         if broken is not None and broken[0] == k:
             cols[broken[1]] = cols[broken[1]].copy()
             cols[broken[1]][broken[2]] = (cols[broken[1]][broken[2]] + 1) % P
@@ -133,7 +134,7 @@ def test_deep_ali_identity_multi_component(broken):
 
 def test_components_mask_points_and_log_sizes_concatenate_in_allocation_order():
     alloc = A.TraceLocationAllocator()
-    cs = [A.WideFibonacciComponent(6, 5, alloc), A.MulAddComponent(3, alloc), A.WideFibonacciComponent(4, 3, alloc)]
+    cs = [F.WideFibonacciComponent(6, 5, alloc), F.MulAddComponent(3, alloc), F.WideFibonacciComponent(4, 3, alloc)]
     assert [c.trace_locations[1] for c in cs] == [(0, 5), (5, 8), (8, 11)]
     comps = A.Components(cs)
     assert comps.column_log_sizes() == [[], [6] * 5 + [3] * 3 + [4] * 3]

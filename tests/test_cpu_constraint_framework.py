@@ -13,25 +13,6 @@ from tstwo_amd.fields import QM31
 P = M.P
 
 
-class WideFibonacciEval:
-    def __init__(self, log_n_rows, n=100):
-        self.log_n_rows, self.n = log_n_rows, n
-
-    def log_size(self):
-        return self.log_n_rows
-
-    def max_constraint_log_degree_bound(self):
-        return self.log_n_rows + 1
-
-    def evaluate(self, eval):
-        a, b = eval.next_trace_mask(), eval.next_trace_mask()
-        for _ in range(2, self.n):
-            c = eval.next_trace_mask()
-            eval.add_constraint(c - (a.square() + b.square()))
-            a, b = b, c
-        return eval
-
-
 def q(t):
     return QM31.from_u32_unchecked(*t)
 
@@ -87,17 +68,46 @@ def test_framework_refusals():
         F.FrameworkComponent(Unnamed(4))                      # reads is_first, names no preprocessed column
 
 
-def test_point_evaluator_of_wide_fibonacci_equals_the_component():
+def _point_constraints_against_the_model(ev, kind, n_cols):
     rng = np.random.default_rng(1)
-    vals = [q(tuple(int(v) for v in rng.integers(0, P, size=4))) for _ in range(100)]
-    got = F.point_constraints(WideFibonacciEval(6), [[v] for v in vals], [])
-    want = A.WideFibonacciComponent(6, 100).constraints_at(vals)
-    assert got == want
+    vals = [tuple(int(v) for v in rng.integers(0, P, size=4)) for _ in range(n_cols)]
+    got = F.point_constraints(ev, [[q(v)] for v in vals], [])
+    assert [c.tup() for c in got] == M.constraints_point(kind, vals)
+
+
+def test_point_evaluator_of_wide_fibonacci_equals_the_model():
+    """The verifier's side of WideFibonacciComponent (the PointEvaluator over WideFibonacciEval) against the model's integers."""
+    _point_constraints_against_the_model(F.WideFibonacciEval(6, 100), M.WIDE_FIB, 100)
+
+
+def test_point_evaluator_of_mul_add_equals_the_model():
+    _point_constraints_against_the_model(F.MulAddEval(6), M.MUL_ADD, 3)
+
+
+class ProgramWideFibonacciEval(F.WideFibonacciEval):
+    """The library eval under another type: exact-type dispatch sends it to the program interpreter."""
+
+
+def test_hand_written_kernel_is_chosen_by_exact_eval_type():
+    wf, ma = F.WideFibonacciComponent(8), F.MulAddComponent(8)
+    assert (wf.kind, ma.kind) == (A.AIR_WIDE_FIB, A.AIR_MUL_ADD)
+    assert wf.program is None and ma.program is None             # the hand-written path compiles no program
+
+    class UserEval:
+        kind = A.AIR_MUL_ADD                                      # an eval cannot opt into a hand-written kernel
+        def log_size(self): return 4
+        def max_constraint_log_degree_bound(self): return 5
+        def evaluate(self, eval):
+            x, y = eval.next_trace_mask(), eval.next_trace_mask()
+            eval.add_constraint(x * y - 1)
+    for comp in (F.FrameworkComponent(F.FibonacciRowsEval(5), None, [0]), F.FrameworkComponent(UserEval()),
+                 F.FrameworkComponent(ProgramWideFibonacciEval(8))):
+        assert comp.kind is None and comp.program is not None
 
 
 def test_program_is_deterministic_and_small():
-    p1 = F.FrameworkComponent(WideFibonacciEval(8)).program
-    p2 = F.FrameworkComponent(WideFibonacciEval(8)).program
+    p1 = F.FrameworkComponent(ProgramWideFibonacciEval(8)).program
+    p2 = F.FrameworkComponent(ProgramWideFibonacciEval(8)).program
     assert p1.words == p2.words
     assert p1.n_constraints == 98 and p1.n_loads == 100      # every column loaded once
     assert p1.n_regs <= 6                                      # x_i and x_i^2 die as the window moves
@@ -186,7 +196,7 @@ def test_components_share_preprocessed_columns():
     alloc = A.TraceLocationAllocator()
     c1 = F.FrameworkComponent(F.FibonacciRowsEval(5), alloc, [2])
     c2 = F.FrameworkComponent(F.FibonacciRowsEval(5), alloc, [2])
-    w = A.WideFibonacciComponent(4, 5, alloc)
+    w = F.WideFibonacciComponent(4, 5, alloc)
     comps = A.Components([c1, w, c2], 3)
     from tstwo_amd.circle import CirclePoint
     pt = CirclePoint(q((1, 2, 3, 4)), q((5, 6, 7, 8)))
@@ -196,7 +206,7 @@ def test_components_share_preprocessed_columns():
     assert comps.column_log_sizes()[0] == [0, 0, 5]
     assert comps.column_log_sizes()[1] == [5, 5, 4, 4, 4, 4, 4, 5, 5]
     # callers without a preprocessed tree see what they saw before
-    legacy = A.Components([A.WideFibonacciComponent(4, 5)])
+    legacy = A.Components([F.WideFibonacciComponent(4, 5)])
     assert legacy.mask_points(pt)[0] == [] and legacy.column_log_sizes()[0] == []
     with pytest.raises(ValueError):
         A.Components([c1], 2)

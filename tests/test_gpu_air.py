@@ -9,6 +9,7 @@ import pytest
 import air_model as M
 from tstwo_amd import _lib as L
 from tstwo_amd import air as A
+from tstwo_amd import constraint_framework as F
 from tstwo_amd.backend import HipColumn, SecureColumnByCoords
 from tstwo_amd.channel import Blake2sChannel
 from tstwo_amd.circle import CanonicCoset
@@ -104,7 +105,7 @@ def _device_trace(model_components, twiddles):
 
 def _host_components(specs):
     alloc = A.TraceLocationAllocator()
-    return [A.WideFibonacciComponent(log, n, alloc) if kind == M.WIDE_FIB else A.MulAddComponent(log, alloc) for kind, log, n in specs]
+    return [F.WideFibonacciComponent(log, n, alloc) if kind == M.WIDE_FIB else F.MulAddComponent(log, alloc) for kind, log, n in specs]
 
 
 def _model_components(specs, rng):
@@ -160,7 +161,7 @@ def _verify(components, proof, config, channel, merkle_channel=None, mix_log=Non
 def _wide_fib(log, n_cols, seed=0, alloc=None):
     rng = np.random.default_rng(seed)
     a, b = rng.integers(0, P, size=1 << log), rng.integers(0, P, size=1 << log)
-    return A.WideFibonacciComponent(log, n_cols, alloc), A.generate_wide_fib_trace(log, a, b, n_cols)
+    return F.WideFibonacciComponent(log, n_cols, alloc), A.generate_wide_fib_trace(log, a, b, n_cols)
 
 
 @pytest.mark.parametrize("log", [4, 5, 6, 8, 10, 12, 14, 16])
@@ -173,7 +174,7 @@ def test_prove_verify_wide_fibonacci_100(log):
 
 
 def test_prove_verify_example05_table():
-    comp = A.MulAddComponent(4)
+    comp = F.MulAddComponent(4)
     domain = CanonicCoset(4).circleDomain()
     trace = [HipCircleEvaluation(domain, col(c)) for c in M.example05_trace(4)]
     config = PcsConfig()
@@ -185,7 +186,7 @@ def _multi():
     alloc = A.TraceLocationAllocator()
     c1, t1 = _wide_fib(10, 100, 1, alloc)
     c2, t2 = _wide_fib(8, 16, 2, alloc)
-    c3 = A.MulAddComponent(5, alloc)
+    c3 = F.MulAddComponent(5, alloc)
     rng = np.random.default_rng(3)
     t3 = [HipCircleEvaluation(CanonicCoset(5).circleDomain(), col(c))
           for c in M.mul_add_trace(rng.integers(0, P, size=32), rng.integers(0, P, size=32))]
@@ -271,7 +272,7 @@ def test_verify_rejects_tampered_root(honest):
 
 def test_verify_rejects_other_log_size(honest):
     comp, config, proof = honest
-    other = A.WideFibonacciComponent(comp.log_size + 1, comp.n_columns)
+    other = F.WideFibonacciComponent(comp.log_size + 1, comp.n_columns)
     with pytest.raises(REJECT):
         _verify([other], proof, config, Blake2sChannel())
     _verify([comp], proof, config, Blake2sChannel())        # the honest proof still verifies

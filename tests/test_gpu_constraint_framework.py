@@ -49,43 +49,6 @@ def col(a):
     return HipColumn(np.asarray(a, dtype=np.uint32))
 
 
-class WideFibonacciEval:
-    def __init__(self, log_n_rows, n=100):
-        self.log_n_rows, self.n = log_n_rows, n
-
-    def log_size(self):
-        return self.log_n_rows
-
-    def max_constraint_log_degree_bound(self):
-        return self.log_n_rows + 1
-
-    def evaluate(self, eval):
-        a, b = eval.next_trace_mask(), eval.next_trace_mask()
-        for _ in range(2, self.n):
-            c = eval.next_trace_mask()
-            eval.add_constraint(c - (a.square() + b.square()))
-            a, b = b, c
-        return eval
-
-
-class MulAddEval:
-    """The Rust tutorial's example 05 as a FrameworkEval."""
-
-    def __init__(self, log_n_rows):
-        self.log_n_rows = log_n_rows
-
-    def log_size(self):
-        return self.log_n_rows
-
-    def max_constraint_log_degree_bound(self):
-        return self.log_n_rows + 1
-
-    def evaluate(self, eval):
-        x0, x1, x2 = eval.next_trace_mask(), eval.next_trace_mask(), eval.next_trace_mask()
-        eval.add_constraint(x0 * x1 + x0 - x2)
-        return eval
-
-
 # ------------------------------------------------------------------ the kernel against the model
 def _call_raw(cols_ptrs, trace_log, log_expand, words, n_constraints, coeffs, dinv, acc_ptrs):
     cw = L.u32x([w for c in coeffs for w in c])
@@ -205,16 +168,25 @@ def _device_trace(cols, log, eval_log, twiddles, pre=()):
     return A.Trace([p0, p1], [e0, e1])
 
 
+class ProgramWideFibonacciEval(F.WideFibonacciEval):
+    """The library evals under other types: exact-type dispatch sends them to the program interpreter."""
+
+
+class ProgramMulAddEval(F.MulAddEval):
+    pass
+
+
 @pytest.mark.parametrize("which", ["wide_fib", "mul_add"])
 def test_framework_composition_equals_hand_written(which):
     rng = np.random.default_rng(31)
     log = 10
     if which == "wide_fib":
         cols = M.wide_fib_trace(rng.integers(0, P, size=1 << log), rng.integers(0, P, size=1 << log), 100)
-        hand, fw = A.WideFibonacciComponent(log, 100), F.FrameworkComponent(WideFibonacciEval(log, 100))
+        hand, fw = F.WideFibonacciComponent(log, 100), F.FrameworkComponent(ProgramWideFibonacciEval(log, 100))
     else:
         cols = M.mul_add_trace(rng.integers(0, P, size=1 << log), rng.integers(0, P, size=1 << log))
-        hand, fw = A.MulAddComponent(log), F.FrameworkComponent(MulAddEval(log))
+        hand, fw = F.MulAddComponent(log), F.FrameworkComponent(ProgramMulAddEval(log))
+    assert hand.kind is not None and fw.kind is None            # one component per kernel
     tw = precompute_twiddles(CanonicCoset(log + 2).circleDomain().halfCoset)
     trace = _device_trace(cols, log, log + 1, tw)
     alpha = q(rand_felt(rng))
@@ -273,13 +245,13 @@ def test_prove_verify_fibonacci_rows_poseidon252(log):
 
 
 def _mixed():
-    """FibonacciRowsEval + WideFibonacciComponent + a framework mul-add; preprocessed tree: [unread, is_first] of the same size."""
+    """FibonacciRowsEval + WideFibonacciComponent + a mul-add on the program path; preprocessed tree: [unread, is_first] of the same size."""
     alloc = A.TraceLocationAllocator()
     rng = np.random.default_rng(77)
     fr, fr_main, fr_pre = _fib_rows(9, 2, 7, alloc, pre_index=1)
-    wf = A.WideFibonacciComponent(8, 20, alloc)
+    wf = F.WideFibonacciComponent(8, 20, alloc)
     wf_main = A.generate_wide_fib_trace(8, rng.integers(0, P, size=1 << 8), rng.integers(0, P, size=1 << 8), 20)
-    ma = F.FrameworkComponent(MulAddEval(6), alloc)
+    ma = F.FrameworkComponent(ProgramMulAddEval(6), alloc)
     ma_main = _evals(M.mul_add_trace(rng.integers(0, P, size=64), rng.integers(0, P, size=64)), 6)
     unread = _evals([rng.integers(0, P, size=1 << 9)], 9)
     return [fr, wf, ma], unread + fr_pre, fr_main + wf_main + ma_main, [9, 9]

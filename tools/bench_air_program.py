@@ -34,25 +34,6 @@ HBM_COPY = 6.3e12                # bytes/s, measured copy rate (MI355X_MICROARCH
 N_COLS = 100
 
 
-class WideFibonacciEval:
-    def __init__(self, log_n_rows, n=N_COLS):
-        self.log_n_rows, self.n = log_n_rows, n
-
-    def log_size(self):
-        return self.log_n_rows
-
-    def max_constraint_log_degree_bound(self):
-        return self.log_n_rows + 1
-
-    def evaluate(self, eval):
-        a, b = eval.next_trace_mask(), eval.next_trace_mask()
-        for _ in range(2, self.n):
-            c = eval.next_trace_mask()
-            eval.add_constraint(c - (a.square() + b.square()))
-            a, b = b, c
-        return eval
-
-
 def time_ms(fn, reps):
     fn()
     L.sync()
@@ -81,16 +62,18 @@ def run(log, reps, rng):
     cols = [e.values for e in A.generate_wide_fib_trace(el, rng.integers(0, P, size=rows), rng.integers(0, P, size=rows), N_COLS)]
     dinv = A.denominator_inverses(log, el)
     acc_h, acc_p = SecureColumnByCoords.zeros(rows), SecureColumnByCoords.zeros(rows)
-    comp = F.FrameworkComponent(WideFibonacciEval(log))
-    coeffs = [coeff] * comp.n_constraints
+    pe = F.ProgramEvaluator()                  # the library eval runs on the hand-written kernel: compile its program here
+    F.WideFibonacciEval(log, N_COLS).evaluate(pe)
+    program = pe.compile()
+    coeffs = [coeff] * program.n_constraints
     A.evaluate_constraint_quotients(A.AIR_WIDE_FIB, cols, log, 1, coeffs, dinv, acc_h)
-    F.evaluate_program(cols, log, 1, comp.program, coeffs, dinv, acc_p)
+    F.evaluate_program(cols, log, 1, program, coeffs, dinv, acc_p)
     same = all(np.array_equal(x, y) for x, y in zip(acc_h.to_numpy(), acc_p.to_numpy()))
     hand = time_ms(lambda: A.evaluate_constraint_quotients(A.AIR_WIDE_FIB, cols, log, 1, coeffs, dinv, acc_h), reps)
-    prog = time_ms(lambda: F.evaluate_program(cols, log, 1, comp.program, coeffs, dinv, acc_p), reps)
+    prog = time_ms(lambda: F.evaluate_program(cols, log, 1, program, coeffs, dinv, acc_p), reps)
     res["wide_fib_hand"] = entry(hand, N_COLS, rows)
     res["wide_fib_program"] = entry(prog, N_COLS, rows)
-    res["wide_fib_program"].update({"n_instr": comp.program.n_instr, "n_regs": comp.program.n_regs, "same_result": same})
+    res["wide_fib_program"].update({"n_instr": program.n_instr, "n_regs": program.n_regs, "same_result": same})
     res["program_over_hand"] = prog / hand
     del cols, acc_h, acc_p
     # FibonacciRowsEval on its evaluation domain (log + 2); random values: the kernel's work does not depend on them

@@ -32,6 +32,7 @@ sys.path.insert(0, ROOT)
 
 from tstwo_amd import _lib as L  # noqa: E402
 from tstwo_amd import air as A  # noqa: E402
+from tstwo_amd import constraint_framework as F  # noqa: E402
 from tstwo_amd.backend import HipColumn, SecureColumnByCoords  # noqa: E402
 from tstwo_amd.channel import Blake2sChannel  # noqa: E402
 from tstwo_amd.circle import CanonicCoset, CirclePoint  # noqa: E402
@@ -119,7 +120,7 @@ def verify_ms(comp, proof, config) -> float:
 def run(log, reps, isa) -> dict:
     rng = np.random.default_rng(log)
     a, b = HipColumn(rng.integers(0, P, size=1 << log, dtype=np.uint32)), HipColumn(rng.integers(0, P, size=1 << log, dtype=np.uint32))
-    comp = A.WideFibonacciComponent(log, N_COLS)
+    comp = F.WideFibonacciComponent(log, N_COLS)
     config = PcsConfig()
     res = {"log_n": log, "n_columns": N_COLS}
     trace, res["trace_gen_ms"] = sync_ms(lambda: A.generate_wide_fib_trace(log, a, b, N_COLS))

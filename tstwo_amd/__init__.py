@@ -35,9 +35,10 @@ from .vcs import (Blake2sMerkleChannel, Blake2sMerkleHasher, DeviceHashLayer, Hi
                   MerkleProver, MerkleVerifier)
 from .poseidon import (DeviceFeltLayer, FieldElement252, HipPoseidon252MerkleOps, Poseidon252Channel,  # noqa: F401
                        Poseidon252MerkleChannel, Poseidon252MerkleHasher, Poseidon252MerkleProver)
-from .air import (ColumnAccumulator, ComponentProvers, Components, DomainEvaluationAccumulator, FrameworkComponent,  # noqa: F401
-                  MulAddComponent, PointEvaluationAccumulator, Trace, TraceLocationAllocator, WideFibonacciComponent,
-                  coset_vanishing, generate_wide_fib_trace)
+from .air import (ColumnAccumulator, ComponentProvers, Components, DomainEvaluationAccumulator,  # noqa: F401
+                  PointEvaluationAccumulator, Trace, TraceLocationAllocator, coset_vanishing, generate_wide_fib_trace)
+from .constraint_framework import (FrameworkComponent, MulAddComponent, MulAddEval, WideFibonacciComponent,  # noqa: F401
+                                   WideFibonacciEval)
 from .prover import ConstraintsNotSatisfied, InvalidStructure, OodsNotMatching, StarkProof, prove, verify  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -1,13 +1,13 @@
-"""AIR components and the composition polynomial on the device.
+"""AIR accumulators, component sets and the composition polynomial on the device.
 
-Follows Rust stwo's air/accumulation.rs, air/components.rs and constraint_framework/component.rs, which the reference carries as
-shapes in air/accumulator.ts, air/components.ts and constraint_framework/index.ts (their logic there is stubbed).  Two constraint
-kinds are supported, both reading only their own row (mask offset 0):
-  WideFibonacciComponent  examples/fibonacci.ts WideFibonacciEval: c_i = x_{i+2} - (x_i^2 + x_{i+1}^2)
-  MulAddComponent         TestEval of the Rust tutorial's example 05: c = x_0 x_1 + x_0 - x_2
-The verifier side (evaluate_constraint_quotients_at_point) is host QM31 code; the prover side evaluates every row of the
-evaluation domain in one tstwo_air_constraint_quotients launch per component, and the domain accumulator's finalize chains existing
-device entries (evaluate, accumulate, interpolate).  Nothing is read back to the host on the prover side."""
+Follows Rust stwo's air/accumulation.rs and air/components.rs, which the reference carries as shapes in air/accumulator.ts and
+air/components.ts (their logic there is stubbed).  The components themselves are constraint_framework.FrameworkComponents (wide
+Fibonacci and mul-add included); this module holds what every component shares: the point and domain accumulators, the vanishing
+polynomial and the denominators, trace locations, and the verifier's and prover's views of a component set.  The domain
+accumulator's finalize chains existing device entries (evaluate, accumulate, interpolate); nothing is read back to the host on the
+prover side.  evaluate_constraint_quotients wraps the hand-written constraint kernel (TSTWO_AIR_*), generate_wide_fib_trace the
+wide Fibonacci trace generator.  air.WideFibonacciComponent and air.MulAddComponent still resolve, to the functions of
+constraint_framework."""
 from __future__ import annotations
 
 import ctypes as C
@@ -134,7 +134,7 @@ class DomainEvaluationAccumulator:
         return cur
 
 
-# ------------------------------------------------------------------ components
+# ------------------------------------------------------------------ trace locations and the committed trace
 class TraceLocationAllocator:
     """Consecutive column ranges per tree, in allocation order, so that several components share one trace tree."""
 
@@ -162,78 +162,7 @@ class Trace:
         return Trace(commitment_scheme.polynomials(), commitment_scheme.evaluations())
 
 
-class FrameworkComponent:
-    """A component whose constraints read only their own row of `n_columns` main-trace columns of log size `log_size`, with
-    constraint degree 2 (max_constraint_log_degree_bound = log_size + 1).  Subclasses give `kind` (TSTWO_AIR_*), `n_columns`,
-    `n_constraints` and `constraints_at(values)` (the host form, for the verifier)."""
-
-    kind = None
-    LOG_CONSTRAINT_DEGREE = 1
-
-    def __init__(self, location_allocator: TraceLocationAllocator | None, log_size: int, n_columns: int, n_constraints: int):
-        if log_size < 1:
-            raise ValueError("log_size must be at least 1")
-        self.log_size, self.n_columns, self.n_constraints = log_size, n_columns, n_constraints
-        alloc = location_allocator or TraceLocationAllocator()
-        self.trace_locations = alloc.next_for_structure({ORIGINAL_TRACE_IDX: n_columns})
-
-    # --- Component
-    def max_constraint_log_degree_bound(self) -> int:
-        return self.log_size + self.LOG_CONSTRAINT_DEGREE
-
-    def trace_log_degree_bounds(self) -> list:
-        """TreeVec of column log sizes: the (empty) preprocessed tree, then this component's main-trace columns."""
-        return [[], [self.log_size] * self.n_columns]
-
-    def mask_points(self, point: CirclePoint) -> list:
-        return [[], [[point] for _ in range(self.n_columns)]]
-
-    def _columns(self) -> range:
-        start, end = self.trace_locations[ORIGINAL_TRACE_IDX]
-        return range(start, end)
-
-    def evaluate_constraint_quotients_at_point(self, point: CirclePoint, mask: list, acc: PointEvaluationAccumulator) -> None:
-        """PointEvaluator: each constraint at the OODS point times 1 / coset_vanishing(trace coset, point), in constraint order."""
-        denom_inv = coset_vanishing(CanonicCoset(self.log_size).coset, point).inverse()
-        values = []
-        for ci in self._columns():
-            col = mask[ORIGINAL_TRACE_IDX][ci]
-            if len(col) != 1:
-                raise ValueError("one sampled value per column expected")
-            values.append(col[0])
-        for c in self.constraints_at(values):
-            acc.accumulate(c.mul(denom_inv))
-
-    def constraints_at(self, values: list) -> list:
-        raise NotImplementedError
-
-    # --- ComponentProver
-    def trace_on_eval_domain(self, trace: Trace, twiddles: TwiddleTree) -> list:
-        """This component's columns on CanonicCoset(max_constraint_log_degree_bound).circle_domain(): the committed evaluation when
-        it already lives there (log blowup 1), else the polynomials evaluated there (one batched launch sequence)."""
-        eval_domain = CanonicCoset(self.max_constraint_log_degree_bound()).circleDomain()
-        cols, missing = [], []
-        for ci in self._columns():
-            ev = trace.evals[ORIGINAL_TRACE_IDX][ci]
-            if ev.domain == eval_domain:
-                cols.append(ev.values)
-            else:
-                cols.append(None)
-                missing.append(len(cols) - 1)
-        if missing:
-            polys = [trace.polys[ORIGINAL_TRACE_IDX][self._columns()[k]] for k in missing]
-            for k, ev in zip(missing, evaluate_polynomials(polys, eval_domain, twiddles)):
-                cols[k] = ev.values
-        return cols
-
-    def evaluate_constraint_quotients_on_domain(self, trace: Trace, acc: DomainEvaluationAccumulator, twiddles: TwiddleTree) -> None:
-        eval_log = self.max_constraint_log_degree_bound()
-        cols = self.trace_on_eval_domain(trace, twiddles)
-        [column_acc] = acc.columns([(eval_log, self.n_constraints)])
-        evaluate_constraint_quotients(self.kind, cols, self.log_size, eval_log - self.log_size, column_acc.random_coeff_powers,
-                                      denominator_inverses(self.log_size, eval_log), column_acc.col)
-
-
+# ------------------------------------------------------------------ the hand-written constraint kernel, the wide Fibonacci trace
 def evaluate_constraint_quotients(kind: int, cols, trace_log_size: int, log_expand: int, coeffs, denom_inv, accum: SecureColumnByCoords) -> None:
     """tstwo_air_constraint_quotients: accum[r] += sum_i coeffs[i] c_i(r) * denom_inv[r >> trace_log_size] over the trace `cols` on
     the evaluation domain of log size trace_log_size + log_expand (bit-reversed)."""
@@ -241,32 +170,6 @@ def evaluate_constraint_quotients(kind: int, cols, trace_log_size: int, log_expa
     dinv = L.u32x([d.value if isinstance(d, M31) else int(d) for d in denom_inv])
     L.call("tstwo_air_constraint_quotients", kind, L.ptr_array([c.ptr for c in cols]), len(cols), trace_log_size, log_expand,
            words, len(coeffs), dinv, accum.ptrs())
-
-
-class WideFibonacciComponent(FrameworkComponent):
-    """WideFibonacciEval<N> (examples/fibonacci.ts): N columns, N - 2 constraints x_{i+2} = x_i^2 + x_{i+1}^2."""
-
-    kind = AIR_WIDE_FIB
-
-    def __init__(self, log_n_rows: int, n_columns: int = 100, location_allocator: TraceLocationAllocator | None = None):
-        if n_columns < 3:
-            raise ValueError("wide Fibonacci needs at least 3 columns")
-        super().__init__(location_allocator, log_n_rows, n_columns, n_columns - 2)
-
-    def constraints_at(self, v: list) -> list:
-        return [v[i + 2].sub(v[i].square().add(v[i + 1].square())) for i in range(self.n_columns - 2)]
-
-
-class MulAddComponent(FrameworkComponent):
-    """TestEval of the Rust tutorial's example 05: 3 columns, x_0 x_1 + x_0 - x_2 = 0."""
-
-    kind = AIR_MUL_ADD
-
-    def __init__(self, log_n_rows: int, location_allocator: TraceLocationAllocator | None = None):
-        super().__init__(location_allocator, log_n_rows, 3, 1)
-
-    def constraints_at(self, v: list) -> list:
-        return [v[0].mul(v[1]).add(v[0]).sub(v[2])]
 
 
 def generate_wide_fib_trace(log_n: int, a, b, n_columns: int = 100) -> list:
@@ -280,6 +183,15 @@ def generate_wide_fib_trace(log_n: int, a, b, n_columns: int = 100) -> list:
     L.call("tstwo_air_wide_fib_trace", C.c_void_p(a.ptr), C.c_void_p(b.ptr), log_n, L.ptr_array([c.ptr for c in cols]), n_columns)
     domain = CanonicCoset(log_n).circleDomain()
     return [HipCircleEvaluation(domain, c) for c in cols]
+
+
+def __getattr__(name):
+    """air.WideFibonacciComponent / air.MulAddComponent, where callers found them before: the functions of constraint_framework
+    (imported on first use, since constraint_framework imports this module)."""
+    if name in ("WideFibonacciComponent", "MulAddComponent"):
+        from . import constraint_framework
+        return getattr(constraint_framework, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 # ------------------------------------------------------------------ component sets (air/components.rs)
@@ -302,7 +214,7 @@ class Components:
         self.components = list(components)
         self.n_preprocessed_columns = n_preprocessed_columns
         for c in self.components:
-            for idx in getattr(c, "preprocessed_column_indices", ()):
+            for idx in c.preprocessed_column_indices:
                 if not 0 <= idx < n_preprocessed_columns:
                     raise ValueError(f"preprocessed column {idx} out of range (the preprocessed tree has {n_preprocessed_columns})")
 
@@ -314,10 +226,10 @@ class Components:
         pts = _concat_cols([c.mask_points(point) for c in self.components])
         while len(pts) <= ORIGINAL_TRACE_IDX:
             pts.append([])
-        if self.n_preprocessed_columns or any(getattr(c, "preprocessed_column_indices", ()) for c in self.components):
+        if self.n_preprocessed_columns or any(c.preprocessed_column_indices for c in self.components):
             pre = [[] for _ in range(self.n_preprocessed_columns)]
             for c in self.components:
-                for idx in getattr(c, "preprocessed_column_indices", ()):
+                for idx in c.preprocessed_column_indices:
                     pre[idx] = [point]
             pts[PREPROCESSED_TRACE_IDX] = pre
         return pts
@@ -326,10 +238,10 @@ class Components:
         sizes = _concat_cols([c.trace_log_degree_bounds() for c in self.components])
         while len(sizes) <= ORIGINAL_TRACE_IDX:
             sizes.append([])
-        if self.n_preprocessed_columns or any(getattr(c, "preprocessed_column_indices", ()) for c in self.components):
+        if self.n_preprocessed_columns or any(c.preprocessed_column_indices for c in self.components):
             pre, seen = [0] * self.n_preprocessed_columns, set()
             for c in self.components:
-                for idx, lg in zip(getattr(c, "preprocessed_column_indices", ()), c.trace_log_degree_bounds()[PREPROCESSED_TRACE_IDX]):
+                for idx, lg in zip(c.preprocessed_column_indices, c.trace_log_degree_bounds()[PREPROCESSED_TRACE_IDX]):
                     if idx in seen and pre[idx] != lg:
                         raise ValueError(f"preprocessed column {idx} read with two log sizes ({pre[idx]} and {lg})")
                     pre[idx] = lg

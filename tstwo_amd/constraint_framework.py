@@ -1,14 +1,16 @@
-"""A constraint framework for user-defined AIRs (Rust stwo constraint_framework/: FrameworkEval, EvalAtRow, InfoEvaluator,
+"""The constraint framework: every AIR component (Rust stwo constraint_framework/: FrameworkEval, EvalAtRow, InfoEvaluator,
 PointEvaluator, FrameworkComponent; the reference carries the shapes in constraint_framework/index.ts).
 
-A component is defined by one `evaluate(eval)` function.  Three evaluators drive it:
+A component is a FrameworkComponent of an eval, an object with `log_size()`, `max_constraint_log_degree_bound()` and one
+`evaluate(eval)` function.  Three evaluators drive it:
   InfoEvaluator     the mask offsets of each column, the number of constraints and the degree of each;
   ProgramEvaluator  the constraints as a straight-line program for tstwo_air_eval_program (include/tstwo_hip.h): identical loads
                     (same column and offset) and identical sub-expressions are computed once, registers are reused after their
                     last use, and the number of live registers is bounded by MAX_REGS;
   PointEvaluator    the constraints over QM31 at the out-of-domain point (the verifier, and the prover's sanity check).
-FrameworkComponent turns an eval into a component that `prover.prove` / `prover.verify` accept beside the hand-written ones of
-air.py: the prover evaluates its constraints on the whole evaluation domain with one tstwo_air_eval_program launch.
+The prover evaluates a component's constraints on the whole evaluation domain with one launch: WideFibonacciEval and MulAddEval
+(exactly these types, not subclasses) run on the hand-written kernel of tstwo_air_constraint_quotients, every other eval on the
+program interpreter.  WideFibonacciComponent and MulAddComponent are FrameworkComponents of those two evals, as in Rust.
 
 Only the main trace (ORIGINAL_TRACE_IDX) is read at row offsets; preprocessed columns are read at offset 0 (as in Rust), and values
 inside constraints are base-field (M31) values: interaction trees and secure-field (LogUp) columns are not supported.
@@ -19,8 +21,9 @@ import bisect
 import ctypes as C
 
 from . import _lib as L
-from .air import (ORIGINAL_TRACE_IDX, PREPROCESSED_TRACE_IDX, DomainEvaluationAccumulator, PointEvaluationAccumulator,
-                  TraceLocationAllocator, coset_vanishing, denominator_inverses, _lift)
+from .air import (AIR_MUL_ADD, AIR_WIDE_FIB, ORIGINAL_TRACE_IDX, PREPROCESSED_TRACE_IDX, DomainEvaluationAccumulator,
+                  PointEvaluationAccumulator, TraceLocationAllocator, coset_vanishing, denominator_inverses,
+                  evaluate_constraint_quotients, _lift)
 from .backend import SecureColumnByCoords
 from .circle import CanonicCoset, CirclePoint, bit_reverse_index
 from .fields import M31, QM31, P
@@ -449,8 +452,8 @@ def evaluate_program(cols, trace_log_size: int, log_expand: int, program: Progra
 class FrameworkComponent:
     """A component defined by a FrameworkEval (`log_size()`, `max_constraint_log_degree_bound()`, `evaluate(eval)`).  Its main
     columns are allocated in the main trace tree by `location_allocator`; `preprocessed_column_indices[i]` is the position in the
-    preprocessed tree (tree 0) of the column `get_preprocessed_column(i)` reads.  Implements the Component / ComponentProver
-    methods of air.FrameworkComponent, so it mixes with the hand-written components in prover.prove / prover.verify."""
+    preprocessed tree (tree 0) of the column `get_preprocessed_column(i)` reads.  `kind` is the TSTWO_AIR_* kind of the
+    hand-written kernel for the eval's exact type (None: the program path, and `program` holds the compiled constraints)."""
 
     def __init__(self, eval_, location_allocator: TraceLocationAllocator | None = None, preprocessed_column_indices=None):
         self.eval = eval_
@@ -474,9 +477,12 @@ class FrameworkComponent:
             raise ValueError(f"evaluate reads {inf.n_preprocessed()} preprocessed columns, {len(self.preprocessed_column_indices)} named")
         alloc = location_allocator or TraceLocationAllocator()
         self.trace_locations = alloc.next_for_structure({ORIGINAL_TRACE_IDX: self.n_columns})
-        pe = ProgramEvaluator()
-        eval_.evaluate(pe)
-        self.program = pe.compile(self.n_columns)
+        self.kind = _HAND_WRITTEN_KINDS.get(type(eval_))
+        self.program = None
+        if self.kind is None:
+            pe = ProgramEvaluator()
+            eval_.evaluate(pe)
+            self.program = pe.compile(self.n_columns)
 
     # --- Component
     def max_constraint_log_degree_bound(self) -> int:
@@ -523,18 +529,89 @@ class FrameworkComponent:
                 cols[k] = ev.values
         return cols
 
+    def trace_on_eval_domain(self, trace, twiddles) -> list:
+        """The columns the kernels read, on CanonicCoset(max_constraint_log_degree_bound).circle_domain(): the main columns, then
+        the preprocessed ones; each the committed evaluation when it already lives there (log blowup 1), else its polynomial
+        evaluated there (one batched launch sequence per tree)."""
+        return (self._on_eval_domain(trace, ORIGINAL_TRACE_IDX, self._columns(), twiddles)
+                + self._on_eval_domain(trace, PREPROCESSED_TRACE_IDX, self.preprocessed_column_indices, twiddles))
+
     def evaluate_constraint_quotients_on_domain(self, trace, acc: DomainEvaluationAccumulator, twiddles) -> None:
         eval_log = self.max_constraint_log_degree_bound()
-        cols = (self._on_eval_domain(trace, ORIGINAL_TRACE_IDX, self._columns(), twiddles)
-                + self._on_eval_domain(trace, PREPROCESSED_TRACE_IDX, self.preprocessed_column_indices, twiddles))
+        cols = self.trace_on_eval_domain(trace, twiddles)
         [column_acc] = acc.columns([(eval_log, self.n_constraints)])
         if self.n_constraints == 0:
             return
-        evaluate_program(cols, self.log_size, eval_log - self.log_size, self.program, column_acc.random_coeff_powers,
-                         denominator_inverses(self.log_size, eval_log), column_acc.col)
+        coeffs, denom_inv = column_acc.random_coeff_powers, denominator_inverses(self.log_size, eval_log)
+        if self.kind is not None:
+            evaluate_constraint_quotients(self.kind, cols, self.log_size, eval_log - self.log_size, coeffs, denom_inv, column_acc.col)
+        else:
+            evaluate_program(cols, self.log_size, eval_log - self.log_size, self.program, coeffs, denom_inv, column_acc.col)
 
 
-# ------------------------------------------------------------------ example: Fibonacci over rows
+# ------------------------------------------------------------------ evals: wide Fibonacci, mul-add, Fibonacci over rows
+class WideFibonacciEval:
+    """WideFibonacciEval<N> (examples/fibonacci.ts): N columns, N - 2 constraints x_{i+2} = x_i^2 + x_{i+1}^2 on each row."""
+
+    def __init__(self, log_n_rows: int, n_columns: int = 100):
+        if n_columns < 3:
+            raise ValueError("wide Fibonacci needs at least 3 columns")
+        self.log_n_rows, self.n_columns = log_n_rows, n_columns
+
+    def log_size(self) -> int:
+        return self.log_n_rows
+
+    def max_constraint_log_degree_bound(self) -> int:
+        return self.log_n_rows + 1
+
+    def evaluate(self, eval):
+        a, b = eval.next_trace_mask(), eval.next_trace_mask()
+        for _ in range(2, self.n_columns):
+            c = eval.next_trace_mask()
+            eval.add_constraint(c - (a.square() + b.square()))
+            a, b = b, c
+        return eval
+
+    logSize = log_size
+    maxConstraintLogDegreeBound = max_constraint_log_degree_bound
+
+
+class MulAddEval:
+    """TestEval of the Rust tutorial's example 05: 3 columns, x_0 x_1 + x_0 - x_2 = 0 on each row."""
+
+    def __init__(self, log_n_rows: int):
+        self.log_n_rows = log_n_rows
+
+    def log_size(self) -> int:
+        return self.log_n_rows
+
+    def max_constraint_log_degree_bound(self) -> int:
+        return self.log_n_rows + 1
+
+    def evaluate(self, eval):
+        x0, x1, x2 = eval.next_trace_mask(), eval.next_trace_mask(), eval.next_trace_mask()
+        eval.add_constraint(x0 * x1 + x0 - x2)
+        return eval
+
+    logSize = log_size
+    maxConstraintLogDegreeBound = max_constraint_log_degree_bound
+
+
+# the evals whose exact type runs on the hand-written kernel (2.8x faster than the interpreter on wide Fibonacci)
+_HAND_WRITTEN_KINDS = {WideFibonacciEval: AIR_WIDE_FIB, MulAddEval: AIR_MUL_ADD}
+
+
+def WideFibonacciComponent(log_n_rows: int, n_columns: int = 100,
+                           location_allocator: TraceLocationAllocator | None = None) -> FrameworkComponent:
+    """Rust's `type WideFibonacciComponent = FrameworkComponent<WideFibonacciEval<N>>`."""
+    return FrameworkComponent(WideFibonacciEval(log_n_rows, n_columns), location_allocator)
+
+
+def MulAddComponent(log_n_rows: int, location_allocator: TraceLocationAllocator | None = None) -> FrameworkComponent:
+    """FrameworkComponent<MulAddEval>."""
+    return FrameworkComponent(MulAddEval(log_n_rows), location_allocator)
+
+
 def coset_index_to_circle_domain_index(coset_index: int, log_domain_size: int) -> int:
     """utils.rs: the circle-domain index of the point at `coset_index` of CanonicCoset(log_domain_size)."""
     if coset_index % 2 == 0:

@@ -1,19 +1,37 @@
 // air.hip — constraint evaluation of an AIR over its trace on the evaluation domain (the device form of Rust stwo's
 // FrameworkComponent::evaluate_constraint_quotients_on_domain, constraint_framework/component.rs; the reference carries the shapes in
-// constraint_framework/index.ts and air/accumulator.ts) for constraints that read only their own row (mask offset 0), and the wide
-// Fibonacci trace generator (examples/fibonacci.ts generateTrace, Rust examples/wide_fibonacci generate_trace).
-//
-// Constraint kinds:
-//   TSTWO_AIR_WIDE_FIB  N >= 3 columns, c_i = x_{i+2} - (x_i^2 + x_{i+1}^2), i < N - 2  (WideFibonacciEval<N>)
-//   TSTWO_AIR_MUL_ADD   3 columns,      c_0 = x_0 x_1 + x_0 - x_2                        (TestEval of the Rust tutorial's example 05)
+// constraint_framework/index.ts and air/accumulator.ts), and the wide Fibonacci trace generator (examples/fibonacci.ts
+// generateTrace, Rust examples/wide_fibonacci generate_trace).  Two kernels evaluate constraints, with one contract:
+//   k_constraint_quotients<KIND, W>  hand-written constraints that read only their own row (mask offset 0):
+//     TSTWO_AIR_WIDE_FIB  N >= 3 columns, c_i = x_{i+2} - (x_i^2 + x_{i+1}^2), i < N - 2  (WideFibonacciEval<N>)
+//     TSTWO_AIR_MUL_ADD   3 columns,      c_0 = x_0 x_1 + x_0 - x_2                        (TestEval of the Rust tutorial's example 05)
+//   k_air_program<W>  any constraints, as a straight-line program (tstwo_amd/constraint_framework.py compiles a FrameworkEval's
+//     `evaluate` into it) interpreted for every row, with loads at row offsets (Rust stwo constraint_framework:
+//     next_interaction_mask with offsets, utils.rs offset_bit_reversed_circle_domain_index).
 // Row r (bit-reversed order on CanonicCoset(trace_log + log_expand).circle_domain()):
 //   row_res = sum_i coeff_i c_i(r),   accum[r] += row_res * denom_inv[r >> trace_log]
 //
-// One lane owns W = 4 consecutive rows (16-byte loads: a wave reads 1 KiB of one column at a time, coalesced) and sweeps the columns
-// once: every column is squared once, the last two squares stay in registers.  The four coordinates of row_res are sums of
-// M31 x M31 products, kept in 64 bits: a product of canonical values is < 2^62, so four of them and a folded remainder (< 2^33) fit;
-// the sum is folded (and/alignbit, no reduction to canonical) after every fourth constraint and reduced once per row at the end.
-// The coefficients and the denominators travel in the kernel argument segment and are read with scalar loads (wave-uniform index).
+// Both: one lane owns W = 4 consecutive rows (16-byte loads: a wave reads 1 KiB of one column at a time, coalesced) when every
+// column and accumulator is 16-byte aligned, else W = 1.  The four coordinates of row_res are sums of M31 x M31 products, kept in
+// 64 bits: a product of canonical values is < 2^62, so four of them and a folded remainder (< 2^33) fit; the sum is folded
+// (and/alignbit, no reduction to canonical) after every fourth constraint and reduced once per row at the end.  The denominators
+// travel in the kernel argument segment.
+//
+// k_constraint_quotients sweeps the columns once: every column is squared once, the last two squares stay in registers.  The
+// coefficients travel in the kernel argument segment and are read with scalar loads (wave-uniform index).
+//
+// k_air_program reads the program words with scalar loads (constant address space, wave-uniform program counter), so the opcode
+// lands in an SGPR and every dispatch is a scalar branch — no lane branches on an opcode.
+// Temporaries: a register file in LDS, [reg][lane] of W-word vectors (one 16-byte slot per lane and register when W = 4).  A lane
+// only touches its own slots, so no barrier is needed; registers indexed at run time never reach private (scratch) memory.
+// Workgroups are one wave: the LDS a workgroup needs is n_regs KiB (W = 4), and residency falls with it, not with a block size.
+// Loads at offset 0 of W = 4 rows are one 16-byte global load; loads at other offsets gather per row (the neighbour of four
+// consecutive rows is not four consecutive rows: rows r and r + 1 sit in opposite halves of the circle domain and move in
+// opposite directions), with the index computed per row.  Across a wave the gathered rows are still runs of consecutive rows
+// (the offset moves the high bits of r), so the loads of one instruction cover the same cache lines as an offset-0 load.
+#include <algorithm>
+#include <string>
+
 #include "common.h"
 
 using namespace tstwo;
@@ -21,10 +39,12 @@ using namespace tstwo;
 namespace {
 
 constexpr int kThreads = 256;
+constexpr int kWave = 64;
 constexpr u32 kMaxConstraints = 128;         // 4 x 128 coefficient words in the kernel argument (N <= 130 wide-Fibonacci columns)
 constexpr u32 kMaxLogExpand = 4;
 constexpr u32 kMaxDenoms = 1u << kMaxLogExpand;
 constexpr u32 kMaxLog = 28;                  // word offsets of gload*/gstore* stay below 2^30
+static_assert(TSTWO_AIR_PROGRAM_MAX_COLS <= 0x10000, "the column operand is 16 bits wide");
 
 struct AirArgs {
     u32 coeff[4 * kMaxConstraints];          // QM31 coefficient of constraint i at [4i, 4i + 4)
@@ -37,22 +57,70 @@ constexpr int kArgsOff = (int)sizeof(ColPtrs);
 static_assert(sizeof(ColPtrs) % 8 == 0, "AirArgs must follow ColPtrs without padding");
 static_assert(sizeof(ColPtrs) + sizeof(AirArgs) <= 4096, "kernel arguments exceed 4 KiB");
 
+struct ProgArgs {
+    const u32 *prog;                         // device: 2 words per instruction, then 4 coefficient words per constraint
+    u32 denom_inv[kMaxDenoms];
+    Soa4 acc;
+    u32 n_instr, n_rows, trace_log, eval_log, log_expand, n_denoms;
+};
+
+// ---------------------------------------------------------------- shared by both kernels
+template <int W>
+__device__ __forceinline__ void load_rows(const u32 *col, u32 row, u32 (&x)[W]) {
+    if constexpr (W == 4) {
+        const uint4 v = gload4(col, row);
+        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+    } else {
+        x[0] = gload1(col, row);
+    }
+}
+
+// x = t1 + 2^31 t2 + 2^63 t3 == t1 + t2 + 2 t3 (mod P), < 2^31 + 2 + 2^32 < 2^33: room for four more products
+__device__ __forceinline__ u64 fold64(u64 x) {
+    const u32 lo = (u32)x, hi = (u32)(x >> 32);
+    const u32 t2 = __builtin_amdgcn_alignbit(hi, lo, 31);
+    return (u64)((lo & M31_P) + ((hi >> 31) << 1)) + t2;
+}
+template <int W>
+__device__ __forceinline__ void fold_all(u64 (&acc)[W][4]) {
+#pragma unroll
+    for (int e = 0; e < W; e++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc[e][j] = fold64(acc[e][j]);
+}
+
+// The row epilogue of both kernels: accum[row + e] += reduce(acc[e]) * denom_inv[(row + e) >> trace_log], `a` the kernel's AirArgs
+// or ProgArgs.  A macro, not a function: handing the kernel argument to a function, even a forced-inline one, changes how the
+// compiler schedules the scalar loads of the denominator table and the accumulator pointers.
+#define TSTWO_AIR_ADD_ROWS(W, a, row, acc)                                                                                      \
+    do {                                                                                                                        \
+        u32 r_[4][W];                                                                                                           \
+        _Pragma("unroll") for (int e = 0; e < W; e++) {                                                                         \
+            /* denom_inv[(row + e) >> trace_log]: a select over the (<= 16, wave-uniform) table, no indexed private array */   \
+            const u32 di = ((row) + e) >> (a).trace_log;                                                                        \
+            u32 d = (a).denom_inv[0];                                                                                           \
+            _Pragma("unroll") for (u32 k = 1; k < kMaxDenoms; k++)                                                              \
+                if (k < (a).n_denoms && di == k) d = (a).denom_inv[k];                                                          \
+            _Pragma("unroll") for (int j = 0; j < 4; j++) r_[j][e] = m31_mul(m31_reduce_u64((acc)[e][j]), d);                   \
+        }                                                                                                                       \
+        _Pragma("unroll") for (int j = 0; j < 4; j++) {                                                                         \
+            if constexpr (W == 4) {                                                                                             \
+                const uint4 o = gload4((a).acc.p[j], row);                                                                      \
+                gstore4((a).acc.p[j], row, make_uint4(m31_add(o.x, r_[j][0]), m31_add(o.y, r_[j][1]), m31_add(o.z, r_[j][2]),   \
+                                                      m31_add(o.w, r_[j][3])));                                                 \
+            } else {                                                                                                            \
+                gstore1((a).acc.p[j], row, m31_add(gload1((a).acc.p[j], row), r_[j][0]));                                       \
+            }                                                                                                                   \
+        }                                                                                                                       \
+    } while (0)
+
+// ---------------------------------------------------------------- hand-written constraints
 // coefficient word j of constraint i straight from the kernel argument segment: one scalar load (no copy of the array to scratch)
 __device__ __forceinline__ u32 coeff_word(u32 i, u32 j) {
     typedef const u32 __attribute__((address_space(4))) *k32;
     typedef const char __attribute__((address_space(4))) *kbytes;
     const k32 c = (k32)((kbytes)__builtin_amdgcn_kernarg_segment_ptr() + kArgsOff + offsetof(AirArgs, coeff));
     return c[(u32)__builtin_amdgcn_readfirstlane((int)(4 * i + j))];
-}
-
-template <int W>
-__device__ __forceinline__ void load_rows(const u32 *col, u32 row, u32 (&x)[W]) {
-    if (W == 4) {
-        const uint4 v = gload4(col, row);
-        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-    } else {
-        x[0] = gload1(col, row);
-    }
 }
 
 // acc[e][j] += coeff_i[j] * c[e]
@@ -66,19 +134,6 @@ __device__ __forceinline__ void accumulate(u64 (&acc)[W][4], u32 i, const u32 (&
         acc[e][2] += (u64)q2 * c[e];
         acc[e][3] += (u64)q3 * c[e];
     }
-}
-// x = t1 + 2^31 t2 + 2^63 t3 == t1 + t2 + 2 t3 (mod P), < 2^31 + 2 + 2^32 < 2^33: room for four more products
-__device__ __forceinline__ u64 fold64(u64 x) {
-    const u32 lo = (u32)x, hi = (u32)(x >> 32);
-    const u32 t2 = __builtin_amdgcn_alignbit(hi, lo, 31);
-    return (u64)((lo & M31_P) + ((hi >> 31) << 1)) + t2;
-}
-template <int W>
-__device__ __forceinline__ void fold_all(u64 (&acc)[W][4]) {
-#pragma unroll
-    for (int e = 0; e < W; e++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) acc[e][j] = fold64(acc[e][j]);
 }
 
 // row_res of rows [row, row + W) into acc (unreduced)
@@ -135,27 +190,7 @@ __global__ void __launch_bounds__(kThreads) k_constraint_quotients(ColPtrs cols,
 #pragma unroll
             for (int j = 0; j < 4; j++) acc[e][j] = 0;
         eval_rows<KIND, W>(cols, a, row, acc);
-        u32 r[4][W];
-#pragma unroll
-        for (int e = 0; e < W; e++) {
-            // denom_inv[(row + e) >> trace_log]: a select over the (<= 16, wave-uniform) table, no indexed private array
-            const u32 di = (row + e) >> a.trace_log;
-            u32 d = a.denom_inv[0];
-#pragma unroll
-            for (u32 k = 1; k < kMaxDenoms; k++)
-                if (k < a.n_denoms && di == k) d = a.denom_inv[k];
-#pragma unroll
-            for (int j = 0; j < 4; j++) r[j][e] = m31_mul(m31_reduce_u64(acc[e][j]), d);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (W == 4) {
-                const uint4 o = gload4(a.acc.p[j], row);
-                gstore4(a.acc.p[j], row, make_uint4(m31_add(o.x, r[j][0]), m31_add(o.y, r[j][1]), m31_add(o.z, r[j][2]), m31_add(o.w, r[j][3])));
-            } else {
-                gstore1(a.acc.p[j], row, m31_add(gload1(a.acc.p[j], row), r[j][0]));
-            }
-        }
+        TSTWO_AIR_ADD_ROWS(W, a, row, acc);
     }
 }
 
@@ -193,16 +228,155 @@ __global__ void __launch_bounds__(kThreads) k_wide_fib_trace(ColPtrs out, const 
     }
 }
 
+// ---------------------------------------------------------------- the program interpreter
+typedef const u32 __attribute__((address_space(4))) *k32;
+
+__device__ __forceinline__ u32 uni(u32 x) { return (u32)__builtin_amdgcn_readfirstlane((int)x); }
+
+// offset_bit_reversed_circle_domain_index: the bit-reversed position of the row `off` trace steps away from row r.  One trace
+// step is 2^(log_expand - 1) steps of the evaluation domain's half coset; the first half of the domain walks forward, the
+// second (the conjugates) backward.
+__device__ __forceinline__ u32 neighbour_row(u32 r, u32 eval_log, u32 log_expand, int off) {
+    const u32 i = __builtin_bitreverse32(r) >> (32 - eval_log);
+    const u32 half = 1u << (eval_log - 1);
+    const u32 step = (u32)off << (log_expand - 1);
+    const u32 hi = i & half;
+    const u32 j = ((hi ? i - step : i + step) & (half - 1)) | hi;
+    return __builtin_bitreverse32(j) >> (32 - eval_log);
+}
+
+template <int W>
+__device__ __forceinline__ void lds_read(const u32 *regs, u32 reg, u32 (&v)[W]) {
+    const u32 lane = threadIdx.x;
+    if constexpr (W == 4) {
+        const uint4 x = *(const uint4 *)(regs + (reg * kWave + lane) * 4);
+        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+    } else {
+        v[0] = regs[reg * kWave + lane];
+    }
+}
+template <int W>
+__device__ __forceinline__ void lds_write(u32 *regs, u32 reg, const u32 (&v)[W]) {
+    const u32 lane = threadIdx.x;
+    if constexpr (W == 4) *(uint4 *)(regs + (reg * kWave + lane) * 4) = make_uint4(v[0], v[1], v[2], v[3]);
+    else regs[reg * kWave + lane] = v[0];
+}
+
+template <int W>
+__global__ void __launch_bounds__(kWave) k_air_program(ColPtrs cols, ProgArgs a) {
+    extern __shared__ u32 regs[];
+    const k32 prog = (k32)a.prog;
+    const u32 coeff_base = 2 * a.n_instr;
+    const u32 stride = gridDim.x * kWave;
+    for (u32 t = blockIdx.x * kWave + threadIdx.x; t < a.n_rows / W; t += stride) {
+        const u32 row = t * W;
+        u64 acc[W][4];
+#pragma unroll
+        for (int e = 0; e < W; e++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) acc[e][j] = 0;
+        u32 n_acc = 0;
+#pragma unroll 1
+        for (u32 pc = 0; pc < a.n_instr; pc++) {
+            const u32 w0 = prog[uni(2 * pc)], w1 = prog[uni(2 * pc + 1)];
+            const u32 op = w0 & 0xffu, dst = (w0 >> 8) & 0xffu, x = w0 >> 16;
+            u32 v[W];
+            if (op == TSTWO_AIR_OP_LOAD) {
+                const u32 *col = colp_u(cols, x);
+                const int off = (int)w1;
+                if (off == 0) {
+                    load_rows<W>(col, row, v);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < W; e++) v[e] = gload1(col, neighbour_row(row + e, a.eval_log, a.log_expand, off));
+                }
+            } else if (op == TSTWO_AIR_OP_CONST) {
+#pragma unroll
+                for (int e = 0; e < W; e++) v[e] = w1;
+            } else if (op == TSTWO_AIR_OP_ACC) {
+                lds_read<W>(regs, x, v);
+                const u32 k = uni(coeff_base + 4 * n_acc);
+                const u32 q0 = prog[k], q1 = prog[k + 1], q2 = prog[k + 2], q3 = prog[k + 3];
+#pragma unroll
+                for (int e = 0; e < W; e++) {
+                    acc[e][0] += (u64)q0 * v[e];
+                    acc[e][1] += (u64)q1 * v[e];
+                    acc[e][2] += (u64)q2 * v[e];
+                    acc[e][3] += (u64)q3 * v[e];
+                }
+                if ((++n_acc & 3) == 0) fold_all<W>(acc);
+                continue;
+            } else {
+                u32 p[W];
+                lds_read<W>(regs, x, p);
+                if (op == TSTWO_AIR_OP_SQR) {
+#pragma unroll
+                    for (int e = 0; e < W; e++) v[e] = m31_sqr(p[e]);
+                } else if (op == TSTWO_AIR_OP_NEG) {
+#pragma unroll
+                    for (int e = 0; e < W; e++) v[e] = m31_neg(p[e]);
+                } else {
+                    u32 q[W];
+                    lds_read<W>(regs, w1, q);
+                    if (op == TSTWO_AIR_OP_ADD) {
+#pragma unroll
+                        for (int e = 0; e < W; e++) v[e] = m31_add(p[e], q[e]);
+                    } else if (op == TSTWO_AIR_OP_SUB) {
+#pragma unroll
+                        for (int e = 0; e < W; e++) v[e] = m31_sub(p[e], q[e]);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < W; e++) v[e] = m31_mul(p[e], q[e]);
+                    }
+                }
+            }
+            lds_write<W>(regs, dst, v);
+        }
+        TSTWO_AIR_ADD_ROWS(W, a, row, acc);
+    }
+}
+
+// ---------------------------------------------------------------- host
 unsigned grid_for(size_t work) {
     unsigned b = ceil_div(work, kThreads);
     const unsigned cap = (unsigned)ctx().n_cus * 16;
     if (b > cap) b = cap;
     return b ? b : 1;
 }
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 bool table_aligned16(const u32 *const *t, size_t n) {
     for (size_t i = 0; i < n; i++) if (!aligned16(t[i])) return false;
     return true;
+}
+
+int bad(const std::string &msg) { return set_error(TSTWO_ERR_BAD_ARG, msg); }
+
+// the limits of the evaluation domain; `prefix` starts each error text
+int check_domain(const char *prefix, u32 trace_log_size, u32 log_expand) {
+    if (log_expand > kMaxLogExpand) return bad(std::string(prefix) + "log_expand too large");
+    if (trace_log_size + log_expand > kMaxLog) return bad(std::string(prefix) + "evaluation domain too large");
+    return TSTWO_OK;
+}
+
+// range-checks the coefficient words (copied to coeff_dst) and the 2^log_expand denominators (copied into the kernel argument)
+template <class Args>
+int take_coeffs_and_denoms(const u32 *coeffs, size_t n_constraints, u32 *coeff_dst, const u32 *denom_inv, u32 log_expand, Args &a) {
+    for (size_t i = 0; i < 4 * n_constraints; i++) {
+        if (coeffs[i] >= M31_P) return bad("coefficient word out of range");
+        coeff_dst[i] = coeffs[i];
+    }
+    a.n_denoms = 1u << log_expand;
+    for (u32 i = 0; i < a.n_denoms; i++) {
+        if (denom_inv[i] >= M31_P) return bad("denominator out of range");
+        a.denom_inv[i] = denom_inv[i];
+    }
+    return TSTWO_OK;
+}
+
+// W = 4 rows per lane when the rows split into fours and every column and accumulator is 16-byte aligned
+bool four_rows_per_lane(u32 n_rows, const u32 *const *cols, size_t n_cols, u32 *const accum[4]) {
+    bool vec = n_rows % 4 == 0 && table_aligned16(cols, n_cols);
+    for (int j = 0; j < 4; j++) vec = vec && aligned16(accum[j]);
+    return vec;
 }
 
 template <int KIND>
@@ -237,28 +411,19 @@ int tstwo_air_constraint_quotients(u32 kind, const u32 *const *cols, size_t n_co
                                    const u32 *coeffs, size_t n_constraints, const u32 *denom_inv, u32 *const accum[4]) {
     TSTWO_REQUIRE_READY();
     if (kind == TSTWO_AIR_WIDE_FIB) {
-        if (n_cols < 3 || n_constraints != n_cols - 2) return set_error(TSTWO_ERR_BAD_ARG, "wide Fibonacci: N >= 3 columns, N - 2 constraints");
+        if (n_cols < 3 || n_constraints != n_cols - 2) return bad("wide Fibonacci: N >= 3 columns, N - 2 constraints");
     } else if (kind == TSTWO_AIR_MUL_ADD) {
-        if (n_cols != 3 || n_constraints != 1) return set_error(TSTWO_ERR_BAD_ARG, "mul-add: 3 columns, 1 constraint");
+        if (n_cols != 3 || n_constraints != 1) return bad("mul-add: 3 columns, 1 constraint");
     } else {
-        return set_error(TSTWO_ERR_BAD_ARG, "unknown constraint kind");
+        return bad("unknown constraint kind");
     }
-    if (n_constraints > kMaxConstraints) return set_error(TSTWO_ERR_BAD_ARG, "too many constraints in one component");
-    if (log_expand > kMaxLogExpand) return set_error(TSTWO_ERR_BAD_ARG, "log_expand too large");
-    if (trace_log_size + log_expand > kMaxLog) return set_error(TSTWO_ERR_BAD_ARG, "evaluation domain too large");
-    if (!coeffs || !denom_inv) return set_error(TSTWO_ERR_BAD_ARG, "null host argument");
+    if (n_constraints > kMaxConstraints) return bad("too many constraints in one component");
+    if (int rc = check_domain("", trace_log_size, log_expand)) return rc;
+    if (!coeffs || !denom_inv) return bad("null host argument");
     TSTWO_REQUIRE_TABLE(cols, n_cols);
     TSTWO_REQUIRE_TABLE(accum, 4);
     AirArgs a = {};
-    for (size_t i = 0; i < 4 * n_constraints; i++) {
-        if (coeffs[i] >= M31_P) return set_error(TSTWO_ERR_BAD_ARG, "coefficient word out of range");
-        a.coeff[i] = coeffs[i];
-    }
-    a.n_denoms = 1u << log_expand;
-    for (u32 i = 0; i < a.n_denoms; i++) {
-        if (denom_inv[i] >= M31_P) return set_error(TSTWO_ERR_BAD_ARG, "denominator out of range");
-        a.denom_inv[i] = denom_inv[i];
-    }
+    if (int rc = take_coeffs_and_denoms(coeffs, n_constraints, a.coeff, denom_inv, log_expand, a)) return rc;
     for (int j = 0; j < 4; j++) a.acc.p[j] = accum[j];
     a.n_cols = (u32)n_cols;
     a.n_constraints = (u32)n_constraints;
@@ -266,9 +431,93 @@ int tstwo_air_constraint_quotients(u32 kind, const u32 *const *cols, size_t n_co
     a.n_rows = 1u << (trace_log_size + log_expand);
     ColPtrs cp;
     if (int rc = fill_col_table(cp, cols, n_cols, 0)) return rc;
-    bool vec = a.n_rows % 4 == 0 && table_aligned16(cols, n_cols);
-    for (int j = 0; j < 4; j++) vec = vec && aligned16(accum[j]);
+    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, accum);
     return kind == TSTWO_AIR_WIDE_FIB ? launch_quotients<TSTWO_AIR_WIDE_FIB>(cp, a, vec) : launch_quotients<TSTWO_AIR_MUL_ADD>(cp, a, vec);
+}
+
+int tstwo_air_eval_program(const u32 *const *cols, size_t n_cols, u32 trace_log_size, u32 log_expand, const u32 *program,
+                           size_t program_len, const u32 *coeffs, size_t n_constraints, const u32 *denom_inv, u32 *const accum[4]) {
+    TSTWO_REQUIRE_READY();
+    if (log_expand < 1) return bad("air program: log_expand must be at least 1 (the neighbour index needs eval > trace)");
+    if (int rc = check_domain("air program: ", trace_log_size, log_expand)) return rc;
+    if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return bad("air program: number of columns out of range");
+    if (program_len == 0 || program_len > TSTWO_AIR_PROGRAM_MAX_INSTR) return bad("air program: program length out of range");
+    if (n_constraints == 0 || n_constraints > TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS) return bad("air program: number of constraints out of range");
+    if (!program || !coeffs || !denom_inv) return bad("null host argument");
+    TSTWO_REQUIRE_TABLE(cols, n_cols);
+    TSTWO_REQUIRE_TABLE(accum, 4);
+    // the program and coefficient words travel through the small-upload ring, which a captured graph cannot replay
+    {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(ctx().stream, &st) != hipSuccess) (void)hipGetLastError();
+        else if (st != hipStreamCaptureStatusNone)
+            return bad("host-array upload during graph capture (the air program and its coefficients cannot be recorded)");
+    }
+    // validate every instruction: opcodes, registers (each read one written before), columns, offsets, constants; count ACCs
+    bool written[TSTWO_AIR_PROGRAM_MAX_REGS] = {};
+    u32 n_regs = 0;
+    size_t n_acc = 0;
+    auto reg_ok = [&](u32 reg) { return reg < TSTWO_AIR_PROGRAM_MAX_REGS && written[reg]; };
+    for (size_t pc = 0; pc < program_len; pc++) {
+        const u32 w0 = program[2 * pc], w1 = program[2 * pc + 1];
+        const u32 op = w0 & 0xffu, dst = (w0 >> 8) & 0xffu, x = w0 >> 16;
+        switch (op) {
+            case TSTWO_AIR_OP_LOAD: {
+                if (x >= n_cols) return bad("air program: column out of range");
+                const int off = (int)w1;
+                if (off > TSTWO_AIR_PROGRAM_MAX_OFFSET || off < -TSTWO_AIR_PROGRAM_MAX_OFFSET) return bad("air program: row offset beyond the limit");
+                break;
+            }
+            case TSTWO_AIR_OP_CONST:
+                if (w1 >= M31_P) return bad("air program: constant out of range");
+                break;
+            case TSTWO_AIR_OP_ADD: case TSTWO_AIR_OP_SUB: case TSTWO_AIR_OP_MUL:
+                if (!reg_ok(x) || !reg_ok(w1)) return bad("air program: register out of range or read before written");
+                break;
+            case TSTWO_AIR_OP_SQR: case TSTWO_AIR_OP_NEG:
+                if (!reg_ok(x)) return bad("air program: register out of range or read before written");
+                break;
+            case TSTWO_AIR_OP_ACC:
+                if (!reg_ok(x)) return bad("air program: register out of range or read before written");
+                n_acc++;
+                continue;                   // writes no register
+            default:
+                return bad("air program: bad opcode");
+        }
+        if (dst >= TSTWO_AIR_PROGRAM_MAX_REGS) return bad("air program: register out of range or read before written");
+        written[dst] = true;
+        if (dst + 1 > n_regs) n_regs = dst + 1;
+    }
+    if (n_acc != n_constraints) return bad("air program: the number of ACC instructions differs from n_constraints");
+    // upload: program words, then coefficient words (at most 16 KiB: one slot of the ring, no host synchronisation)
+    static_assert((2 * TSTWO_AIR_PROGRAM_MAX_INSTR + 4 * TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS) * 4 <= kUpSlotBytes, "program upload exceeds one ring slot");
+    u32 staged[2 * TSTWO_AIR_PROGRAM_MAX_INSTR + 4 * TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS];
+    const size_t prog_words = 2 * program_len, words = prog_words + 4 * n_constraints;
+    ProgArgs a = {};
+    if (int rc = take_coeffs_and_denoms(coeffs, n_constraints, staged + prog_words, denom_inv, log_expand, a)) return rc;
+    std::copy(program, program + prog_words, staged);
+    if (int rc = ensure_scratch(words * sizeof(u32))) return rc;
+    if (int rc = small_h2d(ctx().scratch, staged, words * sizeof(u32))) return rc;
+    ColPtrs cp;
+    if (int rc = fill_col_table(cp, cols, n_cols, 0)) return rc;
+    for (int j = 0; j < 4; j++) a.acc.p[j] = accum[j];
+    a.prog = ctx().scratch;
+    a.n_instr = (u32)program_len;
+    a.trace_log = trace_log_size;
+    a.eval_log = trace_log_size + log_expand;
+    a.log_expand = log_expand;
+    a.n_rows = 1u << a.eval_log;
+    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, accum);
+    const int W = vec ? 4 : 1;
+    const size_t lds = (size_t)(n_regs ? n_regs : 1) * kWave * W * sizeof(u32);
+    const size_t work = a.n_rows / W;
+    unsigned grid = ceil_div(work, kWave);
+    const unsigned cap = (unsigned)ctx().n_cus * 32;
+    if (grid > cap) grid = cap;
+    if (vec) hipLaunchKernelGGL(k_air_program<4>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, a);
+    else hipLaunchKernelGGL(k_air_program<1>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, a);
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
 }
 
 }  // extern "C"

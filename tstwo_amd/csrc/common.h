@@ -233,5 +233,6 @@ inline bool table_has_null(T *const *t, size_t n) {
 }
 #define TSTWO_REQUIRE_PTRS(...) do { if (::tstwo::has_null({__VA_ARGS__})) return set_error(TSTWO_ERR_BAD_ARG, "null device pointer"); } while (0)
 #define TSTWO_REQUIRE_TABLE(t, n) do { if (::tstwo::table_has_null((t), (n))) return set_error(TSTWO_ERR_BAD_ARG, "null device pointer in table"); } while (0)
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace tstwo

@@ -28,7 +28,6 @@ unsigned grid_for(size_t work, unsigned cap_per_cu) {
     if (b > cap) b = cap;
     return b ? b : 1;
 }
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 template <class T>
 bool all_aligned16(const T &s) {
     for (int k = 0; k < 4; k++) if (!aligned16(s.p[k])) return false;

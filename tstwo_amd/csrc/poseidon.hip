@@ -150,8 +150,6 @@ __global__ void __launch_bounds__(kThreads) k_p252_grind(FeltArg d, u32 pow_bits
     if (felt::trailing_zeros(h) >= pow_bits) atomicMin(best, nonce);
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 int fill_cols(ColPtrs &cp, const u32 *const *cols, size_t n_cols) {
     if (n_cols == 0) {
         for (int k = 0; k < kMaxColsPerLaunch; k++) cp.p[k] = nullptr;
