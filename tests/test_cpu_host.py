@@ -592,3 +592,14 @@ def test_libraries_read_only_the_kept_switches():
                 assert f in ("context.hip", "comm.hip"), (f, line)
                 outside += 1
     assert outside <= 8, outside
+    # the Python package likewise: no module names a TSTWO_* variable (as a string of its own) except the loader's
+    import ast
+    pkg = os.path.join(ROOT, "tstwo_amd")
+    for dirpath, _, files in os.walk(pkg):
+        for f in sorted(files):
+            if f.endswith(".py"):
+                path = os.path.join(dirpath, f)
+                tree = ast.parse(open(path).read(), path)
+                read = {n.value for n in ast.walk(tree) if isinstance(n, ast.Constant) and isinstance(n.value, str)
+                        and re.fullmatch(r"TSTWO_[A-Z0-9_]+", n.value)}
+                assert read <= {"TSTWO_HIP_LIB"}, (os.path.relpath(path, ROOT), sorted(read))

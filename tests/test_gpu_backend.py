@@ -878,8 +878,8 @@ def test_line_interpolate_capi_errors():
         L.call("tstwo_line_interpolate", cols.ptrs(), 4, L.vp(0), tw.log_size, o4)
 
 
-def test_fri_commit_device_last_layer_equals_host_last_layer(monkeypatch):
-    """The last layer interpolated on the device (one read-back with the channel state) and on the host (TSTWO_FRI_HOST_LAST_LAYER)
+def test_fri_commit_device_last_layer_equals_host_last_layer():
+    """The last layer interpolated on the device (one read-back with the channel state) and on the host (host_last_layer)
     give the same last-layer polynomial and channel."""
     LOGD, BLOW = 9, 2
     domain = T.CanonicCoset(LOGD + BLOW).circleDomain()
@@ -888,18 +888,14 @@ def test_fri_commit_device_last_layer_equals_host_last_layer(monkeypatch):
     evs = T.evaluate_polynomials(polys, domain, tw)
     col = T.SecureEvaluation(domain, T.SecureColumnByCoords([e.values for e in evs]))
     results = []
-    for env in (None, "TSTWO_FRI_HOST_LAST_LAYER"):
+    for host in (False, True):
         for bound in (0, 3, 5):
-            if env:
-                monkeypatch.setenv(env, "1")
             ch = T.Blake2sChannel()
-            fp = T.FriProver.commit(ch, T.FriConfig(bound, BLOW, 10), [col], tw)
-            if env:
-                monkeypatch.delenv(env)
-            results.append((env, bound, [c.tup() for c in fp.last_layer_poly.coeffs], ch.digest_bytes() if hasattr(ch, "digest_bytes") else ch._digest))
-    base = {b: r for e, b, *r in results if e is None}
-    for e, b, *r in results:
-        assert r == base[b], (e, b)
+            fp = T.FriProver.commit(ch, T.FriConfig(bound, BLOW, 10), [col], tw, host_last_layer=host)
+            results.append((host, bound, [c.tup() for c in fp.last_layer_poly.coeffs], ch.digest_bytes() if hasattr(ch, "digest_bytes") else ch._digest))
+    base = {b: r for h, b, *r in results if not h}
+    for h, b, *r in results:
+        assert r == base[b], (h, b)
 
 
 # ---------------------------------------------------------------- poly/circle/secure_poly.ts, poly.ts:56-73, poly/utils.ts:78-100
@@ -1370,7 +1366,7 @@ def _fri_commit_digest(prover, ch):
 
 
 _FRI_BIG_CASES = {"single19": ([17], 2, (3, 2, 12)), "mixed19": ([17, 15, 12], 2, (4, 2, 10)), "single18b1": ([17], 1, (2, 1, 8))}
-def test_fri_commit_layers_big_layers_match_host_loop_and_verify(monkeypatch):
+def test_fri_commit_layers_big_layers_match_host_loop_and_verify():
     """The prover-critical branches of tstwo_fri_commit_layers above 2^16 rows — fold fused into k_merkle_leaf4<true> through
     commit_layer (grid-strided, deferred digest stores), k_fold_circle2 with a capped grid, commit_upper_levels starting with
     1024-lane workgroups, k_channel_mix_draw when the hook is left set — ran only in timing tools.  Circle log 18-19, one column
@@ -1382,9 +1378,7 @@ def test_fri_commit_layers_big_layers_match_host_loop_and_verify(monkeypatch):
         tw = _secure_low_degree_eval(log_degs[0], blow, 8300 + log_degs[0])[1]
         ch_a, ch_b = T.Blake2sChannel(), T.Blake2sChannel()
         a = T.FriProver.commit(ch_a, cfg, cols, tw)
-        monkeypatch.setenv("TSTWO_FRI_COMMIT_HOST_LOOP", "1")
-        b = T.FriProver.commit(ch_b, cfg, cols, tw)
-        monkeypatch.delenv("TSTWO_FRI_COMMIT_HOST_LOOP")
+        b = T.FriProver.commit(ch_b, cfg, cols, tw, per_layer_calls=True)
         assert len(a.inner_layers) == len(b.inner_layers) == (log_degs[0] + blow - 1) - (cfgt[0] + blow)
         assert a.first_layer.merkle_tree.root() == b.first_layer.merkle_tree.root()
         for la, lb in zip(a.inner_layers, b.inner_layers):
@@ -1398,7 +1392,7 @@ def test_fri_commit_layers_big_layers_match_host_loop_and_verify(monkeypatch):
         _fri_verify(cfg, proof, log_degs, _query_evals(cols, positions), positions)
 
 
-def test_fri_commit_layers_capi_matches_host_loop_and_reports_errors(monkeypatch):
+def test_fri_commit_layers_capi_matches_host_loop_and_reports_errors():
     """tstwo_fri_commit_layers (the whole commit loop in one call) against the per-layer calls of round 2 (same device
     transcript): identical trees, evaluations, last-layer polynomial and channel state, for one and for mixed-size columns; bad
     arguments come back as errors and leak nothing."""
@@ -1408,9 +1402,7 @@ def test_fri_commit_layers_capi_matches_host_loop_and_reports_errors(monkeypatch
         tw = _secure_low_degree_eval(log_degs[0], 2, 8100 + log_degs[0])[1]
         ch_a, ch_b = T.Blake2sChannel(), T.Blake2sChannel()
         a = T.FriProver.commit(ch_a, cfg, cols, tw)
-        monkeypatch.setenv("TSTWO_FRI_COMMIT_HOST_LOOP", "1")
-        b = T.FriProver.commit(ch_b, cfg, cols, tw)
-        monkeypatch.delenv("TSTWO_FRI_COMMIT_HOST_LOOP")
+        b = T.FriProver.commit(ch_b, cfg, cols, tw, per_layer_calls=True)
         assert ch_a.digest() == ch_b.digest()
         assert a.first_layer.merkle_tree.root() == b.first_layer.merkle_tree.root()
         assert len(a.inner_layers) == len(b.inner_layers) > 0

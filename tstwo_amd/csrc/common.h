@@ -203,12 +203,12 @@ __device__ __forceinline__ u32 *colp_u(const ColPtrs &c, u32 i) {
 }
 constexpr int kSecondTableOff = (int)sizeof(ColPtrs);     // kernel signature (ColPtrs cols, <ColPtrs | NoSrc> src, ...)
 #endif
-// merkle.hip: tstwo_merkle_commit + the channel's mix_root / draw_felt on its root, as one launch sequence without a separate
-// channel launch where the tree's last launch can carry it
-int merkle_commit_then_channel(const u32 *const *cols, const u32 *log_sizes, size_t n_cols, uint8_t *layers, u32 *chan, u32 *felt);
-// merkle.hip: fold_line fused into the next layer's leaf hashing + tree + channel step
-int merkle_commit4_folded(const u32 *const prev[4], u32 log_new, const u32 *inv_x, const u32 *alpha_dev, u32 *const new_cols[4],
-                          uint8_t *layers, u32 *chan, u32 *felt);
+// merkle.hip: tstwo_merkle_commit + the channel's mix_root / draw_felt on its root (felt: the drawn QM31), as one launch sequence
+// without a separate channel launch where the tree's last launch can carry it.  fold_in (null: no fold): `cols` are 4 columns of
+// 2^log rows (1 <= log <= 30) that the tree's leaf launch first writes as fold_line of the 4 columns fold_in (x^-1 at inv_x, the
+// alpha at alpha_dev) — bit-identical to tstwo_fri_fold_line_dev before the commit.
+int merkle_commit_then_channel(const u32 *const *cols, const u32 *log_sizes, size_t n_cols, uint8_t *layers, u32 *chan, u32 *felt,
+                               const u32 *const *fold_in, const u32 *inv_x, const u32 *alpha_dev);
 // merkle.hip: the FRI commit's last layers (2^log0 <= 2^9 rows and below) in one single-workgroup launch
 int launch_fri_tail(u32 *const (*eval)[4], uint8_t *const *trees, u32 n_layers, u32 log0, const u32 *itw, u32 tw_log, u32 *chan, u32 *alphas,
                     const u32 *const *pre, const u32 *pre_alpha);

@@ -347,15 +347,18 @@ static void launch_fold_line(const CSoa4 &i4, const Soa4 &o4, size_t n_out, cons
     // (a two-rows-per-lane form with 16-byte loads, as in k_fold_circle2, measured the same 6.2-6.4 TB/s: not kept)
     hipLaunchKernelGGL(k_fold_line, dim3(capped_blocks(n_out, 256)), dim3(256), 0, ctx().stream, i4, o4, n_out, inv_x, alpha, alpha_dev);
 }
-static void launch_fold_circle(bool from_tree, const Soa4 &d4, const CSoa4 &s4, size_t n_out, const u32 *twp, qm31 a, qm31 a2, const qm31 *alpha_dev) {
+// accum = false (dst written, not updated: the first fold of tstwo_fri_commit_layers) exists with tree twiddles only
+static void launch_fold_circle(bool from_tree, bool accum, const Soa4 &d4, const CSoa4 &s4, size_t n_out, const u32 *twp, qm31 a, qm31 a2,
+                               const qm31 *alpha_dev) {
     bool two = from_tree && n_out >= 4;
     for (int k = 0; k < 4; k++) two = two && (((uintptr_t)s4.p[k]) & 15) == 0 && (((uintptr_t)d4.p[k]) & 7) == 0;
-    if (two)
-        hipLaunchKernelGGL(k_fold_circle2<true>, dim3(capped_blocks(n_out / 2, 256)), dim3(256), 0, ctx().stream, d4, s4, n_out, twp, a, a2, alpha_dev);
-    else if (from_tree)
-        hipLaunchKernelGGL(k_fold_circle<true>, dim3(capped_blocks(n_out, 256)), dim3(256), 0, ctx().stream, d4, s4, n_out, twp, a, a2, alpha_dev);
-    else
-        hipLaunchKernelGGL(k_fold_circle<false>, dim3(capped_blocks(n_out, 256)), dim3(256), 0, ctx().stream, d4, s4, n_out, twp, a, a2, alpha_dev);
+    const dim3 g2(capped_blocks(n_out / 2, 256)), g1(capped_blocks(n_out, 256));
+    hipStream_t st = ctx().stream;
+    if (two && accum) hipLaunchKernelGGL(k_fold_circle2<true>, g2, dim3(256), 0, st, d4, s4, n_out, twp, a, a2, alpha_dev);
+    else if (from_tree && accum) hipLaunchKernelGGL(k_fold_circle<true>, g1, dim3(256), 0, st, d4, s4, n_out, twp, a, a2, alpha_dev);
+    else if (!from_tree) hipLaunchKernelGGL(k_fold_circle<false>, g1, dim3(256), 0, st, d4, s4, n_out, twp, a, a2, alpha_dev);
+    else if (two) hipLaunchKernelGGL(k_fold_circle2<false>, g2, dim3(256), 0, st, d4, s4, n_out, twp, a, a2, alpha_dev);
+    else hipLaunchKernelGGL((k_fold_circle<true, false>), g1, dim3(256), 0, st, d4, s4, n_out, twp, a, a2, alpha_dev);
 }
 
 }  // namespace
@@ -408,7 +411,7 @@ static int fold_circle_common(bool from_tree, u32 *const dst[4], size_t dst_len,
     host::Q a2 = host::qmul(a, a);
     Soa4 d4 = {{dst[0], dst[1], dst[2], dst[3]}};
     CSoa4 s4 = {{src[0], src[1], src[2], src[3]}};
-    launch_fold_circle(from_tree, d4, s4, dst_len, twp, to_q(a), to_q(a2), nullptr);
+    launch_fold_circle(from_tree, true, d4, s4, dst_len, twp, to_q(a), to_q(a2), nullptr);
     TSTWO_LAUNCH_CHECK();
     return TSTWO_OK;
 }
@@ -458,7 +461,7 @@ int tstwo_fri_fold_circle_into_line_dev(u32 *const dst[4], size_t dst_len, const
     const u32 *seg1 = itw + ((size_t)1 << tw_log) - ((size_t)1 << (log_n - 1));
     Soa4 d4 = {{dst[0], dst[1], dst[2], dst[3]}};
     CSoa4 s4 = {{src[0], src[1], src[2], src[3]}};
-    launch_fold_circle(true, d4, s4, dst_len, seg1, qm31{0, 0, 0, 0}, qm31{0, 0, 0, 0}, (const qm31 *)alpha_dev);
+    launch_fold_circle(true, true, d4, s4, dst_len, seg1, qm31{0, 0, 0, 0}, qm31{0, 0, 0, 0}, (const qm31 *)alpha_dev);
     TSTWO_LAUNCH_CHECK();
     return TSTWO_OK;
 }
@@ -505,7 +508,7 @@ int tstwo_fri_fold_circle_into_line_rows(u32 *const dst[4], const u32 *const src
     host::Q a2 = host::qmul(a, a);
     Soa4 d4 = {{dst[0], dst[1], dst[2], dst[3]}};
     CSoa4 s4 = {{src[0], src[1], src[2], src[3]}};
-    launch_fold_circle(true, d4, s4, n_rows, seg1, to_q(a), to_q(a2), nullptr);
+    launch_fold_circle(true, true, d4, s4, n_rows, seg1, to_q(a), to_q(a2), nullptr);
     TSTWO_LAUNCH_CHECK();
     return TSTWO_OK;
 }
@@ -548,7 +551,8 @@ int tstwo_fri_commit_layers(const u32 *const *circle_cols, const u32 *col_logs, 
         for (size_t i = 0; i < n_columns; i++) for (int k = 0; k < 4; k++) logs[4 * i + k] = col_logs[i];
         void *t = nullptr;
         if ((rc = alloc(&t, tstwo_merkle_layers_bytes(col_logs[0])))) return fail(rc);
-        if ((rc = merkle_commit_then_channel(circle_cols, logs.data(), 4 * n_columns, (uint8_t *)t, chan, alphas))) return fail(rc);
+        if ((rc = merkle_commit_then_channel(circle_cols, logs.data(), 4 * n_columns, (uint8_t *)t, chan, alphas, nullptr, nullptr, nullptr)))
+            return fail(rc);
         *first_tree = (uint8_t *)t;
     }
     u32 *alpha = alphas;
@@ -562,14 +566,7 @@ int tstwo_fri_commit_layers(const u32 *const *circle_cols, const u32 *col_logs, 
         const u32 *seg1 = itw + ((size_t)1 << tw_log) - ((size_t)1 << (col_logs[0] - 1));
         Soa4 d4 = {{cur[0], cur[1], cur[2], cur[3]}};
         CSoa4 s4 = {{circle_cols[0], circle_cols[1], circle_cols[2], circle_cols[3]}};
-        bool two = cur_log >= 2;
-        for (int k = 0; k < 4; k++) two = two && (((uintptr_t)s4.p[k]) & 15) == 0 && (((uintptr_t)d4.p[k]) & 7) == 0;
-        if (two)
-            hipLaunchKernelGGL(k_fold_circle2<false>, dim3(capped_blocks((size_t)1 << (cur_log - 1), 256)), dim3(256), 0, ctx().stream, d4, s4,
-                               (size_t)1 << cur_log, seg1, qm31{0, 0, 0, 0}, qm31{0, 0, 0, 0}, (const qm31 *)alpha);
-        else
-            hipLaunchKernelGGL((k_fold_circle<true, false>), dim3(capped_blocks((size_t)1 << cur_log, 256)), dim3(256), 0, ctx().stream, d4, s4,
-                               (size_t)1 << cur_log, seg1, qm31{0, 0, 0, 0}, qm31{0, 0, 0, 0}, (const qm31 *)alpha);
+        launch_fold_circle(true, false, d4, s4, (size_t)1 << cur_log, seg1, qm31{0, 0, 0, 0}, qm31{0, 0, 0, 0}, (const qm31 *)alpha);
         if (hipGetLastError() != hipSuccess) return fail(set_error(TSTWO_ERR_HIP, "fri commit: fold launch failed"));
         nxt = 1;
     }
@@ -621,10 +618,10 @@ int tstwo_fri_commit_layers(const u32 *const *circle_cols, const u32 *col_logs, 
             if ((rc = alloc(&t, tstwo_merkle_layers_bytes(cur_log)))) return fail(rc);
             o.layers = (uint8_t *)t;
             const u32 lg4[4] = {cur_log, cur_log, cur_log, cur_log};
-            if ((rc = merkle_commit_then_channel(cur, lg4, 4, o.layers, chan, alpha))) return fail(rc);      // FriInnerLayerProver::new + mix / draw
+            if ((rc = merkle_commit_then_channel(cur, lg4, 4, o.layers, chan, alpha, nullptr, nullptr, nullptr))) return fail(rc);      // FriInnerLayerProver::new + mix / draw
         }
         // fold this layer.  When the folded evaluation is committed as it stands (no circle column joins it, the tail does not take
-        // it), the fold runs inside the leaf launch of ITS tree: the folded row is that tree's leaf message (merkle_commit4_folded)
+        // it), the fold runs inside the leaf launch of ITS tree: the folded row is that tree's leaf message (merkle_commit_then_channel's fold)
         const u32 next_log = cur_log - 1;
         u32 *folded[4];
         if ((rc = alloc_eval(folded, next_log))) return fail(rc);
@@ -636,7 +633,8 @@ int tstwo_fri_commit_layers(const u32 *const *circle_cols, const u32 *col_logs, 
             void *t = nullptr;
             if ((rc = alloc(&t, tstwo_merkle_layers_bytes(next_log)))) return fail(rc);
             const u32 *seg = itw + ((size_t)1 << tw_log) - ((size_t)1 << cur_log);
-            if ((rc = merkle_commit4_folded(cur, next_log, seg, alpha, folded, (uint8_t *)t, chan, alphas + 4 * (n + 2)))) return fail(rc);
+            const u32 lg4[4] = {next_log, next_log, next_log, next_log};
+            if ((rc = merkle_commit_then_channel(folded, lg4, 4, (uint8_t *)t, chan, alphas + 4 * (n + 2), cur, seg, alpha))) return fail(rc);
             cur_tree = (uint8_t *)t;
             fused = true;
         }

@@ -670,29 +670,19 @@ __global__ void __launch_bounds__(WG) k_merkle_leaf4_upq(u32 *__restrict__ c0, u
 }
 
 // Column-free levels log_child-1 .. log_stop of the tree, a few fused launches instead of one launch per level.
-// Set by the FRI commit loop around a tstwo_merkle_commit call: the single-workgroup launch that produces the root takes the
-// channel step with it and clears the hook; a hook still set afterwards means the tree went another way (the caller then
-// launches k_channel_mix_draw itself).
-// (thread_local: the hooks belong to the call chain that set them — a second host thread committing a tree of its own while
-// tstwo_fri_commit_layers is between "set" and "consumed" must not pick them up.)
-thread_local ChanHook g_chan_hook = {nullptr, nullptr};
-// Likewise for a fold: set by merkle_commit4_folded around a tstwo_merkle_commit of the 4 NEW coordinate columns; the leaf launch
-// of that tree folds the previous layer into them on the way (FoldSpec) and clears it.
-thread_local FoldSpec g_fold = {};
-thread_local bool g_fold_set = false;
+// hook (null, or hook->chan null: none): a channel step on the root of a single tree.  When log_stop is 0 the last launch, one
+// workgroup, produces the root and takes the step with it; *hook is then cleared.
 // Layers below 2^kUpLog nodes are latency-bound: tstwo_merkle_commit builds them with the fused multi-level launches above
 // (k_merkle_upq) instead of one launch per layer.
 constexpr int kUpLog = 16;
-int commit_upper_levels(uint8_t *layers, u32 log_child, u32 log_stop);
-int commit_upper_levels(TreeSet ts, unsigned n_trees, u32 log_child, u32 log_stop) {
+int commit_upper_levels(TreeSet ts, unsigned n_trees, u32 log_child, u32 log_stop, ChanHook *hook) {
     Context &c = ctx();
     const ChanHook none = {nullptr, nullptr};
-    auto take_hook = [&](bool reaches_root) {
-        if (!reaches_root || n_trees != 1 || !g_chan_hook.chan) return none;
-        const ChanHook h = g_chan_hook;
-        g_chan_hook = none;
-        return h;
-    };
+    ChanHook root_hook = none;               // passed to the launches that finish the tree (the last one)
+    if (hook && hook->chan && n_trees == 1 && log_stop == 0 && log_child > log_stop) {
+        root_hook = *hook;
+        *hook = none;
+    }
     while (log_child > log_stop) {
         const u32 remaining = log_child - log_stop;
         const u32 parents_log = log_child - 1;
@@ -704,10 +694,10 @@ int commit_upper_levels(TreeSet ts, unsigned n_trees, u32 log_child, u32 log_sto
             hipLaunchKernelGGL(k_merkle_upq<1024>, dim3(1u << (parents_log - 8), n_trees), dim3(1024), 0, c.stream, ts, log_child, 9u, none);
             log_child -= 9;
         } else if (parents_log <= 6) {            // <= 64 parents: one 64-quad workgroup finishes the tree
-            hipLaunchKernelGGL(k_merkle_upq<256>, dim3(1, n_trees), dim3(256), 0, c.stream, ts, log_child, remaining, take_hook(log_stop == 0));
+            hipLaunchKernelGGL(k_merkle_upq<256>, dim3(1, n_trees), dim3(256), 0, c.stream, ts, log_child, remaining, root_hook);
             log_child -= remaining;
         } else if (parents_log <= 8) {            // <= 256 parents: ONE workgroup of 256 quads finishes the tree (up to 9 levels)
-            hipLaunchKernelGGL(k_merkle_upq<1024>, dim3(1, n_trees), dim3(1024), 0, c.stream, ts, log_child, remaining, take_hook(log_stop == 0));
+            hipLaunchKernelGGL(k_merkle_upq<1024>, dim3(1, n_trees), dim3(1024), 0, c.stream, ts, log_child, remaining, root_hook);
             log_child -= remaining;
         } else {                                  // >= 512 parents: 64 quads per workgroup, 64 -> 1 = up to 7 levels each
             u32 levels = remaining < 7 ? remaining : 7;
@@ -718,10 +708,10 @@ int commit_upper_levels(TreeSet ts, unsigned n_trees, u32 log_child, u32 log_sto
     TSTWO_LAUNCH_CHECK();
     return TSTWO_OK;
 }
-int commit_upper_levels(uint8_t *layers, u32 log_child, u32 log_stop) {
+int commit_upper_levels(uint8_t *layers, u32 log_child, u32 log_stop, ChanHook *hook) {
     TreeSet one = {};
     one.t[0] = (uint4 *)layers;
-    return commit_upper_levels(one, 1, log_child, log_stop);
+    return commit_upper_levels(one, 1, log_child, log_stop, hook);
 }
 
 __global__ void __launch_bounds__(64) k_channel_mix_draw(u32 *__restrict__ chan, const u32 *__restrict__ root, u32 *__restrict__ felt,
@@ -873,11 +863,13 @@ __global__ void __launch_bounds__(256) k_grind(GrindDigest d, u32 pow_bits, unsi
     if (tz >= pow_bits) atomicMin(best, nonce);
 }
 
-int commit_layer(u32 log_size, const uint8_t *prev, const u32 *const *cols, size_t n_cols, uint8_t *out) {
+// fold (null: none): the 4 columns of a leaf layer are first written as the fold it describes, inside the leaf launch.
+int commit_layer(u32 log_size, const uint8_t *prev, const u32 *const *cols, size_t n_cols, uint8_t *out, const FoldSpec *fold) {
     Context &c = ctx();
     if (log_size > 31) return set_error(TSTWO_ERR_BAD_ARG, "merkle: log size out of range");
     if (!out) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null output layer");
     if ((((uintptr_t)out) & 15) || (((uintptr_t)prev) & 15)) return set_error(TSTWO_ERR_BAD_ARG, "merkle: layers must be 16-byte aligned");
+    if (fold && (prev || log_size > 30 || n_cols != 4)) return set_error(TSTWO_ERR_HIP, "fri commit: the fold was not carried by the leaf launch");
     const size_t n_nodes = (size_t)1 << log_size;
     const u32 child_words = prev ? 16u : 0u;
     const u32 W = child_words + (u32)n_cols;
@@ -901,12 +893,10 @@ int commit_layer(u32 log_size, const uint8_t *prev, const u32 *const *cols, size
     }
     if (!prev && log_size <= 30 && n_cols == 4) {
         u32 *w0 = const_cast<u32 *>(cols[0]), *w1 = const_cast<u32 *>(cols[1]), *w2 = const_cast<u32 *>(cols[2]), *w3 = const_cast<u32 *>(cols[3]);
-        if (g_fold_set) {
-            hipLaunchKernelGGL(k_merkle_leaf4<true>, dim3(blocks), dim3(256), 0, c.stream, w0, w1, w2, w3, (uint4 *)out, n_nodes, g_fold);
-            g_fold_set = false;
-        } else {
+        if (fold)
+            hipLaunchKernelGGL(k_merkle_leaf4<true>, dim3(blocks), dim3(256), 0, c.stream, w0, w1, w2, w3, (uint4 *)out, n_nodes, *fold);
+        else
             hipLaunchKernelGGL(k_merkle_leaf4<false>, dim3(blocks), dim3(256), 0, c.stream, w0, w1, w2, w3, (uint4 *)out, n_nodes, FoldSpec{});
-        }
         TSTWO_LAUNCH_CHECK();
         return TSTWO_OK;
     }
@@ -951,32 +941,112 @@ int commit_layer(u32 log_size, const uint8_t *prev, const u32 *const *cols, size
     return TSTWO_OK;
 }
 
+// tstwo_merkle_commit, with the two steps of a FRI commit layer that can ride on the tree's launches.  fold (null: none): the
+// tree's 4 columns are first written as that fold, inside the leaf launch; a launch sequence that cannot carry it is an error.
+// hook (null: none): the channel step on the root, taken by the single-workgroup launch that produces the root and then
+// cleared; a hook still set on return means no launch could take it.
+int commit_tree(const u32 *const *cols, const u32 *log_sizes, size_t n_cols, uint8_t *layers, uint8_t root[32], const FoldSpec *fold,
+                ChanHook *hook) {
+    TSTWO_REQUIRE_READY();
+    if (!layers) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null layers buffer");
+    if (n_cols && !log_sizes) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null log size table");
+    TSTWO_REQUIRE_TABLE(cols, n_cols);
+    u32 max_log = 0;
+    for (size_t i = 0; i < n_cols; i++) {
+        if (log_sizes[i] > 31) return set_error(TSTWO_ERR_BAD_ARG, "merkle: log size out of range");
+        if (log_sizes[i] > max_log) max_log = log_sizes[i];
+    }
+    // a tree of exactly 4 equally long columns with at most 2^kUpLog rows (every FRI layer but the first few): leaves and the
+    // first 7 (or all, below 2^10 rows) levels in one launch
+    if (n_cols == 4 && max_log >= 1 && (int)max_log <= kUpLog && log_sizes[0] == max_log && log_sizes[1] == max_log && log_sizes[2] == max_log &&
+        log_sizes[3] == max_log) {
+        Context &c = ctx();
+        u32 log_child = max_log;
+        u32 *w0 = const_cast<u32 *>(cols[0]), *w1 = const_cast<u32 *>(cols[1]), *w2 = const_cast<u32 *>(cols[2]), *w3 = const_cast<u32 *>(cols[3]);
+        const FoldSpec fs = fold ? *fold : FoldSpec{};
+        if (max_log <= 9) {
+            const ChanHook hk = hook ? *hook : ChanHook{nullptr, nullptr};
+            if (fold) hipLaunchKernelGGL((k_merkle_leaf4_upq<1024, true>), dim3(1), dim3(1024), 0, c.stream, w0, w1, w2, w3, (uint4 *)layers, max_log, max_log, hk, fs);
+            else hipLaunchKernelGGL((k_merkle_leaf4_upq<1024, false>), dim3(1), dim3(1024), 0, c.stream, w0, w1, w2, w3, (uint4 *)layers, max_log, max_log, hk, fs);
+            if (hook) *hook = {nullptr, nullptr};
+            log_child = 0;
+        } else {
+            if (fold) hipLaunchKernelGGL((k_merkle_leaf4_upq<256, true>), dim3(1u << (max_log - 7)), dim3(256), 0, c.stream, w0, w1, w2, w3, (uint4 *)layers, max_log, 7u, ChanHook{nullptr, nullptr}, fs);
+            else hipLaunchKernelGGL((k_merkle_leaf4_upq<256, false>), dim3(1u << (max_log - 7)), dim3(256), 0, c.stream, w0, w1, w2, w3, (uint4 *)layers, max_log, 7u, ChanHook{nullptr, nullptr}, fs);
+            log_child = max_log - 7;
+        }
+        TSTWO_LAUNCH_CHECK();
+        int rc = log_child ? commit_upper_levels(layers, log_child, 0, hook) : TSTWO_OK;
+        if (rc) return rc;
+        if (root) return small_d2h(root, layers, 32);
+        return TSTWO_OK;
+    }
+    const u32 **lc = n_cols ? new const u32 *[n_cols] : nullptr;
+    const uint8_t *prev = nullptr;
+    int rc = TSTWO_OK;
+    int lg = (int)max_log;
+    while (lg >= 0 && rc == TSTWO_OK) {   // vcs/prover.ts:24-27
+        size_t k = 0;
+        for (size_t i = 0; i < n_cols; i++)
+            if (log_sizes[i] == (u32)lg) lc[k++] = cols[i];
+        uint8_t *dst = layers + 32 * (((size_t)1 << lg) - 1);
+        // layer k starts at 32*(2^k-1): 16-byte aligned for every k >= 0 when `layers` is
+        if (k == 0 && prev != nullptr && lg < kUpLog) {
+            // a run of column-free layers below lg+1: fuse them (stop above the next layer that has columns)
+            int stop = lg;
+            while (stop > 0) {
+                bool has = false;
+                for (size_t i = 0; i < n_cols; i++) has = has || log_sizes[i] == (u32)(stop - 1);
+                if (has) break;
+                stop--;
+            }
+            rc = commit_upper_levels(layers, (u32)lg + 1, (u32)stop, hook);
+            prev = layers + 32 * (((size_t)1 << stop) - 1);
+            lg = stop - 1;
+            continue;
+        }
+        if (k == 0 && prev != nullptr) {
+            // two column-free layers at or above 2^kUpLog nodes: one in-lane subtree launch for both (measured for 32 x 2^22:
+            // 0.308 ms, against 0.313 for one launch per layer and 0.326 / 0.332 for runs of 3 / 4 layers)
+            bool pair = lg - 1 >= kUpLog;
+            for (size_t i = 0; i < n_cols; i++) pair = pair && log_sizes[i] != (u32)(lg - 1);
+            if (pair) {
+                const size_t tops = (size_t)1 << (lg - 1);          // >= 2^kUpLog nodes: whole k_merkle_subtree2c workgroups
+                Context &c = ctx();
+                TreeSet one = {};
+                one.t[0] = (uint4 *)layers;
+                hipLaunchKernelGGL(k_merkle_subtree2c, dim3((unsigned)(tops / 256)), dim3(256), 0, c.stream, one, (u32)lg + 1);
+                if (hipGetLastError() != hipSuccess) rc = set_error(TSTWO_ERR_HIP, "merkle: subtree kernel launch failed");
+                lg -= 2;
+                prev = layers + 32 * (((size_t)1 << (lg + 1)) - 1);
+                continue;
+            }
+        }
+        rc = commit_layer((u32)lg, prev, lc, k, dst, prev ? nullptr : fold);      // the leaf layer carries the fold
+        prev = dst;
+        lg--;
+    }
+    delete[] lc;
+    if (rc) return rc;
+    if (root) {
+        int rc2 = small_d2h(root, layers, 32);
+        if (rc2) return rc2;
+    }
+    return TSTWO_OK;
+}
 }  // namespace
 
 namespace tstwo {
 // fri.hip's commit loop: tstwo_merkle_commit(…) followed by mix_root + draw_felt on its root, the channel step riding on the tree's
 // last launch when that launch is a single workgroup (every FRI layer's tree), a k_channel_mix_draw launch otherwise.
-int merkle_commit_then_channel(const u32 *const *cols, const u32 *log_sizes, size_t n_cols, uint8_t *layers, u32 *chan, u32 *felt) {
-    g_chan_hook = {chan, felt};
-    int rc = tstwo_merkle_commit(cols, log_sizes, n_cols, layers, nullptr);
-    const bool pending = g_chan_hook.chan != nullptr;
-    g_chan_hook = {nullptr, nullptr};
+int merkle_commit_then_channel(const u32 *const *cols, const u32 *log_sizes, size_t n_cols, uint8_t *layers, u32 *chan, u32 *felt,
+                               const u32 *const *fold_in, const u32 *inv_x, const u32 *alpha_dev) {
+    FoldSpec fs = {};
+    if (fold_in) fs = {{fold_in[0], fold_in[1], fold_in[2], fold_in[3]}, inv_x, alpha_dev};
+    ChanHook hook = {chan, felt};
+    int rc = commit_tree(cols, log_sizes, n_cols, layers, nullptr, fold_in ? &fs : nullptr, &hook);
     if (rc) return rc;
-    return pending ? tstwo_channel_mix_root_draw_felt(chan, layers, felt) : TSTWO_OK;
-}
-// fri.hip's commit loop: fold_line of a layer INTO the leaf hashing of the next layer's tree.  new_cols (2^log_new rows each,
-// 1 <= log_new <= 30) receive the folded evaluation; `layers` the tree over them; then mix_root + draw_felt as in
-// merkle_commit_then_channel.  Bit-identical to tstwo_fri_fold_line_dev + tstwo_merkle_commit + tstwo_channel_mix_root_draw_felt.
-int merkle_commit4_folded(const u32 *const prev[4], u32 log_new, const u32 *inv_x, const u32 *alpha_dev, u32 *const new_cols[4],
-                          uint8_t *layers, u32 *chan, u32 *felt) {
-    const u32 lg4[4] = {log_new, log_new, log_new, log_new};
-    g_fold = {{prev[0], prev[1], prev[2], prev[3]}, inv_x, alpha_dev};
-    g_fold_set = true;
-    int rc = merkle_commit_then_channel(new_cols, lg4, 4, layers, chan, felt);
-    const bool consumed = !g_fold_set;
-    g_fold_set = false;
-    if (rc) return rc;
-    return consumed ? TSTWO_OK : set_error(TSTWO_ERR_HIP, "fri commit: the fold was not carried by the leaf launch");
+    return hook.chan ? tstwo_channel_mix_root_draw_felt(chan, layers, felt) : TSTWO_OK;      // no launch of the tree took the step
 }
 // fri.hip's commit loop hands the layers from 2^log0 <= 2^9 rows down to the last one to k_fri_tail (see there).
 int launch_fri_tail(u32 *const (*eval)[4], uint8_t *const *trees, u32 n_layers, u32 log0, const u32 *itw, u32 tw_log, u32 *chan, u32 *alphas,
@@ -1311,97 +1381,11 @@ int tstwo_merkle_commit_layer(u32 log_size, const uint8_t *prev, const u32 *cons
     TSTWO_REQUIRE_READY();
     if (n_cols && !cols) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null column table");
     TSTWO_REQUIRE_TABLE(cols, n_cols);
-    return commit_layer(log_size, prev, cols, n_cols, out);
+    return commit_layer(log_size, prev, cols, n_cols, out, nullptr);
 }
 
 int tstwo_merkle_commit(const u32 *const *cols, const u32 *log_sizes, size_t n_cols, uint8_t *layers, uint8_t root[32]) {
-    TSTWO_REQUIRE_READY();
-    if (!layers) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null layers buffer");
-    if (n_cols && !log_sizes) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null log size table");
-    TSTWO_REQUIRE_TABLE(cols, n_cols);
-    u32 max_log = 0;
-    for (size_t i = 0; i < n_cols; i++) {
-        if (log_sizes[i] > 31) return set_error(TSTWO_ERR_BAD_ARG, "merkle: log size out of range");
-        if (log_sizes[i] > max_log) max_log = log_sizes[i];
-    }
-    // a tree of exactly 4 equally long columns with at most 2^kUpLog rows (every FRI layer but the first few): leaves and the
-    // first 7 (or all, below 2^10 rows) levels in one launch
-    if (n_cols == 4 && max_log >= 1 && (int)max_log <= kUpLog && log_sizes[0] == max_log && log_sizes[1] == max_log && log_sizes[2] == max_log &&
-        log_sizes[3] == max_log) {
-        Context &c = ctx();
-        u32 log_child = max_log;
-        u32 *w0 = const_cast<u32 *>(cols[0]), *w1 = const_cast<u32 *>(cols[1]), *w2 = const_cast<u32 *>(cols[2]), *w3 = const_cast<u32 *>(cols[3]);
-        const bool fold = g_fold_set;
-        const FoldSpec fs = fold ? g_fold : FoldSpec{};
-        g_fold_set = false;
-        if (max_log <= 9) {
-            if (fold) hipLaunchKernelGGL((k_merkle_leaf4_upq<1024, true>), dim3(1), dim3(1024), 0, c.stream, w0, w1, w2, w3, (uint4 *)layers, max_log, max_log, g_chan_hook, fs);
-            else hipLaunchKernelGGL((k_merkle_leaf4_upq<1024, false>), dim3(1), dim3(1024), 0, c.stream, w0, w1, w2, w3, (uint4 *)layers, max_log, max_log, g_chan_hook, fs);
-            g_chan_hook = {nullptr, nullptr};
-            log_child = 0;
-        } else {
-            if (fold) hipLaunchKernelGGL((k_merkle_leaf4_upq<256, true>), dim3(1u << (max_log - 7)), dim3(256), 0, c.stream, w0, w1, w2, w3, (uint4 *)layers, max_log, 7u, ChanHook{nullptr, nullptr}, fs);
-            else hipLaunchKernelGGL((k_merkle_leaf4_upq<256, false>), dim3(1u << (max_log - 7)), dim3(256), 0, c.stream, w0, w1, w2, w3, (uint4 *)layers, max_log, 7u, ChanHook{nullptr, nullptr}, fs);
-            log_child = max_log - 7;
-        }
-        TSTWO_LAUNCH_CHECK();
-        int rc = log_child ? commit_upper_levels(layers, log_child, 0) : TSTWO_OK;
-        if (rc) return rc;
-        if (root) return small_d2h(root, layers, 32);
-        return TSTWO_OK;
-    }
-    const u32 **lc = n_cols ? new const u32 *[n_cols] : nullptr;
-    const uint8_t *prev = nullptr;
-    int rc = TSTWO_OK;
-    int lg = (int)max_log;
-    while (lg >= 0 && rc == TSTWO_OK) {   // vcs/prover.ts:24-27
-        size_t k = 0;
-        for (size_t i = 0; i < n_cols; i++)
-            if (log_sizes[i] == (u32)lg) lc[k++] = cols[i];
-        uint8_t *dst = layers + 32 * (((size_t)1 << lg) - 1);
-        // layer k starts at 32*(2^k-1): 16-byte aligned for every k >= 0 when `layers` is
-        if (k == 0 && prev != nullptr && lg < kUpLog) {
-            // a run of column-free layers below lg+1: fuse them (stop above the next layer that has columns)
-            int stop = lg;
-            while (stop > 0) {
-                bool has = false;
-                for (size_t i = 0; i < n_cols; i++) has = has || log_sizes[i] == (u32)(stop - 1);
-                if (has) break;
-                stop--;
-            }
-            rc = commit_upper_levels(layers, (u32)lg + 1, (u32)stop);
-            prev = layers + 32 * (((size_t)1 << stop) - 1);
-            lg = stop - 1;
-            continue;
-        }
-        if (k == 0 && prev != nullptr) {
-            // two column-free layers at or above 2^kUpLog nodes: one in-lane subtree launch for both (measured for 32 x 2^22:
-            // 0.308 ms, against 0.313 for one launch per layer and 0.326 / 0.332 for runs of 3 / 4 layers)
-            bool pair = lg - 1 >= kUpLog;
-            for (size_t i = 0; i < n_cols; i++) pair = pair && log_sizes[i] != (u32)(lg - 1);
-            if (pair) {
-                const size_t tops = (size_t)1 << (lg - 1);          // >= 2^kUpLog nodes: whole k_merkle_subtree2c workgroups
-                Context &c = ctx();
-                TreeSet one = {};
-                one.t[0] = (uint4 *)layers;
-                hipLaunchKernelGGL(k_merkle_subtree2c, dim3((unsigned)(tops / 256)), dim3(256), 0, c.stream, one, (u32)lg + 1);
-                if (hipGetLastError() != hipSuccess) rc = set_error(TSTWO_ERR_HIP, "merkle: subtree kernel launch failed");
-                lg -= 2;
-                prev = layers + 32 * (((size_t)1 << (lg + 1)) - 1);
-                continue;
-            }
-        }
-        rc = commit_layer((u32)lg, prev, lc, k, dst);
-        prev = dst;
-        lg--;
-    }
-    delete[] lc;
-    if (rc) return rc;
-    if (root) {
-        int rc2 = small_d2h(root, layers, 32);
-        if (rc2) return rc2;
-    }
-    return TSTWO_OK;
+    return commit_tree(cols, log_sizes, n_cols, layers, root, nullptr, nullptr);
 }
 
 
@@ -1470,7 +1454,7 @@ int tstwo_merkle_commit_many(const tstwo_commit_request *reqs, size_t n_trees, u
             cur -= 1;
         }
         TSTWO_LAUNCH_CHECK();
-        int rc = commit_upper_levels(ts, (unsigned)n_trees, (u32)cur + 1, 0);
+        int rc = commit_upper_levels(ts, (unsigned)n_trees, (u32)cur + 1, 0, nullptr);
         if (rc) return rc;
     }
     if (roots) {

@@ -6,7 +6,6 @@ coordinate columns (device resident), the root is mixed into the channel, and th
 Layers never leave HBM between fold and commit; only 32-byte roots and the (tiny) last layer reach the host."""
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass, field
 
 from . import _lib as L
@@ -320,10 +319,14 @@ class FriProver:
         self.config, self.first_layer, self.inner_layers, self.last_layer_poly = config, first_layer, inner_layers, last_layer_coeffs
 
     @staticmethod
-    def commit(channel, config: FriConfig, columns, twiddles: TwiddleTree, device_channel: bool = True, merkle_channel=None) -> "FriProver":
+    def commit(channel, config: FriConfig, columns, twiddles: TwiddleTree, device_channel: bool = True, merkle_channel=None, *,
+               per_layer_calls: bool = False, host_last_layer: bool = False) -> "FriProver":
         """columns: SecureEvaluation list, canonic domains, strictly decreasing sizes (fri.ts:644-674).  merkle_channel: the
         Merkle channel of the layer trees (default Blake2sMerkleChannel; Poseidon252MerkleChannel keeps the transcript on the
-        host: the device channel and tstwo_fri_commit_layers are Blake2s only)."""
+        host: the device channel and tstwo_fri_commit_layers are Blake2s only).  With the device transcript, the references the
+        one-call commit is tested and timed against: per_layer_calls runs the layer loop through round 2's per-layer calls
+        (_commit_layers, what FriCommitPlan captures) instead of tstwo_fri_commit_layers; host_last_layer interpolates the last
+        layer on the host (numpy) instead of by tstwo_line_interpolate."""
         if not columns:
             raise ValueError("no columns")
         if not all(c.domain.isCanonic() for c in columns):
@@ -348,11 +351,12 @@ class FriProver:
             alphas = L.DeviceBuffer(16 * (columns[0].domain.logSize() + 2))
             # the whole layer loop is ONE library call (tstwo_fri_commit_layers); FriCommitPlan captures the per-layer calls of
             # _commit_layers instead (a capture cannot allocate)
-            if os.environ.get("TSTWO_FRI_COMMIT_HOST_LOOP"):            # A/B timing: round 2's loop, ~10 C-ABI calls per layer
+            if per_layer_calls:                                         # round 2's loop, ~10 C-ABI calls per layer
                 first_layer, inner, layer_eval = FriProver._commit_layers(config, columns, twiddles, _DeviceTranscript(dch, alphas))
             else:
                 first_layer, inner, layer_eval = FriProver._commit_layers_in_library(config, columns, twiddles, dch, alphas)
-            prefetched = FriProver._fetch_end_of_commit(dch, layer_eval, twiddles)
+            coeff_buf = None if host_last_layer else line_interpolate_device(layer_eval, twiddles)
+            prefetched = FriProver._fetch_end_of_commit(dch, layer_eval, twiddles, coeff_buf)
         else:
             first_layer, inner, layer_eval = FriProver._commit_layers(config, columns, twiddles, _HostTranscript(channel, prover))
             prefetched = None
@@ -364,11 +368,9 @@ class FriProver:
         """What the host needs to finish a device-transcript commit — the channel state and the last layer's polynomial — in ONE
         round trip (six separate read-backs were 0.17 ms of a 0.76 ms commit).  The interpolation itself
         (LineEvaluation.interpolate) runs on the device when the layer fits one workgroup (coeff_buf: already enqueued by the
-        caller); otherwise its inputs (coordinate columns, x^-1 slice of the tree) come back.  Updates the host channel; returns
-        what _commit_last_layer takes as `prefetched`."""
+        caller, line_interpolate_device); otherwise (coeff_buf None) its inputs (coordinate columns, x^-1 slice of the tree) come
+        back.  Updates the host channel; returns what _commit_last_layer takes as `prefetched`."""
         n_last = layer_eval.len()
-        if coeff_buf is None and not os.environ.get("TSTWO_FRI_HOST_LAST_LAYER"):
-            coeff_buf = line_interpolate_device(layer_eval, twiddles)
         pieces = [(dch.buf.ptr, 10)]
         uses_tree = _line_interpolate_uses_tree(layer_eval, twiddles)
         if coeff_buf is not None:
