@@ -533,6 +533,34 @@ int tstwo_air_eval_program(const uint32_t *const *cols, size_t n_cols, uint32_t 
                            const uint32_t *program, size_t program_len, const uint32_t *coeffs, size_t n_constraints,
                            const uint32_t *denom_inv, uint32_t *const accum[4]);
 
+/* ---------------------------------------------------------------- LogUp interaction trace
+ * Rust stwo constraint_framework/logup.rs (LogupTraceGenerator, LogupColGenerator); tstwo_amd/logup.py drives it.
+ * One fraction of an interaction column: numerator num[r] (a device column of M31 values) or, when num is NULL, num_const for
+ * every row; denominator sum_t coeffs[4t .. 4t + 4) * cols[t][r] + constant (QM31 coefficients and constant, M31 columns).
+ * Limits (TSTWO_ERR_BAD_ARG, text in tstwo_last_error): 1 .. TSTWO_LOGUP_MAX_FRACS fractions per column ("1 to 8 fractions per
+ * column"), 1 .. TSTWO_LOGUP_MAX_TERMS terms per denominator ("1 to 16 terms per fraction"), log_size <= TSTWO_LOGUP_MAX_LOG,
+ * every host word < 2^31 - 1 ("... out of range"), no null pointer.  Every column holds 2^log_size words. */
+typedef struct {
+    const uint32_t *num;
+    uint32_t num_const;
+    uint32_t n_terms;
+    const uint32_t *const *cols;
+    const uint32_t *coeffs;
+    uint32_t constant[4];
+} tstwo_logup_frac;
+#define TSTWO_LOGUP_MAX_FRACS 8
+#define TSTWO_LOGUP_MAX_TERMS 16
+#define TSTWO_LOGUP_MAX_LOG 28
+/* out[r] = (prev ? prev[r] : 0) + sum_b num_b[r] / den_b[r] for r < 2^log_size, one launch (out may be prev).  A zero denominator
+ * raises the sticky zero flag (tstwo_check_zero_flag then fails with "0 has no inverse").  The descriptors are uploaded through
+ * the small-upload ring: refused during graph capture.  Asynchronous. */
+int tstwo_logup_column(const tstwo_logup_frac *fracs, size_t n_fracs, const uint32_t *const prev[4], uint32_t log_size,
+                       uint32_t *const out[4]);
+/* The last interaction column, in place: claimed = sum_r col[r]; then, in coset order (mask offset -1 is the previous coset row),
+ * col[pos(k)] = sum_{k' <= k} (col[pos(k')] - claimed / 2^log_size), so the last coset row holds 0.  claimed_sum (host) receives
+ * the 4 words of claimed.  1 <= log_size <= 28.  Synchronous; refused during graph capture. */
+int tstwo_logup_finalize_last(uint32_t *const col[4], uint32_t log_size, uint32_t claimed_sum[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,9 +37,12 @@ from .poseidon import (DeviceFeltLayer, FieldElement252, HipPoseidon252MerkleOps
                        Poseidon252MerkleChannel, Poseidon252MerkleHasher, Poseidon252MerkleProver)
 from .air import (ColumnAccumulator, ComponentProvers, Components, DomainEvaluationAccumulator,  # noqa: F401
                   PointEvaluationAccumulator, Trace, TraceLocationAllocator, coset_vanishing, generate_wide_fib_trace)
-from .constraint_framework import (FrameworkComponent, MulAddComponent, MulAddEval, WideFibonacciComponent,  # noqa: F401
-                                   WideFibonacciEval)
-from .prover import ConstraintsNotSatisfied, InvalidStructure, OodsNotMatching, StarkProof, prove, verify  # noqa: F401
+from .constraint_framework import (FrameworkComponent, MulAddComponent, MulAddEval, PermutationEval,  # noqa: F401
+                                   RangeCheckTableEval, RangeCheckValuesEval, WideFibonacciComponent, WideFibonacciEval)
+from .logup import (INTERACTION_TRACE_IDX, LogupColGenerator, LogupTraceGenerator, LookupElements,  # noqa: F401
+                    RelationEntry)
+from .prover import (ConstraintsNotSatisfied, InvalidLogupSum, InvalidStructure, OodsNotMatching, StarkProof, prove,  # noqa: F401
+                     verify)
 
 __all__ = [n for n in dir() if not n.startswith("_")]
 from .semantics import get_semantics, set_semantics  # noqa: F401,E402

@@ -55,6 +55,12 @@ class FriLayerOut(C.Structure):
     _fields_ = [("log_size", C.c_uint32), ("cols", vp * 4), ("layers", vp)]
 
 
+class LogupFrac(C.Structure):
+    """tstwo_logup_frac (include/tstwo_hip.h)."""
+    _fields_ = [("num", vp), ("num_const", C.c_uint32), ("n_terms", C.c_uint32), ("cols", C.POINTER(vp)), ("coeffs", u32p),
+                ("constant", C.c_uint32 * 4)]
+
+
 _SIGS = {
     "tstwo_init": [C.c_int],
     "tstwo_shutdown": [],
@@ -162,6 +168,8 @@ _SIGS = {
     "tstwo_air_wide_fib_trace": [vp, vp, C.c_uint32, C.POINTER(vp), C.c_size_t],
     "tstwo_air_constraint_quotients": [C.c_uint32, C.POINTER(vp), C.c_size_t, C.c_uint32, C.c_uint32, u32p, C.c_size_t, u32p, P4],
     "tstwo_air_eval_program": [C.POINTER(vp), C.c_size_t, C.c_uint32, C.c_uint32, u32p, C.c_size_t, u32p, C.c_size_t, u32p, P4],
+    "tstwo_logup_column": [C.POINTER(LogupFrac), C.c_size_t, C.POINTER(vp), C.c_uint32, P4],
+    "tstwo_logup_finalize_last": [P4, C.c_uint32, u32p],
 }
 ALLOC_POOL, ALLOC_DIRECT, ALLOC_ASYNC, ALLOC_POISON = 0, 1, 2, 0x10
 # c_void_p arguments above are DEVICE addresses, except these (host memory of any element type)

@@ -20,6 +20,7 @@ from .circle import CanonicCoset, CirclePoint, Coset, bit_reverse_index
 from .fields import M31, QM31
 from .poly import (HipCircleEvaluation, HipCirclePoly, SecureCirclePoly, TwiddleTree, evaluate_polynomials, interpolate_columns,
                    precompute_twiddles)
+from .logup import INTERACTION_TRACE_IDX  # noqa: F401  (the third tree index, beside the two below)
 from .quotients import generate_secure_powers
 
 PREPROCESSED_TRACE_IDX = 0

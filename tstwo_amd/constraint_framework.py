@@ -12,8 +12,12 @@ The prover evaluates a component's constraints on the whole evaluation domain wi
 (exactly these types, not subclasses) run on the hand-written kernel of tstwo_air_constraint_quotients, every other eval on the
 program interpreter.  WideFibonacciComponent and MulAddComponent are FrameworkComponents of those two evals, as in Rust.
 
-Only the main trace (ORIGINAL_TRACE_IDX) is read at row offsets; preprocessed columns are read at offset 0 (as in Rust), and values
-inside constraints are base-field (M31) values: interaction trees and secure-field (LogUp) columns are not supported.
+The main trace (ORIGINAL_TRACE_IDX) is read at row offsets; preprocessed columns are read at offset 0 (as in Rust).  LogUp
+(tstwo_amd/logup.py, Rust logup.rs): add_to_relation / finalize_logup_* read the interaction trace (INTERACTION_TRACE_IDX, 4 base
+columns per secure column, the last one at offsets -1 and 0) and add secure-field (QM31) constraints.  The program path lowers a
+secure value to its 4 base coordinates (SecureExpr): a secure constraint is 4 ACCs whose coefficients are c, c i, c u, c iu for
+its random coefficient c, so the interpreter and its program encoding stay base-field.  The interaction trace itself is built on
+the device by logup.LogupTraceGenerator.
 """
 from __future__ import annotations
 
@@ -27,6 +31,7 @@ from .air import (AIR_MUL_ADD, AIR_WIDE_FIB, ORIGINAL_TRACE_IDX, PREPROCESSED_TR
 from .backend import SecureColumnByCoords
 from .circle import CanonicCoset, CirclePoint, bit_reverse_index
 from .fields import M31, QM31, P
+from .logup import INTERACTION_TRACE_IDX, LogupTraceGenerator, LookupElements, RelationEntry
 from .poly import evaluate_polynomials
 
 # include/tstwo_hip.h TSTWO_AIR_OP_* and TSTWO_AIR_PROGRAM_MAX_*
@@ -139,32 +144,176 @@ class PointValue:
         return PointValue(self.v.square())
 
 
-# ------------------------------------------------------------------ EvalAtRow
-class EvalAtRow:
-    """The surface `evaluate` sees (Rust EvalAtRow).  Subclasses produce the values."""
+# ------------------------------------------------------------------ secure values of the symbolic evaluators
+# A coordinate is an int (a constant) or an Expr.  These helpers fold constants 0 and 1, so that an M31 value lifted to QM31 does
+# not turn into chains of x * 0; Expr itself folds nothing.
+def _sadd(a, b):
+    if isinstance(a, int) and isinstance(b, int):
+        return (a + b) % P
+    if isinstance(a, int) and a == 0:
+        return b
+    if isinstance(b, int) and b == 0:
+        return a
+    return (b + a) if isinstance(a, int) else (a + b)
 
-    def __init__(self):
+
+def _ssub(a, b):
+    if isinstance(a, int) and isinstance(b, int):
+        return (a - b) % P
+    if isinstance(b, int) and b == 0:
+        return a
+    if isinstance(a, int) and a == 0:
+        return -b
+    return (a - b) if isinstance(a, Expr) else (Expr.const(a) - b)
+
+
+def _smul(a, b):
+    if isinstance(a, int) and isinstance(b, int):
+        return a * b % P
+    if (isinstance(a, int) and a == 0) or (isinstance(b, int) and b == 0):
+        return 0
+    if isinstance(a, int) and a == 1:
+        return b
+    if isinstance(b, int) and b == 1:
+        return a
+    return (b * a) if isinstance(a, int) else (a * b)
+
+
+def _sneg(a):
+    return (-a) % P if isinstance(a, int) else -a
+
+
+def _cmul(ar, ai, br, bi):
+    """(ar + ai i)(br + bi i)."""
+    return _ssub(_smul(ar, br), _smul(ai, bi)), _sadd(_smul(ar, bi), _smul(ai, br))
+
+
+def _qmul(x, y):
+    """QM31 product over coordinates: (x0 + x1 u)(y0 + y1 u) = x0 y0 + (2 + i) x1 y1 + (x0 y1 + x1 y0) u (u^2 = 2 + i)."""
+    c0r, c0i = _cmul(x[0], x[1], y[0], y[1])
+    tr, ti = _cmul(x[2], x[3], y[2], y[3])
+    rr, ri = _ssub(_sadd(tr, tr), ti), _sadd(tr, _sadd(ti, ti))         # (2 + i)(tr + ti i)
+    d0r, d0i = _cmul(x[0], x[1], y[2], y[3])
+    d1r, d1i = _cmul(x[2], x[3], y[0], y[1])
+    return (_sadd(c0r, rr), _sadd(c0i, ri), _sadd(d0r, d1r), _sadd(d0i, d1i))
+
+
+class SecureExpr:
+    """A secure-field (QM31) value inside the Info and Program evaluators: 4 base coordinates c (ints for constants, else Expr),
+    the value c0 + c1 i + c2 u + c3 iu.  Mixes with Expr, ints, M31 and QM31 (an Expr on the left of an operator does not know
+    it: write the SecureExpr first)."""
+
+    __slots__ = ("c",)
+
+    def __init__(self, coords):
+        self.c = tuple(coords)
+
+    @staticmethod
+    def lift(o) -> "SecureExpr":
+        if isinstance(o, SecureExpr):
+            return o
+        if isinstance(o, QM31):
+            return SecureExpr(o.tup())
+        if isinstance(o, M31):
+            return SecureExpr((o.value, 0, 0, 0))
+        if isinstance(o, int):
+            return SecureExpr((int(o) % P, 0, 0, 0))
+        if isinstance(o, Expr):
+            return SecureExpr((o, 0, 0, 0))
+        raise TypeError(f"secure constraint values mix with Expr, ints, M31 and QM31, not {type(o).__name__}")
+
+    @property
+    def degree(self) -> int:
+        return max(x.degree if isinstance(x, Expr) else 0 for x in self.c)
+
+    def coords(self) -> list:
+        """The 4 coordinates as Expr nodes (constants as CONST)."""
+        return [Expr.const(x) if isinstance(x, int) else x for x in self.c]
+
+    def __add__(self, o): return SecureExpr(map(_sadd, self.c, SecureExpr.lift(o).c))
+    def __radd__(self, o): return SecureExpr(map(_sadd, SecureExpr.lift(o).c, self.c))
+    def __sub__(self, o): return SecureExpr(map(_ssub, self.c, SecureExpr.lift(o).c))
+    def __rsub__(self, o): return SecureExpr(map(_ssub, SecureExpr.lift(o).c, self.c))
+    def __mul__(self, o): return SecureExpr(_qmul(self.c, SecureExpr.lift(o).c))
+    def __rmul__(self, o): return SecureExpr(_qmul(SecureExpr.lift(o).c, self.c))
+    def __neg__(self): return SecureExpr(map(_sneg, self.c))
+
+    def square(self):
+        return self * self
+
+
+# basis of QM31 over M31 (from_partial_evals): a secure constraint's 4 coordinates take coefficients c * (1, i, u, iu)
+_BASIS = [QM31.from_u32_unchecked(*[1 if j == k else 0 for j in range(4)]) for k in range(4)]
+
+
+def expand_coeffs(coeffs, secure_flags) -> list:
+    """The per-ACC coefficients of a program: c for a base constraint, c * (1, i, u, iu) for a secure one."""
+    out = []
+    for c, secure in zip(coeffs, secure_flags):
+        out += [c.mul(b) for b in _BASIS] if secure else [c]
+    return out
+
+
+# ------------------------------------------------------------------ EvalAtRow
+def _offsets(offsets) -> list:
+    offsets = [int(o) for o in offsets]
+    if not offsets:
+        raise ValueError("a mask needs at least one offset")
+    if any(abs(o) > MAX_OFFSET for o in offsets):
+        raise ValueError(f"row offsets are limited to |offset| <= {MAX_OFFSET}")
+    return offsets
+
+
+class EvalAtRow:
+    """The surface `evaluate` sees (Rust EvalAtRow).  Subclasses produce the values.  claimed_sum and log_size give the LogUp
+    shift claimed_sum / 2^log_size of finalize_logup_batched (Rust LogupAtRow)."""
+
+    def __init__(self, claimed_sum: QM31 | None = None, log_size: int = 0):
         self.n_main = 0                 # main-trace mask columns handed out so far
         self.main_offsets = []          # offsets of each main column, in call order
         self.constraints = []
+        self.n_interaction = 0          # interaction (tree 2) base columns handed out so far
+        self.interaction_offsets = []   # offsets of each of them
+        self.fracs = []                 # LogUp fractions (numerator, denominator) not yet finalized
+        self.n_entries = 0
+        self.logup_finalized = False
+        claimed = claimed_sum if claimed_sum is not None else QM31.zero()
+        self.cumsum_shift = claimed.mulM31(M31(1 << log_size).inverse()) if log_size else claimed
 
     def _value(self, column, offset):
         raise NotImplementedError
 
+    def _secure(self, o):
+        """o as this evaluator's secure value."""
+        return SecureExpr.lift(o)
+
+    def _extension_values(self, k: int, offsets) -> list:
+        """The secure values of interaction columns k .. k + 3 at each offset (symbolic: the 4 loads as coordinates)."""
+        return [SecureExpr([self._value(("int", k + c), o) for c in range(4)]) for o in offsets]
+
     def next_interaction_mask(self, interaction: int, offsets) -> list:
         if interaction == PREPROCESSED_TRACE_IDX:
             raise ValueError("preprocessed columns are read with get_preprocessed_column (offset 0 only)")
+        if interaction == INTERACTION_TRACE_IDX:
+            raise ValueError("the interaction trace is read with next_extension_interaction_mask (4 base columns per value)")
         if interaction != ORIGINAL_TRACE_IDX:
             raise ValueError("only the main trace (ORIGINAL_TRACE_IDX) is supported")
-        offsets = [int(o) for o in offsets]
-        if not offsets:
-            raise ValueError("a mask needs at least one offset")
-        if any(abs(o) > MAX_OFFSET for o in offsets):
-            raise ValueError(f"row offsets are limited to |offset| <= {MAX_OFFSET}")
+        offsets = _offsets(offsets)
         k = self.n_main
         self.n_main += 1
         self.main_offsets.append(offsets)
         return [self._value(("main", k), o) for o in offsets]
+
+    def next_extension_interaction_mask(self, interaction: int, offsets) -> list:
+        """One secure column of the interaction trace: 4 consecutive base columns of tree INTERACTION_TRACE_IDX read at the same
+        offsets, each value QM31.from_partial_evals of the 4 (Rust next_extension_interaction_mask)."""
+        if interaction != INTERACTION_TRACE_IDX:
+            raise ValueError("secure columns live in the interaction trace (INTERACTION_TRACE_IDX)")
+        offsets = _offsets(offsets)
+        k = self.n_interaction
+        self.n_interaction += 4
+        self.interaction_offsets += [list(offsets) for _ in range(4)]
+        return self._extension_values(k, offsets)
 
     def next_trace_mask(self):
         return self.next_interaction_mask(ORIGINAL_TRACE_IDX, [0])[0]
@@ -177,16 +326,78 @@ class EvalAtRow:
     def add_constraint(self, expr) -> None:
         self.constraints.append(expr)
 
+    # --- LogUp (Rust logup.rs LogupAtRow)
+    def add_to_relation(self, entry: RelationEntry) -> None:
+        if self.logup_finalized:
+            raise ValueError("a relation entry added after finalize_logup")
+        self.fracs.append((entry.multiplicity, entry.relation.combine(entry.values)))
+        self.n_entries += 1
+
+    def finalize_logup_batched(self, batching) -> None:
+        """Fractions of one batch are summed (a/b + c/d = (ad + cb)/(bd), left to right) into one interaction column each.  Batch
+        j before the last: column cur_j at [0], constraint (cur_j - cur_{j-1}) den_j - num_j (cur_{-1} = 0).  The last batch:
+        its column at [-1, 0], constraint (cur - prev_row - cur_{last-1} + claimed_sum / 2^log_size) den - num."""
+        if self.logup_finalized:
+            raise ValueError("finalize_logup called twice")
+        batching = [int(b) for b in batching]
+        if not self.fracs:
+            raise ValueError("finalize_logup without relation entries")
+        if len(batching) != len(self.fracs):
+            raise ValueError(f"batching names {len(batching)} entries, {len(self.fracs)} were added")
+        last = max(batching)
+        if sorted(set(batching)) != list(range(last + 1)):
+            raise ValueError("batches must be consecutive from 0")
+        self.logup_finalized = True
+        sums = []
+        for j in range(last + 1):
+            num = den = None
+            for b, (n, d) in zip(batching, self.fracs):
+                if b != j:
+                    continue
+                n, d = self._secure(n), self._secure(d)
+                if den is None:
+                    num, den = n, d
+                else:
+                    num, den = num * d + n * den, den * d
+            sums.append((num, den))
+        self.fracs = []
+        prev_col = self._secure(0)
+        for num, den in sums[:-1]:
+            [cur] = self.next_extension_interaction_mask(INTERACTION_TRACE_IDX, [0])
+            self.add_constraint((cur - prev_col) * den - num)
+            prev_col = cur
+        num, den = sums[-1]
+        prev_row, cur = self.next_extension_interaction_mask(INTERACTION_TRACE_IDX, [-1, 0])
+        self.add_constraint((cur - prev_row - prev_col + self._secure(self.cumsum_shift)) * den - num)
+
+    def finalize_logup(self) -> None:
+        """One fraction per batch."""
+        self.finalize_logup_batched(range(len(self.fracs)))
+
+    def finalize_logup_in_pairs(self) -> None:
+        """Batches 0, 0, 1, 1, ...: two fractions per interaction column."""
+        self.finalize_logup_batched([i // 2 for i in range(len(self.fracs))])
+
+    def check_finished(self) -> None:
+        """Called after `evaluate`: relation entries must have been finalized."""
+        if self.fracs and not self.logup_finalized:
+            raise ValueError("evaluate added relation entries without finalize_logup")
+
     # camelCase aliases (the reference's names)
     nextInteractionMask = next_interaction_mask
+    nextExtensionInteractionMask = next_extension_interaction_mask
     nextTraceMask = next_trace_mask
     getPreprocessedColumn = get_preprocessed_column
     addConstraint = add_constraint
+    addToRelation = add_to_relation
+    finalizeLogupBatched = finalize_logup_batched
+    finalizeLogup = finalize_logup
+    finalizeLogupInPairs = finalize_logup_in_pairs
 
 
 class _SymbolicEval(EvalAtRow):
-    def __init__(self):
-        super().__init__()
+    def __init__(self, claimed_sum: QM31 | None = None, log_size: int = 0):
+        super().__init__(claimed_sum, log_size)
         self.pre_used = set()
 
     def _value(self, column, offset):
@@ -195,7 +406,10 @@ class _SymbolicEval(EvalAtRow):
         return Expr.load(column, offset)
 
     def add_constraint(self, expr) -> None:
-        self.constraints.append(Expr._lift(expr))
+        if isinstance(expr, SecureExpr):
+            self.constraints.append(SecureExpr(expr.coords()))
+        else:
+            self.constraints.append(Expr._lift(expr))
 
 
 class InfoEvaluator(_SymbolicEval):
@@ -214,9 +428,16 @@ class InfoEvaluator(_SymbolicEval):
     def n_preprocessed(self) -> int:
         return max(self.pre_used) + 1 if self.pre_used else 0
 
+    def secure_flags(self) -> list:
+        """Per constraint: True for a secure (QM31) one, which takes 4 ACCs in the program."""
+        return [isinstance(c, SecureExpr) for c in self.constraints]
+
     def mask_offsets(self) -> list:
-        """TreeVec: per preprocessed column read, [0]; per main column, its offsets."""
-        return [[[0] for _ in range(self.n_preprocessed())], [list(o) for o in self.main_offsets]]
+        """TreeVec: per preprocessed column read, [0]; per main column, its offsets; with LogUp, per interaction column its offsets."""
+        trees = [[[0] for _ in range(self.n_preprocessed())], [list(o) for o in self.main_offsets]]
+        if self.n_interaction:
+            trees.append([list(o) for o in self.interaction_offsets])
+        return trees
 
 
 def required_log_degree_bound(log_size: int, max_degree: int) -> int:
@@ -230,14 +451,19 @@ def required_log_degree_bound(log_size: int, max_degree: int) -> int:
 def info(eval_) -> InfoEvaluator:
     ev = InfoEvaluator()
     eval_.evaluate(ev)
+    ev.check_finished()
     return ev
 
 
 class ProgramEvaluator(_SymbolicEval):
-    """Records the constraints, then compile() turns them into the program of tstwo_air_eval_program."""
+    """Records the constraints, then compile() turns them into the program of tstwo_air_eval_program (a secure constraint as its 4
+    coordinates, in order)."""
 
-    def compile(self, n_main: int | None = None) -> "Program":
-        return compile_program(self.constraints, self.n_main if n_main is None else n_main)
+    def compile(self, n_main: int | None = None, n_pre: int = 0) -> "Program":
+        roots = []
+        for c in self.constraints:
+            roots += c.coords() if isinstance(c, SecureExpr) else [c]
+        return compile_program(roots, self.n_main if n_main is None else n_main, n_pre)
 
 
 class Program:
@@ -255,8 +481,9 @@ def encode(op: int, dst: int = 0, x: int = 0, w1: int = 0) -> tuple:
     return (op | (dst << 8) | (x << 16), w1 & 0xffffffff)
 
 
-def compile_program(constraints: list, n_main: int) -> Program:
-    """Straight-line program of the constraint DAG.  Nodes are merged structurally (same operation on the same merged operands;
+def compile_program(constraints: list, n_main: int, n_pre: int = 0) -> Program:
+    """Straight-line program of the constraint DAG over the columns main (n_main), preprocessed (n_pre), interaction, in that order.
+    Nodes are merged structurally (same operation on the same merged operands;
     loads by column and offset; constants by value).  Instructions are ordered by a depth-first walk of each constraint in turn
     (the operand that needs more registers first), each value gets the lowest free register at its definition and frees it
     after its last use (an instruction may write the register its last operand read).  Raises ValueError when the program
@@ -361,7 +588,7 @@ def compile_program(constraints: list, n_main: int) -> Program:
         d = take(i, protect)
         if n.op == "load":
             (col, offset) = n.args
-            x = col[1] if col[0] == "main" else n_main + col[1]
+            x = col[1] if col[0] == "main" else n_main + col[1] if col[0] == "pre" else n_main + n_pre + col[1]
             if x >= MAX_COLS:
                 raise ValueError(f"more than {MAX_COLS} columns")
             words.extend(encode(OP_LOAD, d, x, offset))
@@ -407,16 +634,28 @@ class PointEvaluator(EvalAtRow):
     """Evaluates the constraints over QM31 (Rust PointEvaluator): main[k] = the values of main column k at its offsets, pre[i] =
     the value of the component's i-th preprocessed column."""
 
-    def __init__(self, main: list, pre: list):
-        super().__init__()
-        self.main, self.pre = main, pre
+    def __init__(self, main: list, pre: list, inter: list = (), claimed_sum: QM31 | None = None, log_size: int = 0):
+        super().__init__(claimed_sum, log_size)
+        self.main, self.pre, self.inter = main, pre, list(inter)
+
+    def _secure(self, o):
+        return PointValue(PointValue._q(o))
+
+    def _extension_values(self, k: int, offsets) -> list:
+        # at the OODS point every base column's sample is a QM31: combine the 4 with from_partial_evals (no packing)
+        if k + 4 > len(self.inter):
+            raise ValueError("more interaction columns than sampled")
+        if any(len(self.inter[k + c]) != len(offsets) for c in range(4)):
+            raise ValueError("one sampled value per mask offset expected")
+        return [PointValue(QM31.from_partial_evals([self.inter[k + c][j] for c in range(4)])) for j in range(len(offsets))]
 
     def next_interaction_mask(self, interaction: int, offsets) -> list:
         offsets = list(offsets)
-        if self.n_main >= len(self.main):
-            raise ValueError("more mask columns than sampled")
-        if len(self.main[self.n_main]) != len(offsets):
-            raise ValueError("one sampled value per mask offset expected")
+        if interaction == ORIGINAL_TRACE_IDX:
+            if self.n_main >= len(self.main):
+                raise ValueError("more mask columns than sampled")
+            if len(self.main[self.n_main]) != len(offsets):
+                raise ValueError("one sampled value per mask offset expected")
         self._j = 0
         return super().next_interaction_mask(interaction, offsets)
 
@@ -431,11 +670,13 @@ class PointEvaluator(EvalAtRow):
         return PointValue(v)
 
 
-def point_constraints(eval_, main: list, pre: list) -> list:
+def point_constraints(eval_, main: list, pre: list, inter: list = (), claimed_sum: QM31 | None = None, log_size: int = 0) -> list:
     """The constraints of eval_ at a point as QM31 values (no denominator): main[k] the sampled values of main column k (one per
-    offset), pre[i] the component's i-th preprocessed column."""
-    ev = PointEvaluator(main, pre)
+    offset), pre[i] the component's i-th preprocessed column, inter[k] the sampled values of interaction column k; claimed_sum
+    and log_size give the LogUp shift."""
+    ev = PointEvaluator(main, pre, inter, claimed_sum, log_size)
     eval_.evaluate(ev)
+    ev.check_finished()
     return [PointValue._q(c) for c in ev.constraints]
 # ------------------------------------------------------------------ the device entry point
 def evaluate_program(cols, trace_log_size: int, log_expand: int, program: Program, coeffs, denom_inv, accum: SecureColumnByCoords) -> None:
@@ -453,9 +694,12 @@ class FrameworkComponent:
     """A component defined by a FrameworkEval (`log_size()`, `max_constraint_log_degree_bound()`, `evaluate(eval)`).  Its main
     columns are allocated in the main trace tree by `location_allocator`; `preprocessed_column_indices[i]` is the position in the
     preprocessed tree (tree 0) of the column `get_preprocessed_column(i)` reads.  `kind` is the TSTWO_AIR_* kind of the
-    hand-written kernel for the eval's exact type (None: the program path, and `program` holds the compiled constraints)."""
+    hand-written kernel for the eval's exact type (None: the program path, and `program` holds the compiled constraints).
+    claimed_sum: the LogUp sum of the component's interaction trace (LogupTraceGenerator.finalize_last), required exactly when
+    `evaluate` adds relation entries; its interaction columns are then allocated in tree INTERACTION_TRACE_IDX, 4 per batch."""
 
-    def __init__(self, eval_, location_allocator: TraceLocationAllocator | None = None, preprocessed_column_indices=None):
+    def __init__(self, eval_, location_allocator: TraceLocationAllocator | None = None, preprocessed_column_indices=None, *,
+                 claimed_sum: QM31 | None = None):
         self.eval = eval_
         self.log_size = eval_.log_size()
         if self.log_size < 1:
@@ -475,29 +719,48 @@ class FrameworkComponent:
         self.preprocessed_column_indices = list(preprocessed_column_indices or [])
         if inf.n_preprocessed() > len(self.preprocessed_column_indices):
             raise ValueError(f"evaluate reads {inf.n_preprocessed()} preprocessed columns, {len(self.preprocessed_column_indices)} named")
+        if inf.n_entries and claimed_sum is None:
+            raise ValueError("evaluate adds relation entries: FrameworkComponent needs claimed_sum")
+        if not inf.n_entries and claimed_sum is not None:
+            raise ValueError("claimed_sum given, but evaluate adds no relation entries")
+        self.claimed_sum = claimed_sum
+        self.interaction_offsets = [list(o) for o in inf.interaction_offsets]
+        self.n_interaction_columns = len(self.interaction_offsets)
+        self.secure_flags = inf.secure_flags()
         alloc = location_allocator or TraceLocationAllocator()
-        self.trace_locations = alloc.next_for_structure({ORIGINAL_TRACE_IDX: self.n_columns})
+        structure = {ORIGINAL_TRACE_IDX: self.n_columns}
+        if self.n_interaction_columns:
+            structure[INTERACTION_TRACE_IDX] = self.n_interaction_columns
+        self.trace_locations = alloc.next_for_structure(structure)
         self.kind = _HAND_WRITTEN_KINDS.get(type(eval_))
         self.program = None
         if self.kind is None:
-            pe = ProgramEvaluator()
+            pe = ProgramEvaluator(claimed_sum, self.log_size)
             eval_.evaluate(pe)
-            self.program = pe.compile(self.n_columns)
+            pe.check_finished()
+            self.program = pe.compile(self.n_columns, len(self.preprocessed_column_indices))
 
     # --- Component
     def max_constraint_log_degree_bound(self) -> int:
         return self.eval.max_constraint_log_degree_bound()
 
     def trace_log_degree_bounds(self) -> list:
-        return [[self.log_size] * len(self.preprocessed_column_indices), [self.log_size] * self.n_columns]
+        trees = [[self.log_size] * len(self.preprocessed_column_indices), [self.log_size] * self.n_columns]
+        if self.n_interaction_columns:
+            trees.append([self.log_size] * self.n_interaction_columns)
+        return trees
 
     def mask_points(self, point: CirclePoint) -> list:
-        """Preprocessed columns at [point]; main column k at point + step * offset for each of its offsets, in order."""
-        return [[[point] for _ in self.preprocessed_column_indices],
-                [[shifted_mask_point(point, self.log_size, o) for o in offs] for offs in self.mask_offsets]]
+        """Preprocessed columns at [point]; main column k at point + step * offset for each of its offsets, in order; the same
+        for the interaction columns (tree INTERACTION_TRACE_IDX) when the eval uses LogUp."""
+        trees = [[[point] for _ in self.preprocessed_column_indices],
+                 [[shifted_mask_point(point, self.log_size, o) for o in offs] for offs in self.mask_offsets]]
+        if self.n_interaction_columns:
+            trees.append([[shifted_mask_point(point, self.log_size, o) for o in offs] for offs in self.interaction_offsets])
+        return trees
 
-    def _columns(self) -> range:
-        start, end = self.trace_locations[ORIGINAL_TRACE_IDX]
+    def _columns(self, tree: int = ORIGINAL_TRACE_IDX) -> range:
+        start, end = self.trace_locations[tree]
         return range(start, end)
 
     def evaluate_constraint_quotients_at_point(self, point: CirclePoint, mask: list, acc: PointEvaluationAccumulator) -> None:
@@ -512,7 +775,13 @@ class FrameworkComponent:
             if len(col) != 1:
                 raise ValueError("one sampled value per preprocessed column expected")
             pre.append(col[0])
-        for c in point_constraints(self.eval, main, pre):
+        inter = []
+        if self.n_interaction_columns:
+            inter = [list(mask[INTERACTION_TRACE_IDX][ci]) for ci in self._columns(INTERACTION_TRACE_IDX)]
+            for vals, offs in zip(inter, self.interaction_offsets):
+                if len(vals) != len(offs):
+                    raise ValueError("one sampled value per mask offset expected")
+        for c in point_constraints(self.eval, main, pre, inter, self.claimed_sum, self.log_size):
             acc.accumulate(c.mul(denom_inv))
 
     # --- ComponentProver
@@ -531,10 +800,13 @@ class FrameworkComponent:
 
     def trace_on_eval_domain(self, trace, twiddles) -> list:
         """The columns the kernels read, on CanonicCoset(max_constraint_log_degree_bound).circle_domain(): the main columns, then
-        the preprocessed ones; each the committed evaluation when it already lives there (log blowup 1), else its polynomial
-        evaluated there (one batched launch sequence per tree)."""
-        return (self._on_eval_domain(trace, ORIGINAL_TRACE_IDX, self._columns(), twiddles)
+        the preprocessed ones, then the interaction ones (LogUp); each the committed evaluation when it already lives there (log
+        blowup 1), else its polynomial evaluated there (one batched launch sequence per tree)."""
+        cols = (self._on_eval_domain(trace, ORIGINAL_TRACE_IDX, self._columns(), twiddles)
                 + self._on_eval_domain(trace, PREPROCESSED_TRACE_IDX, self.preprocessed_column_indices, twiddles))
+        if self.n_interaction_columns:
+            cols += self._on_eval_domain(trace, INTERACTION_TRACE_IDX, self._columns(INTERACTION_TRACE_IDX), twiddles)
+        return cols
 
     def evaluate_constraint_quotients_on_domain(self, trace, acc: DomainEvaluationAccumulator, twiddles) -> None:
         eval_log = self.max_constraint_log_degree_bound()
@@ -546,6 +818,8 @@ class FrameworkComponent:
         if self.kind is not None:
             evaluate_constraint_quotients(self.kind, cols, self.log_size, eval_log - self.log_size, coeffs, denom_inv, column_acc.col)
         else:
+            if any(self.secure_flags):
+                coeffs = expand_coeffs(coeffs, self.secure_flags)
             evaluate_program(cols, self.log_size, eval_log - self.log_size, self.program, coeffs, denom_inv, column_acc.col)
 
 
@@ -678,3 +952,147 @@ def is_first_column(log_size: int):
     c = np.zeros(1 << log_size, dtype=np.uint32)
     c[coset_order_positions(log_size)[0]] = 1
     return c
+
+
+# ------------------------------------------------------------------ LogUp examples: a permutation, a range check
+class PermutationEval:
+    """Columns a and b with the entries (+1, [a]) and (-1, [b]) of one relation, in one batch (finalize_logup_in_pairs).  The claimed
+    sum is 0 exactly when b permutes a (with high probability over the lookup elements).  Degree 3: log_size + 2."""
+
+    def __init__(self, log_n_rows: int, lookup_elements: LookupElements):
+        self.log_n_rows, self.lookup_elements = log_n_rows, lookup_elements
+
+    def log_size(self) -> int:
+        return self.log_n_rows
+
+    def max_constraint_log_degree_bound(self) -> int:
+        return self.log_n_rows + 2
+
+    def evaluate(self, eval):
+        a, b = eval.next_trace_mask(), eval.next_trace_mask()
+        eval.add_to_relation(RelationEntry(self.lookup_elements, 1, [a]))
+        eval.add_to_relation(RelationEntry(self.lookup_elements, -1, [b]))
+        eval.finalize_logup_in_pairs()
+        return eval
+
+    logSize = log_size
+    maxConstraintLogDegreeBound = max_constraint_log_degree_bound
+
+
+class RangeCheckTableEval:
+    """The table side of a range check over [0, 2^log_range): preprocessed column 0 holds value k at coset row k, the main column
+    `multiplicity` says how often the values components use it; entry (-multiplicity, [value]), finalize_logup().  Degree 2."""
+
+    def __init__(self, log_range: int, lookup_elements: LookupElements):
+        self.log_range, self.lookup_elements = log_range, lookup_elements
+
+    def log_size(self) -> int:
+        return self.log_range
+
+    def max_constraint_log_degree_bound(self) -> int:
+        return self.log_range + 1
+
+    def evaluate(self, eval):
+        value = eval.get_preprocessed_column(0)
+        multiplicity = eval.next_trace_mask()
+        eval.add_to_relation(RelationEntry(self.lookup_elements, -multiplicity, [value]))
+        eval.finalize_logup()
+        return eval
+
+    logSize = log_size
+    maxConstraintLogDegreeBound = max_constraint_log_degree_bound
+
+
+class RangeCheckValuesEval:
+    """The values side: two checked columns per row, entries (1, [v0]) and (1, [v1]) in one batch (finalize_logup_in_pairs).
+    Degree 3: log_size + 2."""
+
+    def __init__(self, log_n_rows: int, lookup_elements: LookupElements):
+        self.log_n_rows, self.lookup_elements = log_n_rows, lookup_elements
+
+    def log_size(self) -> int:
+        return self.log_n_rows
+
+    def max_constraint_log_degree_bound(self) -> int:
+        return self.log_n_rows + 2
+
+    def evaluate(self, eval):
+        v0, v1 = eval.next_trace_mask(), eval.next_trace_mask()
+        eval.add_to_relation(RelationEntry(self.lookup_elements, 1, [v0]))
+        eval.add_to_relation(RelationEntry(self.lookup_elements, 1, [v1]))
+        eval.finalize_logup_in_pairs()
+        return eval
+
+    logSize = log_size
+    maxConstraintLogDegreeBound = max_constraint_log_degree_bound
+
+
+def _col(x):
+    from .backend import HipColumn
+    return x if isinstance(x, HipColumn) else HipColumn(x)
+
+
+def permutation_interaction_trace(log_n_rows: int, a, b, lookup_elements: LookupElements):
+    """The interaction trace of PermutationEval on the device: (4 HipCircleEvaluations, claimed sum).  a, b: HipColumns or arrays."""
+    gen = LogupTraceGenerator(log_n_rows)
+    col = gen.new_col()
+    col.write_frac(1, lookup_elements.combine_columns([_col(a)]))
+    col.write_frac(P - 1, lookup_elements.combine_columns([_col(b)]))
+    col.finalize_col()
+    return gen.finalize_last()
+
+
+def _coset_positions(log_size: int):
+    """coset_order_positions as a numpy array, from the closed form of csrc/logup.hip: with j = k >> 1 and rev the bit reversal
+    over log_size - 1 bits, row k sits at 2 rev(j) (k even) or 2 (2^(log_size-1) - 1 - rev(j)) + 1 (k odd)."""
+    import numpy as np
+    k = np.arange(1 << log_size, dtype=np.int64)
+    j, r = k >> 1, np.zeros(1 << log_size, dtype=np.int64)
+    for _ in range(log_size - 1):
+        r, j = (r << 1) | (j & 1), j >> 1
+    return np.where(k % 2 == 0, 2 * r, 2 * ((1 << (log_size - 1)) - 1 - r) + 1)
+
+
+def range_check_table_column(log_range: int):
+    """The preprocessed column of RangeCheckTableEval: value k at coset row k (numpy uint32, storage order)."""
+    import numpy as np
+    c = np.empty(1 << log_range, dtype=np.uint32)
+    c[_coset_positions(log_range)] = np.arange(1 << log_range, dtype=np.uint32)
+    return c
+
+
+def range_check_multiplicities(log_range: int, *value_columns):
+    """The multiplicity column of RangeCheckTableEval (numpy uint32, storage order) for the values in `value_columns`, which
+    must lie in [0, 2^log_range)."""
+    import numpy as np
+    counts = np.zeros(1 << log_range, dtype=np.int64)
+    for v in value_columns:
+        v = np.asarray(v, dtype=np.int64)
+        if v.size and (v.min() < 0 or v.max() >= 1 << log_range):
+            raise ValueError("a checked value lies outside the range")
+        counts += np.bincount(v, minlength=1 << log_range)
+    m = np.empty(1 << log_range, dtype=np.uint32)
+    m[_coset_positions(log_range)] = (counts % P).astype(np.uint32)
+    return m
+
+
+def range_check_table_interaction_trace(log_range: int, multiplicity, lookup_elements: LookupElements):
+    """The interaction trace of RangeCheckTableEval: (4 HipCircleEvaluations, claimed sum); multiplicity: HipColumn or array."""
+    import numpy as np
+    m = multiplicity.to_numpy() if hasattr(multiplicity, "to_numpy") else np.asarray(multiplicity, dtype=np.uint32)
+    neg = ((P - m.astype(np.uint64)) % P).astype(np.uint32)
+    gen = LogupTraceGenerator(log_range)
+    col = gen.new_col()
+    col.write_frac(_col(neg), lookup_elements.combine_columns([_col(range_check_table_column(log_range))]))
+    col.finalize_col()
+    return gen.finalize_last()
+
+
+def range_check_values_interaction_trace(log_n_rows: int, v0, v1, lookup_elements: LookupElements):
+    """The interaction trace of RangeCheckValuesEval: (4 HipCircleEvaluations, claimed sum)."""
+    gen = LogupTraceGenerator(log_n_rows)
+    col = gen.new_col()
+    col.write_frac(1, lookup_elements.combine_columns([_col(v0)]))
+    col.write_frac(1, lookup_elements.combine_columns([_col(v1)]))
+    col.finalize_col()
+    return gen.finalize_last()

@@ -1,0 +1,212 @@
+"""LogUp lookups (Rust stwo constraint_framework/logup.rs): lookup elements, relation entries, and the interaction trace built on
+the device (csrc/logup.hip).
+
+Constraint side (constraint_framework.EvalAtRow): add_to_relation(RelationEntry(relation, multiplicity, values)) records the
+fraction multiplicity / relation.combine(values); finalize_logup_batched groups the fractions into batches, one interaction column
+each (4 base columns of INTERACTION_TRACE_IDX, one QM31 value per row).  Trace side (LogupTraceGenerator): one column per batch,
+column j = column j - 1 + the batch's fractions (tstwo_logup_column, one fused launch per column), then the last column becomes the
+running sum over the coset order, shifted by claimed_sum / 2^log_size so that it ends at 0 (tstwo_logup_finalize_last), which
+also returns the claimed sum.
+
+Caller protocol (the verifier mirrors it): commit the preprocessed tree, commit the main tree, LookupElements.draw, generate the
+interaction trace, channel.mix_felts(claimed sums in component order), commit the interaction tree, prove.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _lib as L
+from .backend import HipColumn, SecureColumnByCoords
+from .circle import CanonicCoset
+from .fields import M31, QM31, P
+from .poly import HipCircleEvaluation
+
+INTERACTION_TRACE_IDX = 2
+# include/tstwo_hip.h TSTWO_LOGUP_MAX_*
+MAX_FRACS, MAX_TERMS, MAX_LOG = 8, 16, 28
+
+
+def _felt(v) -> QM31:
+    if isinstance(v, QM31):
+        return v
+    if isinstance(v, M31):
+        return QM31.from_(v)
+    if isinstance(v, int):
+        return QM31.from_(M31(int(v) % P))
+    raise TypeError(f"a relation value is an int, M31 or QM31 here, not {type(v).__name__}")
+
+
+class LookupElements:
+    """The random elements of one relation (Rust LookupElements<N>): z, alpha and alpha_powers[i] = alpha^i, i < size."""
+
+    def __init__(self, z: QM31, alpha: QM31, size: int):
+        if size < 1:
+            raise ValueError("a relation combines at least one value")
+        self.z, self.alpha = z, alpha
+        self.alpha_powers = [QM31.one()]
+        while len(self.alpha_powers) < size:
+            self.alpha_powers.append(self.alpha_powers[-1].mul(alpha))
+
+    @staticmethod
+    def draw(channel, size: int) -> "LookupElements":
+        z, alpha = channel.draw_felts(2)
+        return LookupElements(z, alpha, size)
+
+    @property
+    def size(self) -> int:
+        return len(self.alpha_powers)
+
+    def _values(self, values) -> list:
+        values = list(values)
+        if len(values) > self.size:
+            raise ValueError(f"{len(values)} values for a relation of size {self.size}")
+        return values
+
+    def combine(self, values):
+        """sum_i alpha^i values[i] - z.  Values inside `evaluate` (Expr / SecureExpr, PointValue) give the same kind of secure
+        value back; ints, M31 and QM31 give a QM31."""
+        from .constraint_framework import Expr, PointValue, SecureExpr
+        values = self._values(values)
+        if any(isinstance(v, (Expr, SecureExpr)) for v in values):
+            acc = SecureExpr.lift(0)
+            for v, p in zip(values, self.alpha_powers):
+                acc = acc + SecureExpr.lift(v) * p
+            return acc - self.z
+        if any(isinstance(v, PointValue) for v in values):
+            acc = PointValue(QM31.zero())
+            for v, p in zip(values, self.alpha_powers):
+                acc = acc + PointValue(PointValue._q(v)) * p
+            return acc - self.z
+        acc = QM31.zero()
+        for v, p in zip(values, self.alpha_powers):
+            acc = acc.add(p.mul(_felt(v)))
+        return acc.sub(self.z)
+
+    def combine_columns(self, values) -> "LinearForm":
+        """combine() over whole device columns, for LogupColGenerator.write_frac: values are HipColumns (M31) or constants, which
+        fold into the constant term here.  No device work."""
+        values = self._values(values)
+        terms, constant = [], self.z.neg()
+        for v, p in zip(values, self.alpha_powers):
+            if isinstance(v, HipColumn):
+                terms.append((p, v))
+            else:
+                constant = constant.add(p.mul(_felt(v)))
+        return LinearForm(terms, constant)
+
+    combineColumns = combine_columns
+
+
+class LinearForm:
+    """sum_t coeff_t cols_t[r] + constant: M31 columns, QM31 coefficients and constant (a tstwo_logup_frac denominator)."""
+
+    def __init__(self, terms, constant: QM31):
+        self.terms, self.constant = list(terms), constant
+
+
+class RelationEntry:
+    """One use of a relation on a row: multiplicity / relation.combine(values) joins the row's LogUp sum."""
+
+    def __init__(self, relation: LookupElements, multiplicity, values):
+        self.relation, self.multiplicity, self.values = relation, multiplicity, list(values)
+
+
+class Fraction:
+    __slots__ = ("numerator", "denominator")
+
+    def __init__(self, numerator, denominator):
+        self.numerator, self.denominator = numerator, denominator
+
+
+# ------------------------------------------------------------------ the device entries
+def logup_column(fracs, prev: SecureColumnByCoords | None, log_size: int, out: SecureColumnByCoords) -> None:
+    """tstwo_logup_column: out[r] = prev[r] (or 0) + sum num / den over fracs = [(numerator: int | M31 | HipColumn, LinearForm)]."""
+    if not 1 <= len(fracs) <= MAX_FRACS:
+        raise ValueError(f"1 to {MAX_FRACS} fractions per column")
+    n = 1 << log_size
+    descs = (L.LogupFrac * len(fracs))()
+    keep = []                           # the host tables must live until the call returns
+    for d, (num, form) in zip(descs, fracs):
+        if not 1 <= len(form.terms) <= MAX_TERMS:
+            raise ValueError(f"a denominator needs 1 to {MAX_TERMS} column terms")
+        if any(col.len() != n for _, col in form.terms):
+            raise ValueError("every column of a fraction must hold 2^log_size values")
+        cols = L.ptr_array([col.ptr for _, col in form.terms])
+        coeffs = L.u32x([w for p, _ in form.terms for w in p.tup()])
+        keep += [cols, coeffs]
+        d.cols, d.coeffs, d.n_terms = C.cast(cols, C.POINTER(L.vp)), C.cast(coeffs, L.u32p), len(form.terms)
+        d.constant[:] = list(form.constant.tup())
+        if isinstance(num, HipColumn):
+            if num.len() != n:
+                raise ValueError("the numerator column must hold 2^log_size values")
+            d.num, d.num_const = num.ptr, 0
+        else:
+            d.num, d.num_const = None, (num.value if isinstance(num, M31) else int(num)) % P
+    prev_ptrs = L.p4([c.ptr for c in prev.columns]) if prev is not None else None
+    L.call("tstwo_logup_column", descs, len(fracs), prev_ptrs, log_size, out.ptrs())
+
+
+def logup_finalize_last(col: SecureColumnByCoords, log_size: int) -> QM31:
+    """tstwo_logup_finalize_last: the column becomes its shifted running sum in coset order; returns the claimed sum."""
+    claimed = (C.c_uint32 * 4)()
+    L.call("tstwo_logup_finalize_last", col.ptrs(), log_size, claimed)
+    return QM31.from_u32_unchecked(*claimed)
+
+
+# ------------------------------------------------------------------ the generator (Rust LogupTraceGenerator)
+class LogupTraceGenerator:
+    """The interaction trace of one component on whole device columns: new_col() per batch, write_frac() per fraction of the
+    batch, finalize_col(), and finalize_last() for the evaluations (4 per batch) and the claimed sum."""
+
+    def __init__(self, log_size: int):
+        if not 1 <= log_size <= MAX_LOG:
+            raise ValueError(f"log_size must be 1 to {MAX_LOG}")
+        self.log_size = log_size
+        self.trace = []                 # SecureColumnByCoords per finished column
+        self._open = None
+
+    def new_col(self) -> "LogupColGenerator":
+        if self._open is not None:
+            raise ValueError("finalize_col() the previous column first")
+        self._open = LogupColGenerator(self)
+        return self._open
+
+    def finalize_last(self):
+        """(HipCircleEvaluations on CanonicCoset(log_size).circle_domain(), 4 per column, claimed sum).  Raises TstwoError
+        "0 has no inverse" when a denominator vanished on some row."""
+        if self._open is not None:
+            raise ValueError("finalize_col() the last column first")
+        if not self.trace:
+            raise ValueError("no interaction column was written")
+        L.call("tstwo_check_zero_flag")
+        claimed = logup_finalize_last(self.trace[-1], self.log_size)
+        domain = CanonicCoset(self.log_size).circleDomain()
+        return [HipCircleEvaluation(domain, c) for col in self.trace for c in col.columns], claimed
+
+    newCol = new_col
+    finalizeLast = finalize_last
+
+
+class LogupColGenerator:
+    def __init__(self, gen: LogupTraceGenerator):
+        self.gen, self.fracs = gen, []
+
+    def write_frac(self, numerator, denominator: LinearForm) -> None:
+        """numerator: an int / M31 for every row, or a HipColumn (M31); denominator: LookupElements.combine_columns(...)."""
+        if not isinstance(denominator, LinearForm):
+            raise TypeError("the denominator is a LookupElements.combine_columns(...) form")
+        if len(self.fracs) >= MAX_FRACS:
+            raise ValueError(f"at most {MAX_FRACS} fractions per column")
+        self.fracs.append((numerator, denominator))
+
+    def finalize_col(self) -> None:
+        if not self.fracs:
+            raise ValueError("a column needs at least one fraction")
+        g = self.gen
+        out = SecureColumnByCoords.uninitialized(1 << g.log_size)
+        logup_column(self.fracs, g.trace[-1] if g.trace else None, g.log_size, out)
+        g.trace.append(out)
+        g._open = None
+
+    writeFrac = write_frac
+    finalizeCol = finalize_col

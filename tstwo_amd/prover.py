@@ -41,6 +41,13 @@ class OodsNotMatching(VerificationError):
         super().__init__("The composition polynomial OODS value does not match the trace OODS values (DEEP-ALI failure).")
 
 
+class InvalidLogupSum(VerificationError):
+    """The claimed LogUp sums of the components do not add up to the expected total (Rust: the sum check of a LogUp relation)."""
+
+    def __init__(self, details: str = ""):
+        super().__init__("The claimed LogUp sums do not add up" + (f": {details}" if details else ""))
+
+
 class InvalidOodsSampleStructure(Exception):
     pass
 
@@ -72,10 +79,17 @@ def _sample_points(components: Components, oods_point: CirclePoint) -> list:
     return pts
 
 
+def _uses_logup(components) -> bool:
+    return any(getattr(c, "n_interaction_columns", 0) for c in components)
+
+
 def prove(components, channel, commitment_scheme) -> StarkProof:
-    """components: FrameworkComponents whose trace trees (preprocessed, then main) are already committed in `commitment_scheme`
-    (a CommitmentSchemeProver).  Raises ConstraintsNotSatisfied when the trace breaks a constraint."""
+    """components: FrameworkComponents whose trace trees (preprocessed, main, and the interaction tree when a component uses
+    LogUp: logup.py's caller protocol) are already committed in `commitment_scheme` (a CommitmentSchemeProver).  Raises
+    ConstraintsNotSatisfied when the trace breaks a constraint."""
     trace = Trace.of(commitment_scheme)
+    if _uses_logup(components) and len(trace.polys) != 3:
+        raise ValueError(f"LogUp components need 3 committed trace trees (preprocessed, main, interaction), not {len(trace.polys)}")
     # the preprocessed tree's width from the commitment scheme (Rust prove; the reference's prover/index.ts:606)
     provers = ComponentProvers(components, len(trace.polys[0]) if trace.polys else 0)
     random_coeff = channel.draw_felt()
@@ -93,9 +107,18 @@ def prove(components, channel, commitment_scheme) -> StarkProof:
     return proof
 
 
-def verify(components, channel, commitment_scheme_verifier, proof: StarkProof) -> None:
+def verify(components, channel, commitment_scheme_verifier, proof: StarkProof, logup_sum: QM31 = QM31.zero()) -> None:
     """components: the same component descriptions the prover used; commitment_scheme_verifier already holds the trace trees'
-    commitments (as the prover's channel saw them).  Raises OodsNotMatching, InvalidStructure or VerificationError."""
+    commitments (as the prover's channel saw them; with LogUp the interaction tree too, after the claimed sums were mixed).
+    Raises InvalidLogupSum when the LogUp components' claimed sums do not add up to logup_sum (nothing is checked without a
+    LogUp component), OodsNotMatching, InvalidStructure or VerificationError."""
+    claimed = [c.claimed_sum for c in components if getattr(c, "claimed_sum", None) is not None]
+    if claimed:
+        total = QM31.zero()
+        for v in claimed:
+            total = total.add(v)
+        if total != logup_sum:
+            raise InvalidLogupSum(f"{total} != {logup_sum}")
     sizes = commitment_scheme_verifier.column_log_sizes()
     comps = Components(components, len(sizes[0]) if sizes else 0)
     random_coeff = channel.draw_felt()
