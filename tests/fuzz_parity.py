@@ -2,7 +2,9 @@
 """Randomised GPU-vs-oracle parity sweep.  tests/test_gpu_fuzz.py runs a fixed-seed slice of it in the -m gpu suite; longer sweeps:
 python tests/fuzz_parity.py --seconds 120 [--big] on a GPU box.
 Random shapes for the CFFT entry points (in place, out of place, fused extension, many columns), Merkle trees of mixed sizes,
-folds, batch inverses, bit reversal and quotients; every result must equal the CPU oracle bit for bit."""
+folds, batch inverses, bit reversal and quotients; every result must equal the CPU oracle bit for bit.
+run(values="edge") (--values edge) draws every column, per column, as uniform words, the edge words of tests/saturation.py (E), all
+P - 1 (S) or a row mix of those with uniform words, instead of uniform words only; the default draws what it always drew."""
 import argparse
 import ctypes as C
 import os
@@ -18,6 +20,7 @@ from oracle import oracle as orc  # noqa: E402  (test infrastructure)
 from tstwo_amd import _lib as L  # noqa: E402
 import tstwo_amd as T  # noqa: E402
 from gpu_util import dev, host, p4, ptrs, vp  # noqa: E402
+from saturation import EDGE  # noqa: E402
 
 rng = np.random.default_rng(0)         # re-seeded by run()
 P = L.P
@@ -33,8 +36,41 @@ def twiddles(n):
     return _tw_cache[n]
 
 
+VALUES = "uniform"                     # set by run(): "uniform" or "edge"
+_EDGE = np.asarray(EDGE, dtype=np.uint32)
+_KINDS = ("uniform", "E", "S", "mixE", "mixS")
+_KINDS_CFFT = ("E", "mixE", "mixS")    # neither uniform nor constant (the transform of a constant column is almost all zeros)
+
+
+def _edge_col(n, lo=0, kinds=_KINDS):
+    """values="edge": n words >= lo of one kind, drawn per column"""
+    kind = kinds[int(rng.integers(0, len(kinds)))]
+    u = rng.integers(lo, P, size=n, dtype=np.uint32)
+    if kind == "uniform":
+        return u
+    fam = np.maximum(_EDGE[rng.integers(0, len(_EDGE), size=n)], lo).astype(np.uint32) if kind.endswith("E") else np.full(n, P - 1, dtype=np.uint32)
+    return np.where(rng.integers(0, 2, size=n) == 1, fam, u).astype(np.uint32) if kind.startswith("mix") else fam
+
+
 def rcol(n):
+    if VALUES == "edge":
+        return _edge_col(n)
     return rng.integers(0, P, size=n, dtype=np.uint32)
+
+
+def rcol_nonzero(n):
+    if VALUES == "edge":
+        return _edge_col(n, 1)
+    return rng.integers(1, P, size=n, dtype=np.uint32)
+
+
+def _force_cfft_column(cols):
+    """values="edge": one column that is neither uniform nor constant; its index (it joins the columns compared with the oracle)"""
+    if VALUES != "edge":
+        return None
+    c = int(rng.integers(0, len(cols)))
+    cols[c] = _edge_col(cols[c].size, 0, _KINDS_CFFT)
+    return c
 
 
 def case_cfft():
@@ -44,9 +80,12 @@ def case_cfft():
         n_cols = min(n_cols, 8)
     tw, itw, otw, oitw = twiddles(n)
     cols = [rcol(1 << n) for _ in range(n_cols)]
+    forced = _force_cfft_column(cols)
     d = [dev(c) for c in cols]
     L.call("tstwo_cfft_evaluate", ptrs(d), n_cols, n, half_odds(n - 1), vp(tw), n - 1)
     pick = rng.choice(n_cols, size=min(3, n_cols), replace=False)
+    if forced is not None and forced not in pick:
+        pick[0] = forced
     ev = {}
     for c in pick:
         ev[c] = host(d[c], 1 << n)
@@ -70,10 +109,11 @@ def case_extended():
         n_cols = min(n_cols, 4)
     tw, _, otw, _ = twiddles(n)
     polys = [rcol(1 << n_poly) for _ in range(n_cols)]
+    forced = _force_cfft_column(polys)
     src = [dev(p) for p in polys]
     out = [L.DeviceBuffer(4 << n) for _ in polys]
     L.call("tstwo_cfft_evaluate_extended", ptrs(src), n_poly, ptrs(out), n_cols, n, half_odds(n - 1), vp(tw), n - 1)
-    c = int(rng.integers(0, n_cols))
+    c = int(rng.integers(0, n_cols)) if forced is None else forced
     e = np.concatenate([polys[c], np.zeros((1 << n) - (1 << n_poly), dtype=np.uint32)])
     assert (host(out[c], 1 << n) == orc.cfft_evaluate(e, n, half_odds(n - 1), otw, n - 1)).all(), ("extended", n_poly, n, n_cols)
     return f"extended {n_poly}->{n} cols={n_cols}"
@@ -119,7 +159,7 @@ def case_fold():
 
 def case_fields():
     n = int(rng.integers(1, 100000))
-    a = rng.integers(1, P, size=n, dtype=np.uint32)
+    a = rcol_nonzero(n)
     da, do = dev(a), L.DeviceBuffer(4 * n + 16)
     L.call("tstwo_m31_batch_inverse", vp(da), vp(do), n)
     assert (host(do, n) == orc.m31_batch_inverse(a)).all(), ("m31 inverse", n)
@@ -190,7 +230,7 @@ def case_pcs():
 
 
 def _rq():
-    return tuple(int(x) for x in rng.integers(0, P, size=4))
+    return tuple(int(x) for x in (_edge_col(4) if VALUES == "edge" else rng.integers(0, P, size=4)))
 
 
 def _rand_secure_point():
@@ -249,7 +289,7 @@ def case_eval_decommit_qm31():
     T.MerkleVerifier(T.Blake2sMerkleHasher, tree.root(), logs).verify(queries, v1, d1)
     # QM31 column mul / batch inverse vs oracle
     m = int(rng.integers(1, 5000))
-    a4 = [rng.integers(1, P, size=m, dtype=np.uint32) for _ in range(4)]
+    a4 = [rcol_nonzero(m) for _ in range(4)]
     b4 = [rcol(m) for _ in range(4)]
     A, B = T.SecureColumnByCoords.from_numpy(a4), T.SecureColumnByCoords.from_numpy(b4)
     be = T.HipBackend()
@@ -297,9 +337,10 @@ def case_cfft_big():
     n_cols = int(rng.integers(1, max_cols + 1))
     tw, itw, otw, oitw = twiddles(n)
     cols = [rcol(1 << n) for _ in range(n_cols)]
+    forced = _force_cfft_column(cols)
     d = [dev(c) for c in cols]
     L.call("tstwo_cfft_evaluate", ptrs(d), n_cols, n, half_odds(n - 1), vp(tw), n - 1)
-    c = int(rng.integers(0, n_cols))
+    c = int(rng.integers(0, n_cols)) if forced is None else forced
     if n <= 18:
         assert (host(d[c], 1 << n) == orc.cfft_evaluate(cols[c], n, half_odds(n - 1), otw, n - 1)).all(), ("big evaluate", n, n_cols, c)
     out = [L.DeviceBuffer(4 << n) for _ in cols]
@@ -337,9 +378,13 @@ def case_merkle_big():
 N_GENERATORS, N_GENERATORS_BIG = 10, 2        # round-robin: that many cases = every generator ran once
 
 
-def run(seconds=60.0, seed=0, big=False, max_cases=None, verbose=True):
-    """Round-robin over the case generators until `seconds` have passed or `max_cases` ran; returns the number of cases."""
-    global rng
+def run(seconds=60.0, seed=0, big=False, max_cases=None, verbose=True, values="uniform", messages=None):
+    """Round-robin over the case generators until `seconds` have passed or `max_cases` ran; returns the number of cases.
+    values="edge": columns and scalars take edge values (see the module's text); "uniform" leaves every random draw as it was.
+    messages: a list that receives every case's message (its shapes: a record of the random draws)."""
+    global rng, VALUES
+    assert values in ("uniform", "edge")
+    VALUES = values
     rng = np.random.default_rng(seed)
     _tw_cache.clear()
     L.init(0)
@@ -353,10 +398,12 @@ def run(seconds=60.0, seed=0, big=False, max_cases=None, verbose=True):
     while time.time() - t0 < seconds and (max_cases is None or done < max_cases):
         msg = cases[done % len(cases)]()
         done += 1
+        if messages is not None:
+            messages.append(msg)
         if verbose and done % (7 if big else 501) == 0:
             print(f"[{time.time() - t0:6.1f}s] {done} cases ok (last: {msg})", flush=True)
     if verbose:
-        print(f"fuzz ok: {done} cases in {time.time() - t0:.1f}s, seed {seed}")
+        print(f"fuzz ok: {done} cases in {time.time() - t0:.1f}s, seed {seed}, values {values}")
     return done
 
 
@@ -365,5 +412,6 @@ if __name__ == "__main__":
     ap.add_argument("--seconds", type=float, default=60)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--big", action="store_true", help="only the large-size cases (tiled CFFT path, 13 <= log <= 22)")
+    ap.add_argument("--values", choices=["uniform", "edge"], default="uniform", help="edge: columns of edge words, P - 1 and row mixes")
     args = ap.parse_args()
-    run(args.seconds, args.seed, args.big)
+    run(args.seconds, args.seed, args.big, values=args.values)

@@ -16,3 +16,11 @@ def test_fuzz_slice_small_shapes():
 def test_fuzz_slice_tiled_sizes():
     import fuzz_parity
     assert fuzz_parity.run(seconds=120, seed=7, big=True, max_cases=40, verbose=False) >= fuzz_parity.N_GENERATORS_BIG
+
+
+def test_fuzz_slice_edge_values():
+    import fuzz_parity
+    # the same generators with columns of edge words, P - 1 and row mixes (tests/saturation.py) instead of uniform words only: the
+    # edge families reach the CFFT (every compared transform has a non-uniform, non-constant column), the folds, decompose,
+    # Merkle, FRI and PCS prove -> verify
+    assert fuzz_parity.run(seconds=45, seed=20261016, max_cases=1500, verbose=False, values="edge") >= fuzz_parity.N_GENERATORS
