@@ -1,5 +1,5 @@
 // microbench5.hip — Blake2s compressions on register data only (no loads): the G functions in program order (round 1's form)
-// against the priority-phased form of tstwo_amd/csrc/merkle.hip (B2S_STEP4).  What the ALUs alone allow for the Merkle kernels.
+// against the priority-phased form of tstwo_amd/csrc/blake2s.cuh (B2S_STEP4).  What the ALUs alone allow for the Merkle kernels.
 //   hipcc --offload-arch=gfx950 -O3 -I tstwo_amd/csrc -o tools/microbench5.bin.so tools/microbench5.hip && tools/microbench5.bin.so
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -212,6 +212,10 @@ int merkle_commit_then_channel(const u32 *const *cols, const u32 *log_sizes, siz
 // merkle.hip: the FRI commit's last layers (2^log0 <= 2^9 rows and below) in one single-workgroup launch
 int launch_fri_tail(u32 *const (*eval)[4], uint8_t *const *trees, u32 n_layers, u32 log0, const u32 *itw, u32 tw_log, u32 *chan, u32 *alphas,
                     const u32 *const *pre, const u32 *pre_alpha);
+// decommit.hip: the roots (digest 0 of each of the n_trees layers buffers, device memory) into host memory: one gather launch, one
+// read-back.  Hidden, unlike the older internal entries above, which are exported only because nothing ever hid them: the
+// library's dynamic symbol list is part of what callers see and does not grow for a function no caller may use.
+__attribute__((visibility("hidden"))) int download_roots(const uint8_t *const *layers, size_t n_trees, uint8_t *roots);
 // Host: describe columns [0, n_cols) of `cols` in `out`; slot 0/1 = which of the two device tables to use when a launch needs two.
 int fill_col_table(ColPtrs &out, const u32 *const *cols, size_t n_cols, int slot);
 constexpr int kMaxHashCols = 256;        // Merkle: columns absorbed per launch (multiple of 16)

@@ -1,91 +1,27 @@
-// merkle.hip — MerkleOps.commitOnLayer / MerkleProver.commit with BLAKE2s-256 (RFC 7693, unkeyed,
-// 32-byte digest — what @noble/hashes blake2s computes for the reference, vcs/blake2_hash.ts:53).
+// merkle.hip — MerkleOps.commitOnLayer / MerkleProver.commit over BLAKE2s-256 (the compression itself: blake2s.cuh).
 //
-// One lane per tree node.  Node message = [left32 || right32]? || LE32(col_0[i]) || ... || LE32(col_{C-1}[i])
-// (vcs/blake2_merkle.ts:9-24).  Column-major columns make lane i read word i of every column: one
-// coalesced 256-byte access per column per wave.  The 16 message words live in VGPRs; the 10 rounds
-// are fully unrolled so SIGMA indexes registers at compile time; rotations are v_alignbit_b32.
-// The compression is VALU-bound (~1.2k lane-ops per 64-byte block, ~19 ops/byte) — DESIGN.md §Merkle
-// prices it against the integer-issue ceiling as well as the HBM roofline the bench reports.
-// Algorithmic bytes for a layer of n nodes: 4*C*n (+ 64*n children) read, 32*n written.
+// Node message = [left32 || right32]? || LE32(col_0[i]) || ... || LE32(col_{C-1}[i]) (vcs/blake2_merkle.ts:9-24), one lane per
+// node in the wide layers: column-major columns make lane i read word i of every column, one coalesced 256-byte access per column
+// per wave.  Algorithmic bytes for a layer of n nodes: 4*C*n (+ 64*n children) read, 32*n written; the compression is VALU-bound
+// (~1.2k lane-ops per 64-byte block) — DESIGN.md §4.2 prices it against the integer-issue ceiling as well as the HBM roofline.
+//
+// Holds the layer kernels (k_merkle_layer, k_merkle_leaf_static, k_merkle_leaf4, k_merkle_inner[_set],
+// k_merkle_subtree2c); the latency path below 2^kUpLog nodes, a quad of lanes per node (k_merkle_upq, k_merkle_leaf4_upq) with
+// the channel step that can ride on a root (ChanHook, k_channel_mix_draw); the FRI commit tail (k_fri_tail) and the grind
+// (k_grind); then the host side — the ONE launch plan (launch_leaf_static, commit_column_free, commit_upper_levels under
+// commit_layer / commit_tree) and the entries built on it: tstwo_merkle_commit[_layer|_many], merkle_commit_then_channel,
+// launch_fri_tail, tstwo_channel_mix_root_draw_felt, tstwo_grind_blake2s.  Reading trees back is decommit.hip's.
 #include <string.h>
 
 #include <vector>
 
+#include "blake2s.cuh"
 #include "common.h"
-#include <stdlib.h>
 
 using namespace tstwo;
+using namespace tstwo::b2s;
 
 namespace {
-
-constexpr u32 IV0 = 0x6A09E667u, IV1 = 0xBB67AE85u, IV2 = 0x3C6EF372u, IV3 = 0xA54FF53Au, IV4 = 0x510E527Fu,
-              IV5 = 0x9B05688Cu, IV6 = 0x1F83D9ABu, IV7 = 0x5BE0CD19u;
-
-__device__ __forceinline__ u32 rotr32(u32 x, int r) { return __builtin_amdgcn_alignbit(x, x, r); }
-
-#define B2S_G(a, b, c, d, x, y)                     \
-    do {                                            \
-        a = a + b + (x); d = rotr32(d ^ a, 16);     \
-        c = c + d;       b = rotr32(b ^ c, 12);     \
-        a = a + b + (y); d = rotr32(d ^ a, 8);      \
-        c = c + d;       b = rotr32(b ^ c, 7);      \
-    } while (0)
-
-// Four independent G functions (a column step or a diagonal step of a round) issued opcode by opcode in priority phases
-// (common.h: heavy = v_add3 / v_alignbit on port 0 at high priority, light = v_xor / v_add on either port): per step
-// 24 heavy + 24 light instructions.  Entered and left at kPrioHeavy.
-#define B2S_4(OP) OP(0) OP(1) OP(2) OP(3)
-#define B2S_STEP4(a0, b0, c0, d0, a1, b1, c1, d1, a2, b2, c2, d2, a3, b3, c3, d3, x0, y0, x1, y1, x2, y2, x3, y3) \
-    do {                                                                                                          \
-        a0 = a0 + b0 + (x0); a1 = a1 + b1 + (x1); a2 = a2 + b2 + (x2); a3 = a3 + b3 + (x3);                       \
-        phase<kPrioLight>(a0, a1, a2, a3);                                                                        \
-        d0 ^= a0; d1 ^= a1; d2 ^= a2; d3 ^= a3;                                                                   \
-        phase<kPrioHeavy>(d0, d1, d2, d3);                                                                        \
-        d0 = rotr32(d0, 16); d1 = rotr32(d1, 16); d2 = rotr32(d2, 16); d3 = rotr32(d3, 16);                       \
-        phase<kPrioLight>(d0, d1, d2, d3);                                                                        \
-        c0 += d0; c1 += d1; c2 += d2; c3 += d3;                                                                   \
-        b0 ^= c0; b1 ^= c1; b2 ^= c2; b3 ^= c3;                                                                   \
-        phase<kPrioHeavy>(b0, b1, b2, b3);                                                                        \
-        b0 = rotr32(b0, 12); b1 = rotr32(b1, 12); b2 = rotr32(b2, 12); b3 = rotr32(b3, 12);                       \
-        a0 = a0 + b0 + (y0); a1 = a1 + b1 + (y1); a2 = a2 + b2 + (y2); a3 = a3 + b3 + (y3);                       \
-        phase<kPrioLight>(a0, a1, a2, a3);                                                                        \
-        d0 ^= a0; d1 ^= a1; d2 ^= a2; d3 ^= a3;                                                                   \
-        phase<kPrioHeavy>(d0, d1, d2, d3);                                                                        \
-        d0 = rotr32(d0, 8); d1 = rotr32(d1, 8); d2 = rotr32(d2, 8); d3 = rotr32(d3, 8);                           \
-        phase<kPrioLight>(d0, d1, d2, d3);                                                                        \
-        c0 += d0; c1 += d1; c2 += d2; c3 += d3;                                                                   \
-        b0 ^= c0; b1 ^= c1; b2 ^= c2; b3 ^= c3;                                                                   \
-        phase<kPrioHeavy>(b0, b1, b2, b3);                                                                        \
-        b0 = rotr32(b0, 7); b1 = rotr32(b1, 7); b2 = rotr32(b2, 7); b3 = rotr32(b3, 7);                           \
-    } while (0)
-
-// One compression (vcs/blake2s_ref.ts:176-230): h <- F(h, m, t, last)
-__device__ __forceinline__ void b2s_compress(u32 h[8], const u32 m[16], u32 t_lo, bool last) {
-    u32 v0 = h[0], v1 = h[1], v2 = h[2], v3 = h[3], v4 = h[4], v5 = h[5], v6 = h[6], v7 = h[7];
-    u32 v8 = IV0, v9 = IV1, v10 = IV2, v11 = IV3, v12 = IV4 ^ t_lo, v13 = IV5, v14 = last ? ~IV6 : IV6, v15 = IV7;
-    phase<kPrioHeavy>(v0, v1, v2, v3);
-    // message schedule SIGMA (vcs/blake2s_ref.ts:9-20) written out so every m[] index is a literal
-#define B2S_ROUND(s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15)                                    \
-    B2S_STEP4(v0, v4, v8, v12, v1, v5, v9, v13, v2, v6, v10, v14, v3, v7, v11, v15,                                         \
-              m[s0], m[s1], m[s2], m[s3], m[s4], m[s5], m[s6], m[s7]);                                                      \
-    B2S_STEP4(v0, v5, v10, v15, v1, v6, v11, v12, v2, v7, v8, v13, v3, v4, v9, v14,                                         \
-              m[s8], m[s9], m[s10], m[s11], m[s12], m[s13], m[s14], m[s15]);
-    B2S_ROUND(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
-    B2S_ROUND(14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
-    B2S_ROUND(11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4)
-    B2S_ROUND(7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8)
-    B2S_ROUND(9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13)
-    B2S_ROUND(2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9)
-    B2S_ROUND(12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11)
-    B2S_ROUND(13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10)
-    B2S_ROUND(6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5)
-    B2S_ROUND(10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0)
-#undef B2S_ROUND
-    phase<kPrioLight>(v4, v5, v6, v7);
-    h[0] ^= v0 ^ v8;  h[1] ^= v1 ^ v9;  h[2] ^= v2 ^ v10; h[3] ^= v3 ^ v11;
-    h[4] ^= v4 ^ v12; h[5] ^= v5 ^ v13; h[6] ^= v6 ^ v14; h[7] ^= v7 ^ v15;
-}
 
 struct LayerParams {
     u32 total_words;   // W: message length in 32-bit words (16 if children, plus one per column)
@@ -361,13 +297,6 @@ __global__ void __launch_bounds__(256) k_merkle_inner_set(TreeSet ts, u32 log_ou
 // and then into that node, so that a parent's message is the two digests still in registers.  The intermediate layer is
 // written once and never read back, and one launch disappears.  Both layers are written to their places in the layers buffer
 // (MerkleProver keeps all layers, vcs/prover.ts:24-29; layer k at byte offset 32*(2^k - 1)).
-struct Digest { u32 w[8]; };
-__device__ __forceinline__ Digest hash_pair(const Digest &l, const Digest &r) {
-    Digest d = {{IV0 ^ 0x01010020u, IV1, IV2, IV3, IV4, IV5, IV6, IV7}};
-    const u32 m[16] = {l.w[0], l.w[1], l.w[2], l.w[3], l.w[4], l.w[5], l.w[6], l.w[7], r.w[0], r.w[1], r.w[2], r.w[3], r.w[4], r.w[5], r.w[6], r.w[7]};
-    b2s_compress(d.w, m, 64u, true);
-    return d;
-}
 // The two-level subtree with every global access a 1 KiB-contiguous wave access (round 4).  In round 3's lane-per-subtree form a
 // lane read its four children as eight 16-byte loads at a 128-byte lane stride and wrote its digests at 64- and 32-byte lane strides: every
 // instruction touches 64 lines a piece each, the pieces of a line arrive a compression apart, and with 32 waves per CU the lines
@@ -435,143 +364,6 @@ __global__ void __launch_bounds__(256) k_merkle_subtree2c(TreeSet ts, u32 log_ch
     for (int k = 0; k < 2; k++) gstore4(up, 4u * (64u * k + lane), o2[k]);
 }
 
-// ---- Upper tree, latency path: one compression spread over a QUAD of lanes (lane j of the quad owns column j of the
-// 4x4 Blake2s state).  The column step is lane-local; the diagonal step rotates rows b, c, d by 1, 2, 3 lanes with DPP
-// quad_perm moves and rotates them back.  A lane needs message words m[SIGMA[r][2j..]], i.e. a lane-dependent choice
-// among registers that are literal per round: three v_cndmask on the constant lane masks j==1, j==2, j==3.
-// ~1/2.4 of the dependent-instruction chain of the one-lane compression, which is what bounds the top of a tree.
-__device__ __forceinline__ u32 quad_rot(u32 x, int by) {   // value held by lane (j + by) & 3 of this lane's quad
-    return by == 1 ? (u32)__builtin_amdgcn_mov_dpp((int)x, 0x39, 0xF, 0xF, false)
-         : by == 2 ? (u32)__builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xF, 0xF, false)
-                   : (u32)__builtin_amdgcn_mov_dpp((int)x, 0x93, 0xF, 0xF, false);
-}
-__device__ __forceinline__ u32 sel4(u32 x0, u32 x1, u32 x2, u32 x3, u32 j) {
-    u32 r = x0;
-    r = j == 1 ? x1 : r;
-    r = j == 2 ? x2 : r;
-    r = j == 3 ? x3 : r;
-    return r;
-}
-// Single 64-byte final block from the initial state (a node of children only: hashNode, vcs/blake2_merkle.ts:9-24).
-// Returns the digest words j (o_lo) and 4+j (o_hi) in lane j of the quad.
-__device__ __forceinline__ void b2s_quad_block64(const u32 (&m)[16], u32 j, u32 &o_lo, u32 &o_hi) {
-    const u32 ivlo = sel4(IV0, IV1, IV2, IV3, j), ivhi = sel4(IV4, IV5, IV6, IV7, j);
-    const u32 h_lo = ivlo ^ (j == 0 ? 0x01010020u : 0u), h_hi = ivhi;
-    u32 a = h_lo, b = h_hi, c = ivlo, d = ivhi ^ sel4(64u, 0u, 0xFFFFFFFFu, 0u, j);
-#define B2SQ_ROUND(s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15)          \
-    {                                                                                            \
-        u32 x = sel4(m[s0], m[s2], m[s4], m[s6], j), y = sel4(m[s1], m[s3], m[s5], m[s7], j);     \
-        B2S_G(a, b, c, d, x, y);                                                                  \
-        b = quad_rot(b, 1); c = quad_rot(c, 2); d = quad_rot(d, 3);                               \
-        x = sel4(m[s8], m[s10], m[s12], m[s14], j); y = sel4(m[s9], m[s11], m[s13], m[s15], j);   \
-        B2S_G(a, b, c, d, x, y);                                                                  \
-        b = quad_rot(b, 3); c = quad_rot(c, 2); d = quad_rot(d, 1);                               \
-    }
-    B2SQ_ROUND(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
-    B2SQ_ROUND(14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
-    B2SQ_ROUND(11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4)
-    B2SQ_ROUND(7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8)
-    B2SQ_ROUND(9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13)
-    B2SQ_ROUND(2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9)
-    B2SQ_ROUND(12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11)
-    B2SQ_ROUND(13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10)
-    B2SQ_ROUND(6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5)
-    B2SQ_ROUND(10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0)
-#undef B2SQ_ROUND
-    o_lo = h_lo ^ a ^ c;
-    o_hi = h_hi ^ b ^ d;
-}
-
-// The same with the message in LDS instead of registers: lane j of the quad reads its words of round r — m[SIGMA[r][2j]],
-// m[SIGMA[r][2j+1]] for the column step, m[SIGMA[r][8+2j]], m[SIGMA[r][8+2j+1]] for the diagonal step — from 40 LDS byte addresses
-// it computed ONCE (quad_msg_addrs: the quad's message slot does not move between tree levels).  40 ds_read_b32 per compression
-// instead of 120 v_cndmask (the three selects per word above): a third fewer issue slots on a path where one wave issues alone.
-typedef __attribute__((address_space(3))) const u32 lds_cu32;
-struct QuadMsgAddrs { u32 a[40]; };
-__device__ __forceinline__ void quad_msg_addrs(QuadMsgAddrs &qa, u32 msg_byte_base, u32 j) {
-#define B2SQ_ADDR(r, s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15)                   \
-    qa.a[4 * r + 0] = msg_byte_base + sel4(4u * s0, 4u * s2, 4u * s4, 4u * s6, j);                             \
-    qa.a[4 * r + 1] = msg_byte_base + sel4(4u * s1, 4u * s3, 4u * s5, 4u * s7, j);                             \
-    qa.a[4 * r + 2] = msg_byte_base + sel4(4u * s8, 4u * s10, 4u * s12, 4u * s14, j);                          \
-    qa.a[4 * r + 3] = msg_byte_base + sel4(4u * s9, 4u * s11, 4u * s13, 4u * s15, j);
-    B2SQ_ADDR(0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
-    B2SQ_ADDR(1, 14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
-    B2SQ_ADDR(2, 11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4)
-    B2SQ_ADDR(3, 7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8)
-    B2SQ_ADDR(4, 9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13)
-    B2SQ_ADDR(5, 2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9)
-    B2SQ_ADDR(6, 12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11)
-    B2SQ_ADDR(7, 13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10)
-    B2SQ_ADDR(8, 6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5)
-    B2SQ_ADDR(9, 10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0)
-#undef B2SQ_ADDR
-}
-__device__ __forceinline__ u32 lds_word(u32 byte_addr) { return *(lds_cu32 *)(uintptr_t)byte_addr; }
-__device__ __forceinline__ void b2s_quad_block64_lds(const QuadMsgAddrs &qa, u32 j, u32 &o_lo, u32 &o_hi) {
-    const u32 ivlo = sel4(IV0, IV1, IV2, IV3, j), ivhi = sel4(IV4, IV5, IV6, IV7, j);
-    const u32 h_lo = ivlo ^ (j == 0 ? 0x01010020u : 0u), h_hi = ivhi;
-    u32 a = h_lo, b = h_hi, c = ivlo, d = ivhi ^ sel4(64u, 0u, 0xFFFFFFFFu, 0u, j);
-    u32 w[40];
-#pragma unroll
-    for (int k = 0; k < 40; k++) w[k] = lds_word(qa.a[k]);
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        B2S_G(a, b, c, d, w[4 * r], w[4 * r + 1]);
-        b = quad_rot(b, 1); c = quad_rot(c, 2); d = quad_rot(d, 3);
-        B2S_G(a, b, c, d, w[4 * r + 2], w[4 * r + 3]);
-        b = quad_rot(b, 3); c = quad_rot(c, 2); d = quad_rot(d, 1);
-    }
-    o_lo = h_lo ^ a ^ c;
-    o_hi = h_hi ^ b ^ d;
-}
-
-// ---- Blake2sChannel on the device (channel/blake2.ts:25-224, Rust semantics).  State = 10 words: digest[8], n_challenges,
-// n_sent.  One quad of lanes runs the (latency-bound) compressions; used by the FRI commit loop so that a layer's root
-// never has to travel to the host before the next fold can be launched.
-__device__ __forceinline__ void chan_hash64(const u32 (&m)[16], u32 j, u32 (&digest)[8]) {
-    u32 lo, hi;
-    b2s_quad_block64(m, j, lo, hi);
-    // every lane of the quad needs the whole digest: word k lives in lane k & 3 (lo for k < 4, hi for k >= 4)
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        digest[k] = (u32)__builtin_amdgcn_readlane((int)lo, k);
-        digest[4 + k] = (u32)__builtin_amdgcn_readlane((int)hi, k);
-    }
-}
-// mix_root (vcs/blake2_merkle.ts:28-31): digest <- H(digest || root), n_challenges += 1, n_sent <- 0; then (optionally)
-// draw_felt (blake2.ts:158-184): H(digest || LE32(n_sent) || 0^28) until all 8 words < 2P; felt = first 4 words reduced.
-// state in registers of every lane of a wave (d, n_chal, n_sent); root: 8 words (global or LDS); felt: the drawn QM31 (valid in
-// every lane).  Executed by one whole wave (chan_hash64 broadcasts through readlane of lanes 0..3).
-__device__ __forceinline__ void chan_mix_draw(u32 (&d)[8], u32 &n_chal, u32 &n_sent, const u32 *root, bool do_mix, bool do_draw, u32 (&felt)[4]) {
-    const u32 j = threadIdx.x & 3;
-    if (do_mix) {
-        u32 m[16];
-#pragma unroll
-        for (int k = 0; k < 8; k++) { m[k] = d[k]; m[8 + k] = root[k]; }
-        chan_hash64(m, j, d);
-        n_chal += 1;
-        n_sent = 0;
-    }
-    if (do_draw) {
-        u32 w[8];
-        bool ok = false;
-        // retry probability per round ~ 2^-28; the loop is bounded so that the kernel always terminates (64 rejections in a
-        // row have probability 2^-1792)
-        for (int tries = 0; tries < 64 && !ok; tries++) {
-            u32 m[16];
-#pragma unroll
-            for (int k = 0; k < 8; k++) { m[k] = d[k]; m[8 + k] = 0; }
-            m[8] = n_sent;
-            n_sent += 1;
-            chan_hash64(m, j, w);
-            ok = true;
-#pragma unroll
-            for (int k = 0; k < 8; k++) ok = ok && (w[k] < 2u * M31_P);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) felt[k] = w[k] >= M31_P ? w[k] - M31_P : w[k];       // M31.reduce of a value < 2P
-    }
-}
 // Levels log_child-1 .. log_child-levels, 4 lanes per node: a workgroup of WG lanes owns WG/4 consecutive parents of the
 // first level and everything above them (WG/4 -> 1 is log2(WG/4)+1 levels).  Children digests live in LDS between levels.
 // the level loop shared by k_merkle_upq and k_merkle_leaf4_upq: `sh` holds the 2*active child digests of this workgroup
@@ -635,6 +427,18 @@ __global__ void __launch_bounds__(WG) k_merkle_upq(TreeSet ts, u32 log_child, u3
     upq_levels<WG>(layers, sh, log_child, levels, active, blockIdx.x);
     if (log_child == levels) chan_step_from_lds(hk, sh);          // this launch reached layer 0: the root is sh[0..7]
 }
+// One leaf of a 4-column tree (a 16-byte message, vcs/blake2_merkle.ts:9-24): hashed, written to the leaf layer (node `node` of
+// layer log_leaf) and to LDS as child digest `slot` of the quad levels that follow.
+__device__ __forceinline__ void leaf4_to_lds(uint4 *layers, u32 log_leaf, size_t node, u32 *sh, u32 slot, u32 m0, u32 m1, u32 m2, u32 m3) {
+    u32 h[8] = {IV0 ^ 0x01010020u, IV1, IV2, IV3, IV4, IV5, IV6, IV7};
+    const u32 m[16] = {m0, m1, m2, m3, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    b2s_compress(h, m, 16u, true);
+    uint4 *leaf = layers + 2 * ((((size_t)1 << log_leaf) - 1) + node);
+    const uint4 lo = make_uint4(h[0], h[1], h[2], h[3]), hi = make_uint4(h[4], h[5], h[6], h[7]);
+    leaf[0] = lo; leaf[1] = hi;
+    reinterpret_cast<uint4 *>(sh)[2 * slot] = lo;
+    reinterpret_cast<uint4 *>(sh)[2 * slot + 1] = hi;
+}
 // A small 4-column tree (every FRI layer below 2^17 rows) without a launch of its own for the leaves: the first 2*active lanes
 // of the workgroup hash one leaf each (16-byte message, vcs/blake2_merkle.ts:9-24), write it to the leaf layer and to LDS,
 // and the quad levels follow in the same launch.
@@ -647,7 +451,6 @@ __global__ void __launch_bounds__(WG) k_merkle_leaf4_upq(u32 *__restrict__ c0, u
     const u32 active = min(Q, 1u << (log_leaf - 1));              // parents of the first level in this workgroup
     if (t < 2 * active) {
         const size_t node = (size_t)blockIdx.x * (2 * active) + t;
-        u32 h[8] = {IV0 ^ 0x01010020u, IV1, IV2, IV3, IV4, IV5, IV6, IV7};
         u32 m0, m1, m2, m3;
         if (FOLD) {
             const qm31 r = fold_row(fold_row_load(fs, node), {fs.alpha[0], fs.alpha[1], fs.alpha[2], fs.alpha[3]});
@@ -656,13 +459,7 @@ __global__ void __launch_bounds__(WG) k_merkle_leaf4_upq(u32 *__restrict__ c0, u
         } else {
             m0 = c0[node]; m1 = c1[node]; m2 = c2[node]; m3 = c3[node];
         }
-        const u32 m[16] = {m0, m1, m2, m3, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        b2s_compress(h, m, 16u, true);
-        uint4 *leaf = layers + 2 * ((((size_t)1 << log_leaf) - 1) + node);
-        const uint4 lo = make_uint4(h[0], h[1], h[2], h[3]), hi = make_uint4(h[4], h[5], h[6], h[7]);
-        leaf[0] = lo; leaf[1] = hi;
-        reinterpret_cast<uint4 *>(sh)[2 * t] = lo;
-        reinterpret_cast<uint4 *>(sh)[2 * t + 1] = hi;
+        leaf4_to_lds(layers, log_leaf, node, sh, t, m0, m1, m2, m3);
     }
     __syncthreads();
     upq_levels<WG>(layers, sh, log_leaf, levels, active, blockIdx.x);
@@ -707,11 +504,6 @@ int commit_upper_levels(TreeSet ts, unsigned n_trees, u32 log_child, u32 log_sto
     }
     TSTWO_LAUNCH_CHECK();
     return TSTWO_OK;
-}
-int commit_upper_levels(uint8_t *layers, u32 log_child, u32 log_stop, ChanHook *hook) {
-    TreeSet one = {};
-    one.t[0] = (uint4 *)layers;
-    return commit_upper_levels(one, 1, log_child, log_stop, hook);
 }
 
 __global__ void __launch_bounds__(64) k_channel_mix_draw(u32 *__restrict__ chan, const u32 *__restrict__ root, u32 *__restrict__ felt,
@@ -788,16 +580,7 @@ __global__ void __launch_bounds__(1024) k_fri_tail(FriTail ft, const u32 *__rest
         // the fold's x^-1 of this layer: requested now, used behind the tree and the channel step
         const u32 tw = t < active ? gload1(itw + ((size_t)1 << tw_log) - ((size_t)1 << lg) + t) : 0u;
         // tree over the 4 coordinate columns (vcs/blake2_merkle.ts:9-24): leaves, then all levels
-        if (t < 2 * active) {
-            u32 h[8] = {IV0 ^ 0x01010020u, IV1, IV2, IV3, IV4, IV5, IV6, IV7};
-            const u32 m[16] = {row[0], row[1], row[2], row[3], 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            b2s_compress(h, m, 16u, true);
-            uint4 *leaf = layers + 2 * ((((size_t)1 << lg) - 1) + t);
-            const uint4 lo = make_uint4(h[0], h[1], h[2], h[3]), hi = make_uint4(h[4], h[5], h[6], h[7]);
-            leaf[0] = lo; leaf[1] = hi;
-            reinterpret_cast<uint4 *>(sh)[2 * t] = lo;
-            reinterpret_cast<uint4 *>(sh)[2 * t + 1] = hi;
-        }
+        if (t < 2 * active) leaf4_to_lds(layers, lg, t, sh, t, row[0], row[1], row[2], row[3]);
         lds_only_barrier();
         upq_levels<1024>(layers, sh, lg, lg, active, 0u);            // the root is in sh[0..7] afterwards
         // channel: mix the root, draw alpha (wave 0; channel/blake2.ts:115-184, Rust draw semantics)
@@ -836,14 +619,6 @@ __global__ void __launch_bounds__(1024) k_fri_tail(FriTail ft, const u32 *__rest
     }
 }
 
-struct GatherItem { const u32 *src; unsigned long long idx; };
-__global__ void __launch_bounds__(256) k_gather_words(const GatherItem *__restrict__ items, u32 words, size_t total, u32 *__restrict__ out) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const size_t item = i / words, w = i % words;
-    out[i] = items[item].src[items[item].idx * words + w];
-}
-
 // Proof-of-work grind: lane i of a batch tests nonce base + i; digest' = Blake2s(digest || LE64(nonce)) is one 40-byte block.
 struct GrindDigest { u32 w[8]; };
 __global__ void __launch_bounds__(256) k_grind(GrindDigest d, u32 pow_bits, unsigned long long base, unsigned long long count,
@@ -863,33 +638,65 @@ __global__ void __launch_bounds__(256) k_grind(GrindDigest d, u32 pow_bits, unsi
     if (tz >= pow_bits) atomicMin(best, nonce);
 }
 
+// Workgroups of a one-lane-per-node launch over n_nodes nodes of each of n_trees trees: at most merkle_cap per CU, then lanes
+// grid-stride over more nodes; a set of trees has the same lanes in flight as one tree's launch.
+unsigned layer_blocks(size_t n_nodes, unsigned n_trees) {
+    const unsigned blocks = ceil_div(n_nodes, 256);
+    const unsigned cap = (unsigned)ctx().n_cus * (unsigned)knobs().merkle_cap / n_trees;
+    return blocks <= cap ? blocks : cap ? cap : 1;
+}
+
+// The leaf layer (2^log_size nodes at leaf.t[tree]) of n_trees >= 1 trees of cols_per_tree = 16 / 32 / 48 / 64 columns each, tree
+// after tree in hp.
+int launch_leaf_static(const HashColPtrs &hp, size_t cols_per_tree, const TreeSet &leaf, unsigned n_trees, u32 log_size) {
+    const size_t n_nodes = (size_t)1 << log_size;
+    const dim3 grid(layer_blocks(n_nodes, n_trees), n_trees);
+    hipStream_t stream = ctx().stream;
+    switch (cols_per_tree / 16) {
+        case 1: hipLaunchKernelGGL(k_merkle_leaf_static<1>, grid, dim3(256), 0, stream, hp, leaf, n_nodes); break;
+        case 2: hipLaunchKernelGGL(k_merkle_leaf_static<2>, grid, dim3(256), 0, stream, hp, leaf, n_nodes); break;
+        case 3: hipLaunchKernelGGL(k_merkle_leaf_static<3>, grid, dim3(256), 0, stream, hp, leaf, n_nodes); break;
+        default: hipLaunchKernelGGL(k_merkle_leaf_static<4>, grid, dim3(256), 0, stream, hp, leaf, n_nodes); break;
+    }
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
+}
+
+// Column-free layers log_child-1 .. log_stop of every tree of a set, the launch plan of every tree above its columns: layers of
+// at least 2^kUpLog nodes two per launch (k_merkle_subtree2c; measured for 32 x 2^22: 0.308 ms, against 0.313 for one launch per
+// layer and 0.326 / 0.332 for runs of 3 / 4 layers), a single leftover one on its own, the smaller ones by commit_upper_levels
+// (which also takes `hook`).
+int commit_column_free(const TreeSet &ts, unsigned n_trees, u32 log_child, u32 log_stop, ChanHook *hook) {
+    hipStream_t stream = ctx().stream;
+    for (; log_child >= log_stop + 2 && log_child - 2 >= (u32)kUpLog; log_child -= 2) {
+        const size_t tops = (size_t)1 << (log_child - 2);           // >= 2^kUpLog nodes: whole k_merkle_subtree2c workgroups
+        hipLaunchKernelGGL(k_merkle_subtree2c, dim3((unsigned)(tops / 256), n_trees), dim3(256), 0, stream, ts, log_child);
+    }
+    if (log_child > log_stop && log_child - 1 >= (u32)kUpLog) {
+        log_child -= 1;
+        hipLaunchKernelGGL(k_merkle_inner_set, dim3(layer_blocks((size_t)1 << log_child, n_trees), n_trees), dim3(256), 0, stream, ts, log_child);
+    }
+    TSTWO_LAUNCH_CHECK();
+    return commit_upper_levels(ts, n_trees, log_child, log_stop, hook);
+}
+
 // fold (null: none): the 4 columns of a leaf layer are first written as the fold it describes, inside the leaf launch.
 int commit_layer(u32 log_size, const uint8_t *prev, const u32 *const *cols, size_t n_cols, uint8_t *out, const FoldSpec *fold) {
     Context &c = ctx();
     if (log_size > 31) return set_error(TSTWO_ERR_BAD_ARG, "merkle: log size out of range");
     if (!out) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null output layer");
-    if ((((uintptr_t)out) & 15) || (((uintptr_t)prev) & 15)) return set_error(TSTWO_ERR_BAD_ARG, "merkle: layers must be 16-byte aligned");
+    if (!aligned16(out) || !aligned16(prev)) return set_error(TSTWO_ERR_BAD_ARG, "merkle: layers must be 16-byte aligned");
     if (fold && (prev || log_size > 30 || n_cols != 4)) return set_error(TSTWO_ERR_HIP, "fri commit: the fold was not carried by the leaf launch");
     const size_t n_nodes = (size_t)1 << log_size;
     const u32 child_words = prev ? 16u : 0u;
     const u32 W = child_words + (u32)n_cols;
-    unsigned blocks = ceil_div(n_nodes, 256);
-    const unsigned cap_mult = (unsigned)knobs().merkle_cap;
-    const unsigned cap = (unsigned)c.n_cus * cap_mult;     // workgroups per CU before lanes grid-stride over more nodes
-    if (blocks > cap) blocks = cap;
+    const unsigned blocks = layer_blocks(n_nodes, 1);
     if (!prev && log_size <= 30 && (n_cols == 16 || n_cols == 32 || n_cols == 48 || n_cols == 64)) {
         HashColPtrs hp;
         for (size_t k = 0; k < n_cols; k++) hp.p[k] = cols[k];
         TreeSet one = {};
         one.t[0] = (uint4 *)out;
-        switch (n_cols / 16) {
-            case 1: hipLaunchKernelGGL(k_merkle_leaf_static<1>, dim3(blocks), dim3(256), 0, c.stream, hp, one, n_nodes); break;
-            case 2: hipLaunchKernelGGL(k_merkle_leaf_static<2>, dim3(blocks), dim3(256), 0, c.stream, hp, one, n_nodes); break;
-            case 3: hipLaunchKernelGGL(k_merkle_leaf_static<3>, dim3(blocks), dim3(256), 0, c.stream, hp, one, n_nodes); break;
-            default: hipLaunchKernelGGL(k_merkle_leaf_static<4>, dim3(blocks), dim3(256), 0, c.stream, hp, one, n_nodes); break;
-        }
-        TSTWO_LAUNCH_CHECK();
-        return TSTWO_OK;
+        return launch_leaf_static(hp, n_cols, one, 1, log_size);
     }
     if (!prev && log_size <= 30 && n_cols == 4) {
         u32 *w0 = const_cast<u32 *>(cols[0]), *w1 = const_cast<u32 *>(cols[1]), *w2 = const_cast<u32 *>(cols[2]), *w3 = const_cast<u32 *>(cols[3]);
@@ -909,11 +716,9 @@ int commit_layer(u32 log_size, const uint8_t *prev, const u32 *const *cols, size
     size_t col_base = 0;
     bool first = true;
     do {
-        size_t avail = n_cols - col_base;
-        size_t take = avail;
+        size_t take = n_cols - col_base;
         // words available to this launch must end on a block boundary unless it is the final launch
-        size_t max_cols = first && prev ? (size_t)kMaxHashCols : (size_t)kMaxHashCols;
-        if (take > max_cols) take = max_cols;
+        if (take > (size_t)kMaxHashCols) take = kMaxHashCols;
         bool final_launch = (col_base + take == n_cols);
         if (!final_launch) {
             // make (child_words + col_base + take) a multiple of 16
@@ -956,27 +761,30 @@ int commit_tree(const u32 *const *cols, const u32 *log_sizes, size_t n_cols, uin
         if (log_sizes[i] > 31) return set_error(TSTWO_ERR_BAD_ARG, "merkle: log size out of range");
         if (log_sizes[i] > max_log) max_log = log_sizes[i];
     }
+    const auto has_cols = [&](u32 lg) {
+        for (size_t i = 0; i < n_cols; i++)
+            if (log_sizes[i] == lg) return true;
+        return false;
+    };
+    TreeSet one = {};
+    one.t[0] = (uint4 *)layers;
     // a tree of exactly 4 equally long columns with at most 2^kUpLog rows (every FRI layer but the first few): leaves and the
     // first 7 (or all, below 2^10 rows) levels in one launch
     if (n_cols == 4 && max_log >= 1 && (int)max_log <= kUpLog && log_sizes[0] == max_log && log_sizes[1] == max_log && log_sizes[2] == max_log &&
         log_sizes[3] == max_log) {
-        Context &c = ctx();
-        u32 log_child = max_log;
         u32 *w0 = const_cast<u32 *>(cols[0]), *w1 = const_cast<u32 *>(cols[1]), *w2 = const_cast<u32 *>(cols[2]), *w3 = const_cast<u32 *>(cols[3]);
         const FoldSpec fs = fold ? *fold : FoldSpec{};
-        if (max_log <= 9) {
-            const ChanHook hk = hook ? *hook : ChanHook{nullptr, nullptr};
-            if (fold) hipLaunchKernelGGL((k_merkle_leaf4_upq<1024, true>), dim3(1), dim3(1024), 0, c.stream, w0, w1, w2, w3, (uint4 *)layers, max_log, max_log, hk, fs);
-            else hipLaunchKernelGGL((k_merkle_leaf4_upq<1024, false>), dim3(1), dim3(1024), 0, c.stream, w0, w1, w2, w3, (uint4 *)layers, max_log, max_log, hk, fs);
-            if (hook) *hook = {nullptr, nullptr};
-            log_child = 0;
-        } else {
-            if (fold) hipLaunchKernelGGL((k_merkle_leaf4_upq<256, true>), dim3(1u << (max_log - 7)), dim3(256), 0, c.stream, w0, w1, w2, w3, (uint4 *)layers, max_log, 7u, ChanHook{nullptr, nullptr}, fs);
-            else hipLaunchKernelGGL((k_merkle_leaf4_upq<256, false>), dim3(1u << (max_log - 7)), dim3(256), 0, c.stream, w0, w1, w2, w3, (uint4 *)layers, max_log, 7u, ChanHook{nullptr, nullptr}, fs);
-            log_child = max_log - 7;
-        }
+        // up to 2^9 rows: one workgroup of 256 quads takes the whole tree and the channel step; above: 64 quads, 7 levels each
+        const bool whole = max_log <= 9;
+        const u32 levels = whole ? max_log : 7u;
+        const ChanHook hk = whole && hook ? *hook : ChanHook{nullptr, nullptr};
+        const auto kernel = whole ? (fold ? k_merkle_leaf4_upq<1024, true> : k_merkle_leaf4_upq<1024, false>)
+                                  : (fold ? k_merkle_leaf4_upq<256, true> : k_merkle_leaf4_upq<256, false>);
+        hipLaunchKernelGGL(kernel, dim3(1u << (max_log - levels)), dim3(whole ? 1024 : 256), 0, ctx().stream, w0, w1, w2, w3, (uint4 *)layers,
+                           max_log, levels, hk, fs);
         TSTWO_LAUNCH_CHECK();
-        int rc = log_child ? commit_upper_levels(layers, log_child, 0, hook) : TSTWO_OK;
+        if (whole && hook) *hook = {nullptr, nullptr};
+        int rc = whole ? TSTWO_OK : commit_upper_levels(one, 1, max_log - levels, 0, hook);
         if (rc) return rc;
         if (root) return small_d2h(root, layers, 32);
         return TSTWO_OK;
@@ -991,36 +799,14 @@ int commit_tree(const u32 *const *cols, const u32 *log_sizes, size_t n_cols, uin
             if (log_sizes[i] == (u32)lg) lc[k++] = cols[i];
         uint8_t *dst = layers + 32 * (((size_t)1 << lg) - 1);
         // layer k starts at 32*(2^k-1): 16-byte aligned for every k >= 0 when `layers` is
-        if (k == 0 && prev != nullptr && lg < kUpLog) {
-            // a run of column-free layers below lg+1: fuse them (stop above the next layer that has columns)
+        if (k == 0 && prev != nullptr) {
+            // a run of column-free layers below lg+1: one launch plan for all of them (stop above the next layer that has columns)
             int stop = lg;
-            while (stop > 0) {
-                bool has = false;
-                for (size_t i = 0; i < n_cols; i++) has = has || log_sizes[i] == (u32)(stop - 1);
-                if (has) break;
-                stop--;
-            }
-            rc = commit_upper_levels(layers, (u32)lg + 1, (u32)stop, hook);
+            while (stop > 0 && !has_cols((u32)stop - 1)) stop--;
+            rc = commit_column_free(one, 1, (u32)lg + 1, (u32)stop, hook);
             prev = layers + 32 * (((size_t)1 << stop) - 1);
             lg = stop - 1;
             continue;
-        }
-        if (k == 0 && prev != nullptr) {
-            // two column-free layers at or above 2^kUpLog nodes: one in-lane subtree launch for both (measured for 32 x 2^22:
-            // 0.308 ms, against 0.313 for one launch per layer and 0.326 / 0.332 for runs of 3 / 4 layers)
-            bool pair = lg - 1 >= kUpLog;
-            for (size_t i = 0; i < n_cols; i++) pair = pair && log_sizes[i] != (u32)(lg - 1);
-            if (pair) {
-                const size_t tops = (size_t)1 << (lg - 1);          // >= 2^kUpLog nodes: whole k_merkle_subtree2c workgroups
-                Context &c = ctx();
-                TreeSet one = {};
-                one.t[0] = (uint4 *)layers;
-                hipLaunchKernelGGL(k_merkle_subtree2c, dim3((unsigned)(tops / 256)), dim3(256), 0, c.stream, one, (u32)lg + 1);
-                if (hipGetLastError() != hipSuccess) rc = set_error(TSTWO_ERR_HIP, "merkle: subtree kernel launch failed");
-                lg -= 2;
-                prev = layers + 32 * (((size_t)1 << (lg + 1)) - 1);
-                continue;
-            }
         }
         rc = commit_layer((u32)lg, prev, lc, k, dst, prev ? nullptr : fold);      // the leaf layer carries the fold
         prev = dst;
@@ -1103,268 +889,6 @@ int tstwo_grind_blake2s(const uint8_t digest[32], u32 pow_bits, uint64_t start_n
     }
 }
 
-int tstwo_gather_words(const void *const *srcs, const uint64_t *idx, u32 words, size_t n_items, u32 *host_out) {
-    TSTWO_REQUIRE_READY();
-    if (n_items == 0 || words == 0) return TSTWO_OK;
-    if (!srcs || !idx || !host_out) return set_error(TSTWO_ERR_BAD_ARG, "gather: null argument");
-    Context &c = ctx();
-    const size_t total = n_items * words;
-    const size_t items_bytes = ((n_items * sizeof(GatherItem) + 63) / 64) * 64;
-    int rc = ensure_scratch(items_bytes + total * sizeof(u32));
-    if (rc) return rc;
-    GatherItem *h = new GatherItem[n_items];
-    for (size_t i = 0; i < n_items; i++) { h[i].src = (const u32 *)srcs[i]; h[i].idx = idx[i]; }
-    rc = small_h2d(c.scratch, h, n_items * sizeof(GatherItem));     // stream-ordered behind whatever still reads the scratch
-    delete[] h;
-    if (rc) return rc;
-    u32 *const page = (u32 *)result_target(total * sizeof(u32));
-    u32 *d_out = page ? page : (u32 *)((unsigned char *)c.scratch + items_bytes);
-    hipLaunchKernelGGL(k_gather_words, dim3(ceil_div(total, 256)), dim3(256), 0, c.stream, (const GatherItem *)c.scratch, words, total, d_out);
-    TSTWO_LAUNCH_CHECK();
-    if (page) {
-        const void *view = nullptr;
-        rc = result_wait(&view);
-        if (rc) return rc;
-        memcpy(host_out, view, total * sizeof(u32));
-        return TSTWO_OK;
-    }
-    return small_d2h(host_out, d_out, total * sizeof(u32));
-}
-
-// MerkleProver.decommit (vcs/prover.ts:32-109) against device-resident layers and columns: the walk over the layers
-// (which nodes are visited, which child digests / column values the verifier cannot recompute) runs here on the host
-// side of the library; the selected words are then fetched with two gathers.
-// The walk of one tree (vcs/prover.ts:32-109): appends the requests to the shared lists.
-struct DecommitLists {
-    std::vector<GatherItem> hashes, queried, witness;      // (device base, element index); digests are 8 words, values 1
-};
-static int plan_decommit(const uint8_t *layers, u32 max_log, const u32 *const *cols, const u32 *col_log_sizes, size_t n_cols,
-                         const u32 *query_logs, const uint64_t *const *queries, const size_t *n_queries, size_t n_query_sets,
-                         DecommitLists &out) {
-    if (!layers || (n_cols && (!cols || !col_log_sizes)) || (n_query_sets && (!query_logs || !queries || !n_queries)))
-        return set_error(TSTWO_ERR_BAD_ARG, "merkle decommit: null argument");
-    if (max_log > 31) return set_error(TSTWO_ERR_BAD_ARG, "merkle: log size out of range");
-    TSTWO_REQUIRE_TABLE(cols, n_cols);
-    for (size_t i = 0; i < n_cols; i++)
-        if (col_log_sizes[i] > max_log) return set_error(TSTWO_ERR_BAD_ARG, "merkle decommit: column larger than the tree");
-    std::vector<uint64_t> last, cur;
-    for (int lg = (int)max_log; lg >= 0; lg--) {
-        const uint64_t *direct = nullptr;
-        size_t nd = 0;
-        for (size_t k = 0; k < n_query_sets; k++)
-            if (query_logs[k] == (u32)lg) { direct = queries[k]; nd = n_queries[k]; }
-        if (nd && !direct) return set_error(TSTWO_ERR_BAD_ARG, "merkle decommit: null argument");
-        for (size_t k = 0; k < nd; k++)
-            if (direct[k] >> lg) return set_error(TSTWO_ERR_BAD_ARG, "merkle decommit: query position outside its layer");
-        const bool has_child = (u32)lg < max_log;
-        const u32 *child_layer = has_child ? (const u32 *)(layers + 32 * (((size_t)1 << (lg + 1)) - 1)) : nullptr;
-        size_t pi = 0, di = 0;
-        cur.clear();
-        for (;;) {
-            bool any = false;
-            uint64_t node = 0;
-            if (pi < last.size()) { node = last[pi] >> 1; any = true; }
-            if (di < nd && (!any || direct[di] < node)) { node = direct[di]; any = true; }
-            if (!any) break;
-            if (has_child)
-                for (uint64_t k = 2 * node; k <= 2 * node + 1; k++) {
-                    if (pi < last.size() && last[pi] == k) pi++;
-                    else out.hashes.push_back({child_layer, k});
-                }
-            const bool queried = di < nd && direct[di] == node;
-            if (queried) di++;
-            for (size_t i = 0; i < n_cols; i++)          // columns of this layer, in the caller's order (stable sort by size)
-                if (col_log_sizes[i] == (u32)lg) (queried ? out.queried : out.witness).push_back({cols[i], node});
-            cur.push_back(node);
-        }
-        last.swap(cur);
-    }
-    return TSTWO_OK;
-}
-
-// One upload of all request items, two launches (8-word digests, 1-word column values), one read-back.
-// (the last n_extra entries of l.hashes go to `extra` instead of hash_witness: the roots of a FRI proof's trees)
-static int run_decommit(const DecommitLists &l, u32 *queried_values, uint8_t *hash_witness, u32 *column_witness, size_t n_extra = 0,
-                        uint8_t *extra = nullptr) {
-    const size_t nh = l.hashes.size(), nq = l.queried.size(), nw = l.witness.size(), nv = nq + nw;
-    if (nh + nv == 0) return TSTWO_OK;
-    Context &c = ctx();
-    std::vector<GatherItem> items;
-    items.reserve(nh + nv);
-    items.insert(items.end(), l.hashes.begin(), l.hashes.end());
-    items.insert(items.end(), l.queried.begin(), l.queried.end());
-    items.insert(items.end(), l.witness.begin(), l.witness.end());
-    const size_t items_bytes = ((items.size() * sizeof(GatherItem) + 63) / 64) * 64;
-    const size_t out_words = 8 * nh + nv;
-    int rc = ensure_scratch(items_bytes + out_words * sizeof(u32));
-    if (rc) return rc;
-    rc = small_h2d(c.scratch, items.data(), items.size() * sizeof(GatherItem));
-    if (rc) return rc;
-    const GatherItem *d_items = (const GatherItem *)c.scratch;
-    // the gathers write straight into the result page when the words fit: the read-back is a synchronisation, not a copy
-    u32 *const page = (u32 *)result_target(out_words * sizeof(u32));
-    u32 *d_out = page ? page : (u32 *)((unsigned char *)c.scratch + items_bytes);
-    if (nh) hipLaunchKernelGGL(k_gather_words, dim3(ceil_div(8 * nh, 256)), dim3(256), 0, c.stream, d_items, 8u, 8 * nh, d_out);
-    if (nv) hipLaunchKernelGGL(k_gather_words, dim3(ceil_div(nv, 256)), dim3(256), 0, c.stream, d_items + nh, 1u, nv, d_out + 8 * nh);
-    TSTWO_LAUNCH_CHECK();
-    std::vector<u32> host(out_words);
-    if (page) {
-        const void *view = nullptr;
-        rc = result_wait(&view);
-        if (rc) return rc;
-        memcpy(host.data(), view, out_words * sizeof(u32));
-    } else {
-        rc = small_d2h(host.data(), d_out, out_words * sizeof(u32));
-        if (rc) return rc;
-    }
-    if (nh - n_extra) memcpy(hash_witness, host.data(), 32 * (nh - n_extra));
-    if (n_extra) memcpy(extra, host.data() + 8 * (nh - n_extra), 32 * n_extra);
-    if (nq) memcpy(queried_values, host.data() + 8 * nh, 4 * nq);
-    if (nw) memcpy(column_witness, host.data() + 8 * nh + nq, 4 * nw);
-    return TSTWO_OK;
-}
-
-int tstwo_merkle_decommit(const uint8_t *layers, u32 max_log, const u32 *const *cols, const u32 *col_log_sizes, size_t n_cols,
-                          const u32 *query_logs, const uint64_t *const *queries, const size_t *n_queries, size_t n_query_sets,
-                          u32 *queried_values, size_t *n_queried, uint8_t *hash_witness, size_t *n_hashes,
-                          u32 *column_witness, size_t *n_column_witness) {
-    TSTWO_REQUIRE_READY();
-    if (!n_queried || !n_hashes || !n_column_witness) return set_error(TSTWO_ERR_BAD_ARG, "merkle decommit: null argument");
-    DecommitLists l;
-    int rc = plan_decommit(layers, max_log, cols, col_log_sizes, n_cols, query_logs, queries, n_queries, n_query_sets, l);
-    if (rc) return rc;
-    const size_t cap_q = *n_queried, cap_h = *n_hashes, cap_w = *n_column_witness;
-    *n_queried = l.queried.size(); *n_hashes = l.hashes.size(); *n_column_witness = l.witness.size();
-    if (l.queried.size() > cap_q || l.hashes.size() > cap_h || l.witness.size() > cap_w ||
-        (l.queried.size() && !queried_values) || (l.hashes.size() && !hash_witness) || (l.witness.size() && !column_witness))
-        return set_error(TSTWO_ERR_BAD_ARG, "merkle decommit: output buffer too small (required counts returned)");
-    return run_decommit(l, queried_values, hash_witness, column_witness);
-}
-
-// Several trees in one round trip (every layer of a FRI proof, every tree of a commitment scheme): request r is described by
-// reqs[r]; the outputs are the concatenation of the per-tree outputs in request order, counts[3r..3r+2] = (queried values,
-// hashes, column witness words) of request r.  totals[3] is in/out like the single-tree call (capacities / required sizes).
-int tstwo_merkle_decommit_many(const tstwo_decommit_request *reqs, size_t n_reqs, u32 *queried_values, uint8_t *hash_witness,
-                               u32 *column_witness, size_t *counts, size_t totals[3]) {
-    TSTWO_REQUIRE_READY();
-    if ((n_reqs && (!reqs || !counts)) || !totals) return set_error(TSTWO_ERR_BAD_ARG, "merkle decommit: null argument");
-    DecommitLists l;
-    for (size_t r = 0; r < n_reqs; r++) {
-        const size_t q0 = l.queried.size(), h0 = l.hashes.size(), w0 = l.witness.size();
-        const tstwo_decommit_request &q = reqs[r];
-        int rc = plan_decommit(q.layers, q.max_log, q.cols, q.col_log_sizes, q.n_cols, q.query_logs, q.queries, q.n_queries,
-                               q.n_query_sets, l);
-        if (rc) return rc;
-        counts[3 * r] = l.queried.size() - q0;
-        counts[3 * r + 1] = l.hashes.size() - h0;
-        counts[3 * r + 2] = l.witness.size() - w0;
-    }
-    const size_t cap_q = totals[0], cap_h = totals[1], cap_w = totals[2];
-    totals[0] = l.queried.size(); totals[1] = l.hashes.size(); totals[2] = l.witness.size();
-    if (l.queried.size() > cap_q || l.hashes.size() > cap_h || l.witness.size() > cap_w ||
-        (l.queried.size() && !queried_values) || (l.hashes.size() && !hash_witness) || (l.witness.size() && !column_witness))
-        return set_error(TSTWO_ERR_BAD_ARG, "merkle decommit: output buffer too small (required counts returned)");
-    return run_decommit(l, queried_values, hash_witness, column_witness);
-}
-
-// ---- FriProver.decommit_on_queries (fri.ts:768-785) in ONE call: the position logic of
-// computeDecommitmentPositionsAndWitnessEvals (fri.ts:346-384) for every layer, the Merkle walk of every layer's tree
-// (vcs/prover.ts:32-109, plan_decommit above) and ONE gather round trip for all witness evaluations, hash witnesses and
-// column witnesses of the proof.
-namespace {
-// Queries.fold (queries.ts:140-158): positions >> n, de-duplicated (the input is ascending, so is the output)
-void fold_queries(std::vector<uint64_t> &q, u32 n) {
-    size_t w = 0;
-    for (size_t i = 0; i < q.size(); i++) {
-        const uint64_t v = q[i] >> n;
-        if (w == 0 || q[w - 1] != v) q[w++] = v;
-    }
-    q.resize(w);
-}
-// fri.ts:346-384: every position of the folding cosets the queries touch (-> Merkle query set), and those among them the
-// verifier cannot compute itself (-> witness evaluations)
-void decommitment_positions(const std::vector<uint64_t> &q, u32 fold_step, std::vector<uint64_t> &positions, std::vector<uint64_t> &witness) {
-    size_t i = 0;
-    while (i < q.size()) {
-        const uint64_t coset = q[i] >> fold_step, start = coset << fold_step;
-        const size_t first = i;
-        while (i < q.size() && (q[i] >> fold_step) == coset) i++;
-        size_t k = first;
-        for (uint64_t pos = start; pos < start + ((uint64_t)1 << fold_step); pos++) {
-            positions.push_back(pos);
-            if (k < i && q[k] == pos) { k++; continue; }       // the verifier can calculate this one
-            witness.push_back(pos);
-        }
-    }
-}
-}  // namespace
-
-int tstwo_fri_decommit(const tstwo_fri_layer *fri_layers, size_t n_layers, const uint64_t *queries, size_t n_queries, u32 log_domain_size,
-                       u32 first_fold_step, u32 fold_step, u32 *witness_evals, uint8_t *hash_witness, u32 *column_witness, uint8_t *commitments,
-                       size_t *counts, size_t totals[3]) {
-    TSTWO_REQUIRE_READY();
-    if ((n_layers && (!fri_layers || !counts)) || (n_queries && !queries) || !totals) return set_error(TSTWO_ERR_BAD_ARG, "fri decommit: null argument");
-    if (log_domain_size > 31 || first_fold_step > 31 || fold_step > 31 || fold_step == 0) return set_error(TSTWO_ERR_BAD_ARG, "fri decommit: log size / fold step out of range");
-    std::vector<uint64_t> q(queries, queries + n_queries);
-    for (size_t i = 0; i < n_queries; i++) {
-        if (q[i] >> log_domain_size) return set_error(TSTWO_ERR_BAD_ARG, "fri decommit: query position outside the domain");
-        if (i && q[i - 1] >= q[i]) return set_error(TSTWO_ERR_BAD_ARG, "fri decommit: query positions must be ascending and distinct");
-    }
-    DecommitLists l;
-    std::vector<GatherItem> evals;            // one item per coordinate word of a witness evaluation, layer by layer
-    std::vector<std::vector<uint64_t>> pos_sets;
-    for (size_t r = 0; r < n_layers; r++) {
-        const tstwo_fri_layer &fl = fri_layers[r];
-        if (!fl.layers || !fl.n_evals || !fl.cols || !fl.eval_logs) return set_error(TSTWO_ERR_BAD_ARG, "fri decommit: null argument");
-        TSTWO_REQUIRE_TABLE(fl.cols, 4 * fl.n_evals);
-        const size_t h0 = l.hashes.size(), w0 = l.witness.size(), e0 = evals.size();
-        // Merkle query sets of this tree: one per distinct evaluation size (first layer: the circle evaluations folded to their
-        // own size, get_query_positions_by_log_size fri.ts:470-480; inner layers: the one line evaluation)
-        pos_sets.clear();
-        std::vector<u32> set_logs;
-        std::vector<u32> col_logs(4 * fl.n_evals);
-        const u32 step = r == 0 ? first_fold_step : fold_step;
-        for (size_t e = 0; e < fl.n_evals; e++) {
-            const u32 lg = fl.eval_logs[e];
-            if (lg > log_domain_size || lg > fl.max_log) return set_error(TSTWO_ERR_BAD_ARG, "fri decommit: evaluation larger than its tree / the query domain");
-            if (r > 0 && (fl.n_evals != 1 || lg != fl.max_log)) return set_error(TSTWO_ERR_BAD_ARG, "fri decommit: an inner layer commits one line evaluation");
-            for (int k = 0; k < 4; k++) col_logs[4 * e + k] = lg;
-            std::vector<uint64_t> cq = q;
-            if (r == 0) fold_queries(cq, log_domain_size - lg);
-            else if (cq.size() && (cq.back() >> lg)) return set_error(TSTWO_ERR_BAD_ARG, "fri decommit: layer sizes do not follow the fold steps");
-            std::vector<uint64_t> pos, wit;
-            decommitment_positions(cq, step, pos, wit);
-            if (pos.size() && (pos.back() >> lg)) return set_error(TSTWO_ERR_BAD_ARG, "fri decommit: fold step larger than the evaluation");
-            for (uint64_t p : wit)
-                for (int k = 0; k < 4; k++) evals.push_back({fl.cols[4 * e + k], p});
-            bool seen = false;
-            for (u32 sl : set_logs) seen = seen || sl == lg;
-            if (!seen) { set_logs.push_back(lg); pos_sets.push_back(std::move(pos)); }
-        }
-        std::vector<const uint64_t *> qp(pos_sets.size());
-        std::vector<size_t> qn(pos_sets.size());
-        for (size_t k = 0; k < pos_sets.size(); k++) { qp[k] = pos_sets[k].data(); qn[k] = pos_sets[k].size(); }
-        const size_t q0 = l.queried.size();
-        int rc = plan_decommit(fl.layers, fl.max_log, fl.cols, col_logs.data(), 4 * fl.n_evals, set_logs.data(), qp.data(), qn.data(), pos_sets.size(), l);
-        if (rc) return rc;
-        l.queried.resize(q0);                  // the queried values themselves are not part of a FRI layer proof (fri.ts:262-269)
-        counts[3 * r] = (evals.size() - e0) / 4;
-        counts[3 * r + 1] = l.hashes.size() - h0;
-        counts[3 * r + 2] = l.witness.size() - w0;
-        // the next layer is queried at the folded positions (fri.ts:776-783)
-        fold_queries(q, r == 0 ? first_fold_step : fold_step);
-    }
-    const size_t cap_e = totals[0], cap_h = totals[1], cap_w = totals[2];
-    totals[0] = evals.size() / 4; totals[1] = l.hashes.size(); totals[2] = l.witness.size();
-    if (totals[0] > cap_e || totals[1] > cap_h || totals[2] > cap_w || (totals[0] && !witness_evals) || (totals[1] && !hash_witness) ||
-        (totals[2] && !column_witness))
-        return set_error(TSTWO_ERR_BAD_ARG, "fri decommit: output buffer too small (required counts returned)");
-    l.queried = evals;                         // travel as the "queried" 1-word items of the shared gather
-    if (commitments)                           // the trees' roots (FriLayerProof.commitment) ride along: digest 0 of every layers buffer
-        for (size_t r = 0; r < n_layers; r++) l.hashes.push_back({(const u32 *)fri_layers[r].layers, 0});
-    return run_decommit(l, witness_evals, hash_witness, column_witness, commitments ? n_layers : 0, commitments);
-}
-
 // Device-resident Blake2sChannel (state: 10 words = digest[8], n_challenges, n_sent).  root: 32 bytes in device memory
 // (e.g. offset 0 of a tstwo_merkle_commit layers buffer) or NULL to skip the mix; felt: 4 words in device memory or NULL
 // to skip the draw.  Nothing is synchronised: the next kernel on the stream can consume `felt`.
@@ -1405,7 +929,7 @@ int tstwo_merkle_commit_many(const tstwo_commit_request *reqs, size_t n_trees, u
         const tstwo_commit_request &q = reqs[r];
         if (!q.layers || !q.cols || !q.log_sizes) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null argument");
         uniform = q.n_cols == n_cols && (n_cols == 16 || n_cols == 32 || n_cols == 48 || n_cols == 64) && n_cols * n_trees <= (size_t)kMaxHashCols &&
-                  (((uintptr_t)q.layers) & 15) == 0;
+                  aligned16(q.layers);
         for (size_t k = 0; k < q.n_cols && uniform; k++) {
             if (!q.cols[k]) return set_error(TSTWO_ERR_BAD_ARG, "null device pointer in table");
             if (r == 0 && k == 0) lg = q.log_sizes[0];
@@ -1419,7 +943,6 @@ int tstwo_merkle_commit_many(const tstwo_commit_request *reqs, size_t n_trees, u
             if (rc) return rc;
         }
     } else {
-        Context &c = ctx();
         HashColPtrs hp;
         TreeSet leaf = {}, ts = {};
         for (size_t r = 0; r < n_trees; r++) {
@@ -1427,44 +950,14 @@ int tstwo_merkle_commit_many(const tstwo_commit_request *reqs, size_t n_trees, u
             ts.t[r] = (uint4 *)reqs[r].layers;
             leaf.t[r] = (uint4 *)(reqs[r].layers + 32 * (((size_t)1 << lg) - 1));
         }
-        const size_t n_nodes = (size_t)1 << lg;
-        unsigned blocks = ceil_div(n_nodes, 256);
-        const unsigned cap_mult = (unsigned)knobs().merkle_cap;
-        const unsigned cap = (unsigned)c.n_cus * cap_mult / (unsigned)n_trees;          // the same lanes in flight as one tree's launch
-        if (blocks > cap) blocks = cap ? cap : 1;
-        const dim3 grid(blocks, (unsigned)n_trees);
-        switch (n_cols / 16) {
-            case 1: hipLaunchKernelGGL(k_merkle_leaf_static<1>, grid, dim3(256), 0, c.stream, hp, leaf, n_nodes); break;
-            case 2: hipLaunchKernelGGL(k_merkle_leaf_static<2>, grid, dim3(256), 0, c.stream, hp, leaf, n_nodes); break;
-            case 3: hipLaunchKernelGGL(k_merkle_leaf_static<3>, grid, dim3(256), 0, c.stream, hp, leaf, n_nodes); break;
-            default: hipLaunchKernelGGL(k_merkle_leaf_static<4>, grid, dim3(256), 0, c.stream, hp, leaf, n_nodes); break;
-        }
-        // column-free layers lg-1 .. kUpLog two per launch (in-lane subtrees), a single leftover layer on its own, then the
-        // quad-lane levels: the launch sequence of tstwo_merkle_commit for a tree whose columns all sit on the leaf layer
-        int cur = (int)lg - 1;
-        while (cur - 1 >= kUpLog) {
-            const size_t tops = (size_t)1 << (cur - 1);
-            hipLaunchKernelGGL(k_merkle_subtree2c, dim3((unsigned)(tops / 256), (unsigned)n_trees), dim3(256), 0, c.stream, ts, (u32)cur + 1);
-            cur -= 2;
-        }
-        if (cur >= kUpLog) {
-            unsigned b1 = ceil_div((size_t)1 << cur, 256);
-            if (b1 > cap) b1 = cap ? cap : 1;
-            hipLaunchKernelGGL(k_merkle_inner_set, dim3(b1, (unsigned)n_trees), dim3(256), 0, c.stream, ts, (u32)cur);
-            cur -= 1;
-        }
-        TSTWO_LAUNCH_CHECK();
-        int rc = commit_upper_levels(ts, (unsigned)n_trees, (u32)cur + 1, 0, nullptr);
+        int rc = launch_leaf_static(hp, n_cols, leaf, (unsigned)n_trees, lg);
+        if (rc == TSTWO_OK) rc = commit_column_free(ts, (unsigned)n_trees, lg, 0, nullptr);
         if (rc) return rc;
     }
-    if (roots) {
-        std::vector<GatherItem> items(n_trees);
-        for (size_t r = 0; r < n_trees; r++) items[r] = {(const u32 *)reqs[r].layers, 0};
-        DecommitLists l;
-        l.hashes = items;
-        return run_decommit(l, nullptr, roots, nullptr);
-    }
-    return TSTWO_OK;
+    if (!roots) return TSTWO_OK;
+    std::vector<const uint8_t *> trees(n_trees);
+    for (size_t r = 0; r < n_trees; r++) trees[r] = reqs[r].layers;
+    return download_roots(trees.data(), n_trees, roots);
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@
 // 32-column leaf 3.
 //
 // Elements in device memory are 8 little-endian u32 limbs, canonical: 32 bytes, so a Poseidon tree has exactly the layout of
-// tstwo_merkle_commit (layer k at byte 32 (2^k - 1), root first) and the decommit / gather entries of merkle.hip serve it as is.
+// tstwo_merkle_commit (layer k at byte 32 (2^k - 1), root first) and the decommit / gather entries of decommit.hip serve it as is.
 #include <algorithm>
 
 #include "common.h"

@@ -339,21 +339,7 @@ class Poseidon252MerkleProver(MerkleProver):
 
     _hash_of = staticmethod(FieldElement252.from_le_bytes)
     _hashes_of = FeltSlices
-
-    @staticmethod
-    def commit(columns, ops=None, sync_root: bool = True) -> "Poseidon252MerkleProver":
-        log_sizes = []
-        for c in columns:
-            n = c.len()
-            if n == 0 or n & (n - 1):
-                raise ValueError("column length is not a power of two")
-            log_sizes.append(n.bit_length() - 1)
-        max_log = max(log_sizes) if columns else 0
-        buf = L.DeviceBuffer(32 * ((2 << max_log) - 1))
-        root = (C.c_uint8 * 32)() if sync_root else None
-        L.call("tstwo_poseidon252_merkle_commit", L.ptr_array([c.ptr for c in columns]), L.u32x(log_sizes), len(columns), _vp(buf.ptr), root)
-        from .vcs import TreeLayers
-        return Poseidon252MerkleProver(TreeLayers(buf, max_log), buf, FieldElement252.from_le_bytes(bytes(root)) if sync_root else None)
+    _commit_entry = "tstwo_poseidon252_merkle_commit"
 
     @staticmethod
     def commit_many(column_sets, sync_root: bool = True) -> list:

@@ -123,6 +123,35 @@ class TreeLayers(_LazyList):
     def _make(self, k): return DeviceHashLayer(self.buf, 1 << k, 32 * ((1 << k) - 1))
 
 
+def _log_sizes(columns) -> list:
+    """log2 of every column's length (a tree takes columns of power-of-two lengths only)."""
+    logs = []
+    for c in columns:
+        n = c.len()
+        if n == 0 or n & (n - 1):
+            raise ValueError("column length is not a power of two")
+        logs.append(n.bit_length() - 1)
+    return logs
+
+
+def _decommit_args(tree, queriesPerLogSize: dict, columns) -> tuple:
+    """One tree's decommitment request as the library takes it: (the fields of tstwo_decommit_request in order, which are also the
+    leading arguments of tstwo_merkle_decommit; the query arrays they point to, to be kept alive; the most values; the most hashes
+    the request can return)."""
+    cols = list(columns)
+    max_log = len(tree.layers) - 1
+    # like the reference, only the entries for layers this tree has are looked at (a commitment scheme hands every tree the
+    # query positions of ALL column sizes, pcs/prover.ts Rust text :137-141)
+    sets = [(lg, list(q)) for lg, q in queriesPerLogSize.items() if q and 0 <= lg <= max_log]
+    total_q = sum(len(q) for _, q in sets)
+    qarrs = [(C.c_uint64 * max(len(q), 1))(*q) for _, q in sets]
+    qptrs = (C.POINTER(C.c_uint64) * max(len(sets), 1))(*[C.cast(a, C.POINTER(C.c_uint64)) for a in qarrs])
+    nq = (C.c_size_t * max(len(sets), 1))(*[len(q) for _, q in sets])
+    args = (tree._buf.ptr, max_log, L.ptr_array([c.ptr for c in cols]), L.u32x([c.len().bit_length() - 1 for c in cols]), len(cols),
+            L.u32x([lg for lg, _ in sets]), qptrs, nq, len(sets))
+    return args, qarrs, total_q * max(1, len(cols)), 2 * total_q * (max_log + 1)
+
+
 class MerkleProver:
     """MerkleProver.commit / root (vcs/prover.ts:13-30,111-113): layers[0] = [root], all layers retained on device."""
 
@@ -130,26 +159,21 @@ class MerkleProver:
     # Poseidon252MerkleProver (poseidon.py) turns them into FieldElement252
     _hash_of = staticmethod(bytes)
     _hashes_of = HashSlices
+    _commit_entry = "tstwo_merkle_commit"              # the library call that builds a tree of this kind
 
     def __init__(self, layers: list, buf: L.DeviceBuffer, root: bytes):
         self.layers, self._buf, self._root = layers, buf, root
 
-    @staticmethod
-    def commit(columns, ops=None, sync_root: bool = True) -> "MerkleProver":
+    @classmethod
+    def commit(cls, columns, ops=None, sync_root: bool = True) -> "MerkleProver":
         """columns: HipColumn list of power-of-two lengths (mixed sizes allowed; order kept within a size).
         sync_root=False: nothing is read back (root() fetches the 32 bytes on first use) — for callers that keep going on the device."""
-        log_sizes = []
-        for c in columns:
-            n = c.len()
-            if n == 0 or n & (n - 1):
-                raise ValueError("column length is not a power of two")
-            log_sizes.append(n.bit_length() - 1)
+        log_sizes = _log_sizes(columns)
         max_log = max(log_sizes) if columns else 0
         buf = L.DeviceBuffer(32 * ((2 << max_log) - 1))
         root = (C.c_uint8 * 32)() if sync_root else None
-        L.call("tstwo_merkle_commit", L.ptr_array([c.ptr for c in columns]), L.u32x(log_sizes), len(columns), _vp(buf.ptr), root)
-        layers = TreeLayers(buf, max_log)
-        return MerkleProver(layers, buf, bytes(root) if sync_root else None)
+        L.call(cls._commit_entry, L.ptr_array([c.ptr for c in columns]), L.u32x(log_sizes), len(columns), _vp(buf.ptr), root)
+        return cls(TreeLayers(buf, max_log), buf, cls._hash_of(bytes(root)) if sync_root else None)
 
     @staticmethod
     def commit_many(column_sets, sync_root: bool = True) -> list:
@@ -159,12 +183,7 @@ class MerkleProver:
         reqs = (L.CommitRequest * max(len(column_sets), 1))()
         keep, bufs, max_logs = [], [], []
         for r, cols in enumerate(column_sets):
-            logs = []
-            for c in cols:
-                n = c.len()
-                if n == 0 or n & (n - 1):
-                    raise ValueError("column length is not a power of two")
-                logs.append(n.bit_length() - 1)
+            logs = _log_sizes(cols)
             max_log = max(logs) if cols else 0
             buf = L.DeviceBuffer(32 * ((2 << max_log) - 1))
             colp, lg = L.ptr_array([c.ptr for c in cols]), L.u32x(logs)
@@ -193,24 +212,13 @@ class MerkleProver:
         """MerkleProver.decommit (vcs/prover.ts:32-109): returns (queried_values, MerkleDecommitment).
         The walk over the layers and the two device gathers run inside the library (tstwo_merkle_decommit);
         `_decommit_walk` below is the same walk on the host mirror, kept for cross-checking."""
-        cols = list(columns)
-        max_log = len(self.layers) - 1
-        # like the reference, only the entries for layers this tree has are looked at (a commitment scheme hands every tree the
-        # query positions of ALL column sizes, pcs/prover.ts Rust text :137-141)
-        sets = [(lg, list(q)) for lg, q in queriesPerLogSize.items() if q and 0 <= lg <= max_log]
-        total_q = sum(len(q) for _, q in sets)
-        cap_v = max(1, total_q * max(1, len(cols)))
-        cap_h = max(1, 2 * total_q * (max_log + 1))
-        qarrs = [(C.c_uint64 * max(len(q), 1))(*q) for _, q in sets]
-        qptrs = (C.POINTER(C.c_uint64) * max(len(sets), 1))(*[C.cast(a, C.POINTER(C.c_uint64)) for a in qarrs])
-        nq = (C.c_size_t * max(len(sets), 1))(*[len(q) for _, q in sets])
+        args, _keep, cap_v, cap_h = _decommit_args(self, queriesPerLogSize, columns)
+        cap_v, cap_h = max(1, cap_v), max(1, cap_h)
         queried = np.empty(cap_v, dtype=np.uint32)
         colwit = np.empty(cap_v, dtype=np.uint32)
         hashes = np.empty(32 * cap_h, dtype=np.uint8)
         n_q, n_h, n_w = C.c_size_t(cap_v), C.c_size_t(cap_h), C.c_size_t(cap_v)
-        L.call("tstwo_merkle_decommit", _vp(self._buf.ptr), max_log, L.ptr_array([c.ptr for c in cols]),
-               L.u32x([c.len().bit_length() - 1 for c in cols]), len(cols), L.u32x([lg for lg, _ in sets]), qptrs, nq, len(sets),
-               queried.ctypes.data_as(L.u32p), C.byref(n_q), hashes.ctypes.data_as(L.u8p), C.byref(n_h),
+        L.call("tstwo_merkle_decommit", *args, queried.ctypes.data_as(L.u32p), C.byref(n_q), hashes.ctypes.data_as(L.u8p), C.byref(n_h),
                colwit.ctypes.data_as(L.u32p), C.byref(n_w))
         hb = hashes.tobytes()
         dec = MerkleDecommitment(self._hashes_of(hb, n_h.value), M31Values(colwit[:n_w.value].tolist()))
@@ -227,20 +235,10 @@ class MerkleProver:
         keep, reqs = [], (L.DecommitRequest * len(requests))()
         cap_v = cap_h = 1
         for r, (tree, qpl, columns) in enumerate(requests):
-            cols = list(columns)
-            max_log = len(tree.layers) - 1
-            sets = [(lg, list(q)) for lg, q in qpl.items() if q and 0 <= lg <= max_log]
-            total_q = sum(len(q) for _, q in sets)
-            cap_v += total_q * max(1, len(cols))
-            cap_h += 2 * total_q * (max_log + 1)
-            qarrs = [(C.c_uint64 * max(len(q), 1))(*q) for _, q in sets]
-            qptrs = (C.POINTER(C.c_uint64) * max(len(sets), 1))(*[C.cast(a, C.POINTER(C.c_uint64)) for a in qarrs])
-            nq = (C.c_size_t * max(len(sets), 1))(*[len(q) for _, q in sets])
-            colp = L.ptr_array([c.ptr for c in cols])
-            logs = L.u32x([c.len().bit_length() - 1 for c in cols])
-            qlogs = L.u32x([lg for lg, _ in sets])
-            keep += [qarrs, qptrs, nq, colp, logs, qlogs]
-            reqs[r] = L.DecommitRequest(tree._buf.ptr, max_log, colp, logs, len(cols), qlogs, qptrs, nq, len(sets))
+            args, qarrs, n_v, n_h = _decommit_args(tree, qpl, columns)
+            cap_v, cap_h = cap_v + n_v, cap_h + n_h
+            keep += [args, qarrs]
+            reqs[r] = L.DecommitRequest(*args)
         queried = np.empty(cap_v, dtype=np.uint32)
         colwit = np.empty(cap_v, dtype=np.uint32)
         hashes = np.empty(32 * cap_h, dtype=np.uint8)
