@@ -111,7 +111,11 @@ int tstwo_zero(void *dev, size_t bytes);                                  /* asy
  * quotient constants: the staging slot they travel through is only valid at capture time — such a call fails with
  * TSTWO_ERR_BAD_ARG "host-array upload during graph capture" and records nothing); allocations must hit the
  * library's caching allocator (run the sequence once eagerly first); all buffers the sequence uses must outlive the
- * graph, which addresses them by value. */
+ * graph, which addresses them by value.  The library's own scratch block (the ticket, partial sums and eq tables of
+ * tstwo_gkr_sum_poly_async, tstwo_gkr_round and tstwo_gkr_gen_eq_evals live in it) is recorded by value too: a block that a
+ * later call outgrows is retired, not freed, and stays mapped until tstwo_shutdown, so a graph may be replayed after any
+ * eager call, however much scratch that call needed.  A captured call that would itself have to grow the block fails with
+ * TSTWO_ERR_BAD_ARG "scratch growth during graph capture" and records nothing; the eager run of the sequence sizes it. */
 int tstwo_graph_begin_capture(void);
 int tstwo_graph_end_capture(void **graph_exec);
 int tstwo_graph_launch(void *graph_exec);

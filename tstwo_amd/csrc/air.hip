@@ -447,12 +447,7 @@ int tstwo_air_eval_program(const u32 *const *cols, size_t n_cols, u32 trace_log_
     TSTWO_REQUIRE_TABLE(cols, n_cols);
     TSTWO_REQUIRE_TABLE(accum, 4);
     // the program and coefficient words travel through the small-upload ring, which a captured graph cannot replay
-    {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(ctx().stream, &st) != hipSuccess) (void)hipGetLastError();
-        else if (st != hipStreamCaptureStatusNone)
-            return bad("host-array upload during graph capture (the air program and its coefficients cannot be recorded)");
-    }
+    if (stream_is_capturing()) return bad("host-array upload during graph capture (the air program and its coefficients cannot be recorded)");
     // validate every instruction: opcodes, registers (each read one written before), columns, offsets, constants; count ACCs
     bool written[TSTWO_AIR_PROGRAM_MAX_REGS] = {};
     u32 n_regs = 0;

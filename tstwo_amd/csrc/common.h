@@ -81,6 +81,8 @@ int set_error(int code, const std::string &msg);
 int hip_fail(hipError_t e, const char *what);
 int require_ready();
 int ensure_scratch(size_t bytes);
+// whether the current stream is recording a graph (tstwo_graph_begin_capture); false when the runtime cannot tell
+bool stream_is_capturing();
 // "Everything enqueued on the stream so far has completed" for the SMALL synchronous results of the boundary (a zero flag, a Merkle
 // root, eval_at_point's value, tstwo_download_many): hipStreamSynchronize costs 9.5 us on this stack whatever the work was, so a
 // one-lane kernel stores a sequence number into page-locked host memory behind the work and the host polls that word (bounded: after

@@ -60,17 +60,31 @@ int require_ready() {
     }
     return TSTWO_OK;
 }
+bool stream_is_capturing() {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(g_ctx.stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return st != hipStreamCaptureStatusNone;
+}
+// The scratch block only grows, and an outgrown block is RETIRED, not freed: launches already enqueued, and graphs captured
+// earlier (the gkr_* entry points record scratch addresses by value), keep a block of their own that stays mapped until
+// tstwo_shutdown.  Growth at least doubles the size, so all retired blocks together are smaller than the live one.  Nothing is
+// freed here, hence no stream synchronisation; growth while the stream is capturing is refused, because the recorded launches
+// would address a block that later eager calls no longer share (include/tstwo_hip.h, "Rules while capturing").
+static std::vector<void *> g_scratch_retired;
 int ensure_scratch(size_t bytes) {
     Context &c = g_ctx;
     if (c.scratch_bytes >= bytes) return TSTWO_OK;
-    if (c.scratch) {
-        TSTWO_HIP(hipStreamSynchronize(c.stream));
-        TSTWO_HIP(hipFree(c.scratch));
-        c.scratch = nullptr;
-        c.scratch_bytes = 0;
-    }
     size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-    TSTWO_HIP(hipMalloc((void **)&c.scratch, want));
+    if (c.scratch) {
+        if (stream_is_capturing())
+            return set_error(TSTWO_ERR_BAD_ARG, "scratch growth during graph capture (run the sequence once eagerly first: the "
+                                                "library's scratch block must already hold what the captured calls need)");
+        if (want < 2 * c.scratch_bytes) want = 2 * c.scratch_bytes;
+    }
+    u32 *grown = nullptr;
+    TSTWO_HIP(hipMalloc((void **)&grown, want));
+    if (c.scratch) g_scratch_retired.push_back(c.scratch);
+    c.scratch = grown;
     c.scratch_bytes = want;
     return TSTWO_OK;
 }
@@ -121,10 +135,8 @@ int result_wait(const void **host_view) {
 // A host-array upload cannot be part of a captured graph: the memcpy node would read a ring slot (or the caller's array) at
 // REPLAY time, long after it has been overwritten, and the slot's event would become a captured event.  Fail loudly instead
 // (include/tstwo_hip.h, "Rules while capturing").
-static int refuse_if_capturing(hipStream_t s) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return TSTWO_OK; }
-    if (st != hipStreamCaptureStatusNone)
+static int refuse_if_capturing() {
+    if (stream_is_capturing())
         return set_error(TSTWO_ERR_BAD_ARG, "host-array upload during graph capture (column tables beyond 64 pointers, gather "
                                             "requests and quotient constants cannot be recorded)");
     return TSTWO_OK;
@@ -132,7 +144,7 @@ static int refuse_if_capturing(hipStream_t s) {
 int small_h2d(void *dev_dst, const void *host_src, size_t bytes) {
     Context &c = g_ctx;
     if (bytes == 0) return TSTWO_OK;
-    if (int rc = refuse_if_capturing(c.stream)) return rc;
+    if (int rc = refuse_if_capturing()) return rc;
     if (!c.up_ring || bytes > kUpSlotBytes) {
         TSTWO_HIP(hipMemcpyAsync(dev_dst, host_src, bytes, hipMemcpyHostToDevice, c.stream));
         TSTWO_HIP(hipStreamSynchronize(c.stream));
@@ -164,7 +176,7 @@ int fill_col_table(ColPtrs &out, const u32 *const *cols, size_t n_cols, int slot
     // A table in device memory cannot be part of a captured graph, whether or not this call would have to upload it: the launch
     // would be recorded against a slot that any later > 64-column call rewrites before the graph is replayed (a cache HIT used
     // to slip through here — only the upload itself was refused).
-    if (int rc = refuse_if_capturing(c.stream)) return rc;
+    if (int rc = refuse_if_capturing()) return rc;
     if (c.coltab_cap < n_cols) {
         size_t cap = 1024;
         while (cap < n_cols) cap *= 2;
@@ -416,6 +428,8 @@ int tstwo_shutdown(void) {
     if (c.coltab) (void)hipFree(c.coltab);
     coltab_cache_reset();
     if (c.scratch) (void)hipFree(c.scratch);
+    for (void *p : g_scratch_retired) (void)hipFree(p);
+    g_scratch_retired.clear();
     if (c.copy_stream[0]) {
         for (int i = 0; i < kCopyStreams; i++) {
             (void)hipStreamSynchronize(c.copy_stream[i]);
@@ -627,7 +641,7 @@ int tstwo_upload_async(void *dev_dst, const void *host_src, size_t bytes) {
     if (bytes == 0) return TSTWO_OK;
     TSTWO_REQUIRE_PTRS(dev_dst, host_src);
     Context &c = g_ctx;
-    if (int rc = refuse_if_capturing(c.stream)) return rc;
+    if (int rc = refuse_if_capturing()) return rc;
     if (!c.copy_stream[0]) {
         for (int i = 0; i < kCopyStreams; i++) {
             TSTWO_HIP(hipStreamCreateWithFlags(&c.copy_stream[i], hipStreamNonBlocking));

@@ -360,12 +360,6 @@ __global__ void __launch_bounds__(kThreads) k_logup_block_scan(u32 *sums, u32 n_
 // ---------------------------------------------------------------- host
 int bad(const std::string &msg) { return set_error(TSTWO_ERR_BAD_ARG, msg); }
 
-bool capturing() {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(ctx().stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return st != hipStreamCaptureStatusNone;
-}
-
 }  // namespace
 
 extern "C" {
@@ -378,7 +372,7 @@ int tstwo_logup_column(const tstwo_logup_frac *fracs, size_t n_fracs, const u32 
     TSTWO_REQUIRE_TABLE(out, 4);
     if (prev) TSTWO_REQUIRE_TABLE(prev, 4);
     // the descriptors travel through the small-upload ring, which a captured graph cannot replay
-    if (capturing()) return bad("host-array upload during graph capture (the logup fraction descriptors cannot be recorded)");
+    if (stream_is_capturing()) return bad("host-array upload during graph capture (the logup fraction descriptors cannot be recorded)");
     const u32 n = 1u << log_size;
     bool vec = n % 4 == 0;
     for (int j = 0; j < 4; j++) vec = vec && aligned16(out[j]) && (!prev || aligned16(prev[j]));
@@ -438,7 +432,7 @@ int tstwo_logup_finalize_last(u32 *const col[4], u32 log_size, u32 claimed_sum[4
     if (log_size < 1 || log_size > kMaxLog) return bad("logup finalize: log_size must be 1 to 28");
     TSTWO_REQUIRE_TABLE(col, 4);
     if (!claimed_sum) return bad("logup finalize: null host argument");
-    if (capturing()) return bad("host read-back during graph capture (the logup claimed sum cannot be recorded)");
+    if (stream_is_capturing()) return bad("host read-back during graph capture (the logup claimed sum cannot be recorded)");
     Soa4 c4 = {{col[0], col[1], col[2], col[3]}};
     if (log_size < kMinTiledLog) {
         if (int rc = ensure_scratch(4 * sizeof(u32))) return rc;
