@@ -500,9 +500,18 @@ int launch_fast_kernel(KernelT kernel, int threads, size_t lds_bytes, size_t til
     return TSTWO_OK;
 }
 
+// Whether the tile accesses of a pass carry the non-temporal policy (cfft_fast.cuh: k_cfft_b_stream / k_cfft_a_stream): forward
+// transforms of a column set of 1 GiB and more — several times the 256 MiB cache, where the in-place read-modify-write gains with
+// it (tools/microbench7.hip) and 256 x 2^22 is 2 % faster; 32 x 2^22 (512 MiB) measures the same either way, 128 MiB and less lose.
+inline bool streams_past_cache(size_t n_cols, u32 n) { return (n_cols << n) >= ((size_t)1 << 28); }
+
 template <bool INV, int K, int LOGTA = 14, int V = (LOGTA == 15 ? 2 : 1)>
 int launch_a(u32 *const *cols, size_t n_cols, u32 n, u32 lo, const u32 *tw_end, u32 scale) {
     const size_t tiles = (size_t)1 << (n - LOGTA);
+    if constexpr (!INV && LOGTA == 15 && V == 2)
+        if (streams_past_cache(n_cols, n))
+            return launch_fast_kernel(fast::k_cfft_a_stream<K>, (1 << (LOGTA - 4)) / V,
+                                      ((size_t)(1 << LOGTA) + (1 << (LOGTA - 5)) + ((size_t)1 << K)) * sizeof(u32), tiles, cols, n_cols, n, lo, tw_end, scale);
     return launch_fast_kernel(fast::k_cfft_a<INV, K, 0, LOGTA, V>, (1 << (LOGTA - 4)) / V,
                               ((size_t)(1 << LOGTA) + (1 << (LOGTA - 5)) + ((size_t)1 << K)) * sizeof(u32), tiles, cols, n_cols, n, lo, tw_end, scale);
 }
@@ -556,6 +565,10 @@ int launch_fast(u32 *const *cols, size_t n_cols, u32 n, const Pass &ps, const u3
     if (ps.lo == 0) {
         const size_t tiles = (size_t)1 << (n - ps.k);
         const size_t lds = (((size_t)1 << ps.k) + ((size_t)1 << (ps.k - 5)) + ((size_t)1 << (ps.k - 4))) * sizeof(u32);
+        if constexpr (!INV)
+            if (streams_past_cache(n_cols, n) && (ps.k == 13 || ps.k == 14))
+                return ps.k == 13 ? launch_fast_kernel(fast::k_cfft_b_stream<13>, 512, lds, tiles, cols, n_cols, n, tw_end, scale)
+                                  : launch_fast_kernel(fast::k_cfft_b_stream<14>, 1024, lds, tiles, cols, n_cols, n, tw_end, scale);
         switch (ps.k) {
             case 14: return launch_fast_kernel(fast::k_cfft_b<INV, 14>, 1024, lds, tiles, cols, n_cols, n, tw_end, scale);
             case 13: return launch_fast_kernel(fast::k_cfft_b<INV, 13>, 512, lds, tiles, cols, n_cols, n, tw_end, scale);

@@ -21,6 +21,13 @@
 
 namespace fast {
 
+// Cache policy of the tile loads and stores (NT, the last template parameter of the two pass bodies): every tile word is read once
+// and written once per pass, and where the column set is far larger than the 256 MiB cache the forward passes gain 2 % with `nt` on
+// them — loads AND stores: the in-place read-modify-write of tools/microbench7.hip gains with both and loses with either alone.
+// Column sets that fit the cache lose 7-11 % with it (the second pass finds the first one's words there) and the inverse passes lose
+// 1.6 % at any size, so only k_cfft_b_stream / k_cfft_a_stream carry it and cfft.hip launches them for large forward transforms only.
+// Twiddle loads (shared by every column of a tile position) always keep the default policy.
+
 __device__ __forceinline__ u32 pad(u32 e) { return e + (e >> 5); }
 // offset of word (m << Q) relative to pad(e0) when e0 has zeros in the group's bit range (no carries: see DESIGN.md)
 template <int Q>
@@ -192,9 +199,9 @@ template <> struct SrcTable<0> { using type = NoSrc; };
 #ifndef TSTWO_B_WAVES
 #define TSTWO_B_WAVES 6
 #endif
-template <bool INV, int LOGT, bool OOP = false>
-__global__ void __launch_bounds__(1 << (LOGT - 4), TSTWO_B_WAVES) k_cfft_b(ColPtrs cols, typename SrcTable<OOP ? 1 : 0>::type src, u32 n_cols, u32 total_items,
-                                                 u32 n, const u32 *__restrict__ tw_end, u32 scale) {
+template <bool INV, int LOGT, bool OOP, bool NT>
+__device__ __forceinline__ void cfft_b_runs(const ColPtrs &cols, const typename SrcTable<OOP ? 1 : 0>::type &src, u32 n_cols, u32 total_items,
+                                            u32 n, const u32 *__restrict__ tw_end, u32 scale) {
     constexpr int THREADS = 1 << (LOGT - 4);
     constexpr int GM = LOGT - 10;              // layers of the middle LDS stage (bits [8, LOGT-2))
     constexpr u32 T = 1u << LOGT, QT = T / 4;
@@ -234,7 +241,7 @@ __global__ void __launch_bounds__(1 << (LOGT - 4), TSTWO_B_WAVES) k_cfft_b(ColPt
         const u32 *__restrict__ d = src_of(col0);
 #pragma unroll
         for (int j = 0; j < 4; j++)
-            pf[j] = INV ? gload4(d, 16 * tp + 4 * j) : gload4(d + 4 * tp + j * QT);
+            pf[j] = INV ? gload4<NT>(d, 16 * tp + 4 * j) : gload4<NT>(d + 4 * tp + j * QT);
         // (twiddle loads as wave-uniform base + 32-bit lane offset: a 64-bit address pair per load, all of them live at once
         // because the loads are issued back to back, is what used to spill in this prologue)
         uint4 q1 = gload4(tw_end - ((size_t)1 << (n - 1)) + ((size_t)hi << (LOGT - 2)), 4 * tp);
@@ -277,7 +284,7 @@ __global__ void __launch_bounds__(1 << (LOGT - 4), TSTWO_B_WAVES) k_cfft_b(ColPt
             }
             lds_barrier();
 #pragma unroll
-            for (int j = 0; j < 4; j++) pf[j] = gload4(next + 4 * t + j * QT);   // (pointer form: the base + 32-bit offset form costs this kernel registers it does not have: +17 us)
+            for (int j = 0; j < 4; j++) pf[j] = gload4<NT>(next + 4 * t + j * QT);   // (pointer form: the base + 32-bit offset form costs this kernel registers it does not have: +17 us)
             lds_stage<GM, 8, LOGT, THREADS, false>(lds, twl, tt);              // layers LOGT-3..8
             lds_barrier();
             lds_stage<4, 4, LOGT, THREADS, false>(lds, twl, tt);               // layers 7..4
@@ -303,7 +310,7 @@ __global__ void __launch_bounds__(1 << (LOGT - 4), TSTWO_B_WAVES) k_cfft_b(ColPt
             }
             lds_barrier();       // last LDS access of this column: the next column's tile may overwrite it
 #pragma unroll
-            for (int j = 0; j < 4; j++) gstore4(data + e0 + 256 * j, o[j]);
+            for (int j = 0; j < 4; j++) gstore4<NT>(data + e0 + 256 * j, o[j]);
         } else {
             u32 v[16];
             // (the lane's 64 consecutive bytes arrive as four 16-byte loads; the coalesced form with a wave-local LDS exchange,
@@ -315,7 +322,7 @@ __global__ void __launch_bounds__(1 << (LOGT - 4), TSTWO_B_WAVES) k_cfft_b(ColPt
             for (int m = 0; m < 16; m++) lds[pad(16 * tt) + m] = v[m];
             lds_wave_fence();    // the next stage reads the blocks this wave has just written
 #pragma unroll
-            for (int j = 0; j < 4; j++) pf[j] = gload4(next, 16 * t + 4 * j);
+            for (int j = 0; j < 4; j++) pf[j] = gload4<NT>(next, 16 * t + 4 * j);
             lds_stage<4, 4, LOGT, THREADS, true>(lds, twl, tt);
             lds_barrier();
             lds_stage<GM, 8, LOGT, THREADS, true>(lds, twl, tt);
@@ -330,10 +337,21 @@ __global__ void __launch_bounds__(1 << (LOGT - 4), TSTWO_B_WAVES) k_cfft_b(ColPt
             top_layers<true, true>(x, ta, tb0, tb1);
             if (scale) scale16(x, scale);
 #pragma unroll
-            for (int j = 0; j < 4; j++) gstore4(data, 4 * t + j * QT, x[j]);
+            for (int j = 0; j < 4; j++) gstore4<NT>(data, 4 * t + j * QT, x[j]);
         }
     }
     }   // runs of one tile
+}
+template <bool INV, int LOGT, bool OOP = false>
+__global__ void __launch_bounds__(1 << (LOGT - 4), TSTWO_B_WAVES) k_cfft_b(ColPtrs cols, typename SrcTable<OOP ? 1 : 0>::type src, u32 n_cols, u32 total_items,
+                                                 u32 n, const u32 *__restrict__ tw_end, u32 scale) {
+    cfft_b_runs<INV, LOGT, OOP, false>(cols, src, n_cols, total_items, n, tw_end, scale);
+}
+// the forward pass of a column set far larger than the cache: tile loads and stores with `nt`
+template <int LOGT>
+__global__ void __launch_bounds__(1 << (LOGT - 4), TSTWO_B_WAVES) k_cfft_b_stream(ColPtrs cols, NoSrc src, u32 n_cols, u32 total_items, u32 n,
+                                                                                const u32 *__restrict__ tw_end, u32 scale) {
+    cfft_b_runs<false, LOGT, false, true>(cols, src, n_cols, total_items, n, tw_end, scale);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -353,9 +371,9 @@ __global__ void __launch_bounds__(1 << (LOGT - 4), TSTWO_B_WAVES) k_cfft_b(ColPt
 #else
 #define TSTWO_A_BOUNDS(LOGT, V) __launch_bounds__((1 << ((LOGT) - 4)) / (V))
 #endif
-template <bool INV, int K, int EXT = 0, int LOGT = 14, int V = (LOGT == 15 ? 2 : 1)>
-__global__ void TSTWO_A_BOUNDS(LOGT, V) k_cfft_a(ColPtrs cols, typename SrcTable<EXT>::type src, u32 n_cols, u32 total_items, u32 n,
-                                                   u32 lo, const u32 *__restrict__ tw_end, u32 scale) {
+template <bool INV, int K, int EXT, int LOGT, int V, bool NT>
+__device__ __forceinline__ void cfft_a_runs(const ColPtrs &cols, const typename SrcTable<EXT>::type &src, u32 n_cols, u32 total_items, u32 n,
+                                            u32 lo, const u32 *__restrict__ tw_end, u32 scale) {
     static_assert(EXT == 0 || (!INV && K >= 2 && EXT <= 2), "fused extension: forward pass with two register layers");
     static_assert(LOGT >= 12 && LOGT <= 15 && LOGT - K >= 4, "strided tile: rows of at least 16 words");
     static_assert((V == 1 || V == 2) && (1 << (LOGT - 4)) / V <= 1024, "virtual lanes (16 words each) per lane");
@@ -446,15 +464,15 @@ __global__ void TSTWO_A_BOUNDS(LOGT, V) k_cfft_a(ColPtrs cols, typename SrcTable
                 const u32 vt = t + (u32)v * THREADS;
                 if constexpr (SB) {
 #pragma unroll
-                    for (int j = 0; j < (EXT == 0 ? 4 : EXT == 1 ? 2 : 1); j++) pf[v][j] = gload4(d + u_quarter(v, j), lane4);
+                    for (int j = 0; j < (EXT == 0 ? 4 : EXT == 1 ? 2 : 1); j++) pf[v][j] = gload4<NT>(d + u_quarter(v, j), lane4);
                 } else if constexpr (EXT == 0) {
 #pragma unroll
-                    for (int j = 0; j < 4; j++) pf[v][j] = gload4(d + goff(4 * vt + j * QT));
+                    for (int j = 0; j < 4; j++) pf[v][j] = gload4<NT>(d + goff(4 * vt + j * QT));
                 } else if constexpr (EXT == 1) {
-                    pf[v][0] = gload4(d + goff(4 * vt));
-                    pf[v][1] = gload4(d + goff(4 * vt + QT));
+                    pf[v][0] = gload4<NT>(d + goff(4 * vt));
+                    pf[v][1] = gload4<NT>(d + goff(4 * vt + QT));
                 } else {
-                    pf[v][0] = gload4(d + goff(4 * vt));
+                    pf[v][0] = gload4<NT>(d + goff(4 * vt));
                 }
             }
         };
@@ -487,8 +505,8 @@ __global__ void TSTWO_A_BOUNDS(LOGT, V) k_cfft_a(ColPtrs cols, typename SrcTable
                     for (int j = 0; j < 4; j++) {
                         uint4 x = pf[v][j];
                         if (INV && scale) x = scale4(x, scale);
-                        if constexpr (SB) gstore4(data + u_quarter(v, j), lane4, x);
-                        else gstore4(data + goff(4 * (t + (u32)v * THREADS) + j * QT), x);
+                        if constexpr (SB) gstore4<NT>(data + u_quarter(v, j), lane4, x);
+                        else gstore4<NT>(data + goff(4 * (t + (u32)v * THREADS) + j * QT), x);
                     }
                 load_tile(next);
             } else {
@@ -526,8 +544,8 @@ __global__ void TSTWO_A_BOUNDS(LOGT, V) k_cfft_a(ColPtrs cols, typename SrcTable
                         for (int g = 0; g < NG; g++)
 #pragma unroll
                             for (int m = 0; m < (1 << G2); m++) {
-                                if constexpr (SB) gstore1(data + u_final(v, g, m), lane_f, w[g][m]);
-                                else gstore1(data + goff(e_final(tt + (u32)v * THREADS, g, m)), w[g][m]);
+                                if constexpr (SB) gstore1<NT>(data + u_final(v, g, m), lane_f, w[g][m]);
+                                else gstore1<NT>(data + goff(e_final(tt + (u32)v * THREADS, g, m)), w[g][m]);
                             }
                     }
                 }
@@ -547,7 +565,7 @@ __global__ void TSTWO_A_BOUNDS(LOGT, V) k_cfft_a(ColPtrs cols, typename SrcTable
                 for (int g = 0; g < NG; g++)
 #pragma unroll
                     for (int m = 0; m < (1 << G2); m++)
-                        pfs[v][g * (1 << G2) + m] = SB ? gload1(d + u_final(v, g, m), lane_f) : gload1(d, goff(e_final(tt + (u32)v * THREADS, g, m)));
+                        pfs[v][g * (1 << G2) + m] = SB ? gload1<NT>(d + u_final(v, g, m), lane_f) : gload1<NT>(d, goff(e_final(tt + (u32)v * THREADS, g, m)));
         }
         stage_twiddles();
         lds_barrier();       // the inverse reads the heap in its first stage, before any other barrier
@@ -578,7 +596,7 @@ __global__ void TSTWO_A_BOUNDS(LOGT, V) k_cfft_a(ColPtrs cols, typename SrcTable
                 for (int g = 0; g < NG; g++)
 #pragma unroll
                     for (int m = 0; m < (1 << G2); m++)
-                        pfs[v][g * (1 << G2) + m] = SB ? gload1(next + u_final(v, g, m), lane_f) : gload1(next, goff(e_final(tt + (u32)v * THREADS, g, m)));
+                        pfs[v][g * (1 << G2) + m] = SB ? gload1<NT>(next + u_final(v, g, m), lane_f) : gload1<NT>(next, goff(e_final(tt + (u32)v * THREADS, g, m)));
             if constexpr (G1 > 0) {
 #pragma unroll
                 for (int v = 0; v < V; v++) lds_stage<G1, C + 4, LOGT, VT, true>(lds, twl, t + (u32)v * THREADS);
@@ -597,13 +615,24 @@ __global__ void TSTWO_A_BOUNDS(LOGT, V) k_cfft_a(ColPtrs cols, typename SrcTable
                 if (scale) scale16(x, scale);
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    if constexpr (SB) gstore4(data + u_quarter(v, j), lane4, x[j]);
-                    else gstore4(data, goff(4 * (t + (u32)v * THREADS) + j * QT), x[j]);
+                    if constexpr (SB) gstore4<NT>(data + u_quarter(v, j), lane4, x[j]);
+                    else gstore4<NT>(data, goff(4 * (t + (u32)v * THREADS) + j * QT), x[j]);
                 }
             }
         }
     }
     }   // runs of one tile
+}
+template <bool INV, int K, int EXT = 0, int LOGT = 14, int V = (LOGT == 15 ? 2 : 1)>
+__global__ void TSTWO_A_BOUNDS(LOGT, V) k_cfft_a(ColPtrs cols, typename SrcTable<EXT>::type src, u32 n_cols, u32 total_items, u32 n,
+                                                   u32 lo, const u32 *__restrict__ tw_end, u32 scale) {
+    cfft_a_runs<INV, K, EXT, LOGT, V, false>(cols, src, n_cols, total_items, n, lo, tw_end, scale);
+}
+// the forward pass on the 2^15 tile for a column set far larger than the cache (k_cfft_b_stream)
+template <int K>
+__global__ void TSTWO_A_BOUNDS(15, 2) k_cfft_a_stream(ColPtrs cols, NoSrc src, u32 n_cols, u32 total_items, u32 n, u32 lo,
+                                                      const u32 *__restrict__ tw_end, u32 scale) {
+    cfft_a_runs<false, K, 0, 15, 2, true>(cols, src, n_cols, total_items, n, lo, tw_end, scale);
 }
 
 }  // namespace fast

@@ -139,44 +139,63 @@ typedef u32 u32x2_t __attribute__((ext_vector_type(2)));
 // The zero-inverse flag lives in host-coherent memory: a plain store of 1 (every writer writes the same value, and only when an
 // input WAS zero — the rare, failing case) is visible to the host once the kernel has completed.
 __device__ __forceinline__ void raise_flag(u32 *flag) { *(volatile TSTWO_GLOBAL u32 *)flag = 1u; }
+// NT: the non-temporal cache policy (`nt`), for words that are read once and written once per pass (the CFFT tiles).
+template <bool NT, class V>
+__device__ __forceinline__ V gload_as(const TSTWO_GLOBAL V *p) {
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+template <bool NT, class V>
+__device__ __forceinline__ void gstore_as(TSTWO_GLOBAL V *p, V v) {
+    if constexpr (NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+template <bool NT = false>
 __device__ __forceinline__ uint4 gload4(const u32 *p) {
-    const u32x4_t v = *(const TSTWO_GLOBAL u32x4_t *)p;
+    const u32x4_t v = gload_as<NT>((const TSTWO_GLOBAL u32x4_t *)p);
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ uint2 gload2(const u32 *p) {
     const u32x2_t v = *(const TSTWO_GLOBAL u32x2_t *)p;
     return make_uint2(v.x, v.y);
 }
-__device__ __forceinline__ u32 gload1(const u32 *p) { return *(const TSTWO_GLOBAL u32 *)p; }
+template <bool NT = false>
+__device__ __forceinline__ u32 gload1(const u32 *p) { return gload_as<NT>((const TSTWO_GLOBAL u32 *)p); }
+template <bool NT = false>
 __device__ __forceinline__ void gstore4(u32 *p, uint4 x) {
     u32x4_t v;
     v.x = x.x; v.y = x.y; v.z = x.z; v.w = x.w;
-    *(TSTWO_GLOBAL u32x4_t *)p = v;
+    gstore_as<NT>((TSTWO_GLOBAL u32x4_t *)p, v);
 }
-__device__ __forceinline__ void gstore1(u32 *p, u32 x) { *(TSTWO_GLOBAL u32 *)p = x; }
+template <bool NT = false>
+__device__ __forceinline__ void gstore1(u32 *p, u32 x) { gstore_as<NT>((TSTWO_GLOBAL u32 *)p, x); }
 // The same with the address split into a (wave-uniform) base and a 32-bit WORD offset below 2^30: the byte offset is formed in
 // 32 bits, so the access is `global_load/store v, v_off, s[base]` — no 64-bit address pair per access in VGPRs and no
 // v_lshl_add_u64 / v_add_co + v_addc (heavy VALU) to build one.
+template <bool NT = false>
 __device__ __forceinline__ uint4 gload4(const u32 *base, u32 word_off) {
-    const u32x4_t v = *(const TSTWO_GLOBAL u32x4_t *)((const TSTWO_GLOBAL char *)base + (word_off << 2));
+    const u32x4_t v = gload_as<NT>((const TSTWO_GLOBAL u32x4_t *)((const TSTWO_GLOBAL char *)base + (word_off << 2)));
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ uint2 gload2(const u32 *base, u32 word_off) {
     const u32x2_t v = *(const TSTWO_GLOBAL u32x2_t *)((const TSTWO_GLOBAL char *)base + (word_off << 2));
     return make_uint2(v.x, v.y);
 }
-__device__ __forceinline__ u32 gload1(const u32 *base, u32 word_off) { return *(const TSTWO_GLOBAL u32 *)((const TSTWO_GLOBAL char *)base + (word_off << 2)); }
+template <bool NT = false>
+__device__ __forceinline__ u32 gload1(const u32 *base, u32 word_off) { return gload_as<NT>((const TSTWO_GLOBAL u32 *)((const TSTWO_GLOBAL char *)base + (word_off << 2))); }
+template <bool NT = false>
 __device__ __forceinline__ void gstore4(u32 *base, u32 word_off, uint4 x) {
     u32x4_t v;
     v.x = x.x; v.y = x.y; v.z = x.z; v.w = x.w;
-    *(TSTWO_GLOBAL u32x4_t *)((TSTWO_GLOBAL char *)base + (word_off << 2)) = v;
+    gstore_as<NT>((TSTWO_GLOBAL u32x4_t *)((TSTWO_GLOBAL char *)base + (word_off << 2)), v);
 }
 __device__ __forceinline__ void gstore2(u32 *base, u32 word_off, uint2 x) {
     u32x2_t v;
     v.x = x.x; v.y = x.y;
     *(TSTWO_GLOBAL u32x2_t *)((TSTWO_GLOBAL char *)base + (word_off << 2)) = v;
 }
-__device__ __forceinline__ void gstore1(u32 *base, u32 word_off, u32 x) { *(TSTWO_GLOBAL u32 *)((TSTWO_GLOBAL char *)base + (word_off << 2)) = x; }
+template <bool NT = false>
+__device__ __forceinline__ void gstore1(u32 *base, u32 word_off, u32 x) { gstore_as<NT>((TSTWO_GLOBAL u32 *)((TSTWO_GLOBAL char *)base + (word_off << 2)), x); }
 // Column pointer i.  Written as a branch, not as `c.ext ? c.ext[i] : c.p[i]`: the compiler merged that into ONE load through a
 // selected generic address — a flat_load for the pointer and flat_loads for every column access derived from it.
 __device__ __forceinline__ u32 *colp(const ColPtrs &c, u32 i) {
