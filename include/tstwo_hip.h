@@ -536,6 +536,23 @@ int tstwo_air_constraint_quotients(uint32_t kind, const uint32_t *const *cols, s
 int tstwo_air_eval_program(const uint32_t *const *cols, size_t n_cols, uint32_t trace_log_size, uint32_t log_expand,
                            const uint32_t *program, size_t program_len, const uint32_t *coeffs, size_t n_constraints,
                            const uint32_t *denom_inv, uint32_t *const accum[4]);
+/* The same programs evaluated on the trace domain itself into output columns (the numerators and denominator terms of a LogUp
+ * interaction trace derived from `evaluate`: tstwo_amd/logup.py derive_interaction_trace).
+ *   cols: n_cols device columns of 2^log_size M31 words on CanonicCoset(log_size).circle_domain(), bit-reversed order (the
+ *   committed trace: main columns, then preprocessed ones, named by position);  out: n_out device columns of the same length,
+ *   each written with canonical M31 values;  1 <= log_size <= 28;  1 <= n_out <= TSTWO_AIR_COLUMNS_MAX_OUT.
+ * Program: the encoding and limits of tstwo_air_eval_program, with
+ *   TSTWO_AIR_OP_STORE  out[w1][r] = r[x]; dst ignored; writes no register.  Every output index < n_out is stored exactly once.
+ *   TSTWO_AIR_OP_ACC is a bad opcode here (as TSTWO_AIR_OP_STORE is in tstwo_air_eval_program).
+ *   TSTWO_AIR_OP_LOAD at offset o reads the row whose point is o steps of CanonicCoset(log_size) away: in coset order, row
+ *   (k + o) mod 2^log_size (offset_bit_reversed_circle_domain_index with eval_log == trace_log).
+ * An `out` pointer equal to a `cols` pointer (or to another `out` pointer) is refused: loads at offsets read rows that other
+ * lanes store.  Every limit is checked (TSTWO_ERR_BAD_ARG, text in tstwo_last_error, prefix "air columns: ").  The program is
+ * uploaded through the small-upload ring: refused during graph capture.  Asynchronous. */
+#define TSTWO_AIR_OP_STORE 8
+#define TSTWO_AIR_COLUMNS_MAX_OUT 64
+int tstwo_air_eval_columns(const uint32_t *const *cols, size_t n_cols, uint32_t log_size, const uint32_t *program,
+                           size_t program_len, uint32_t *const *out, size_t n_out);
 
 /* ---------------------------------------------------------------- LogUp interaction trace
  * Rust stwo constraint_framework/logup.rs (LogupTraceGenerator, LogupColGenerator); tstwo_amd/logup.py drives it.

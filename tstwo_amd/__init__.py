@@ -38,9 +38,11 @@ from .poseidon import (DeviceFeltLayer, FieldElement252, HipPoseidon252MerkleOps
 from .air import (ColumnAccumulator, ComponentProvers, Components, DomainEvaluationAccumulator,  # noqa: F401
                   PointEvaluationAccumulator, Trace, TraceLocationAllocator, coset_vanishing, generate_wide_fib_trace)
 from .constraint_framework import (FrameworkComponent, MulAddComponent, MulAddEval, PermutationEval,  # noqa: F401
-                                   RangeCheckTableEval, RangeCheckValuesEval, WideFibonacciComponent, WideFibonacciEval)
+                                   RangeCheckTableEval, RangeCheckValuesEval, RelationEvaluator, StateMachineEval,
+                                   WideFibonacciComponent, WideFibonacciEval, compile_columns, evaluate_columns,
+                                   state_machine_trace)
 from .logup import (INTERACTION_TRACE_IDX, LogupColGenerator, LogupTraceGenerator, LookupElements,  # noqa: F401
-                    RelationEntry)
+                    RelationEntry, derive_interaction_trace, deriveInteractionTrace)
 from .prover import (ConstraintsNotSatisfied, InvalidLogupSum, InvalidStructure, OodsNotMatching, StarkProof, prove,  # noqa: F401
                      verify)
 

@@ -168,6 +168,7 @@ _SIGS = {
     "tstwo_air_wide_fib_trace": [vp, vp, C.c_uint32, C.POINTER(vp), C.c_size_t],
     "tstwo_air_constraint_quotients": [C.c_uint32, C.POINTER(vp), C.c_size_t, C.c_uint32, C.c_uint32, u32p, C.c_size_t, u32p, P4],
     "tstwo_air_eval_program": [C.POINTER(vp), C.c_size_t, C.c_uint32, C.c_uint32, u32p, C.c_size_t, u32p, C.c_size_t, u32p, P4],
+    "tstwo_air_eval_columns": [C.POINTER(vp), C.c_size_t, C.c_uint32, u32p, C.c_size_t, C.POINTER(vp), C.c_size_t],
     "tstwo_logup_column": [C.POINTER(LogupFrac), C.c_size_t, C.POINTER(vp), C.c_uint32, P4],
     "tstwo_logup_finalize_last": [P4, C.c_uint32, u32p],
 }

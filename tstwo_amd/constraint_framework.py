@@ -8,6 +8,9 @@ A component is a FrameworkComponent of an eval, an object with `log_size()`, `ma
                     (same column and offset) and identical sub-expressions are computed once, registers are reused after their
                     last use, and the number of live registers is bounded by MAX_REGS;
   PointEvaluator    the constraints over QM31 at the out-of-domain point (the verifier, and the prover's sanity check).
+A fourth, RelationEvaluator, keeps the relation entries of `evaluate` as they were added (relation, multiplicity, values) and
+their batching: logup.derive_interaction_trace builds the interaction trace from them, with compile_columns / evaluate_columns
+(tstwo_air_eval_columns) for every multiplicity or value that is an expression of columns.
 The prover evaluates a component's constraints on the whole evaluation domain with one launch: WideFibonacciEval and MulAddEval
 (exactly these types, not subclasses) run on the hand-written kernel of tstwo_air_constraint_quotients, every other eval on the
 program interpreter.  WideFibonacciComponent and MulAddComponent are FrameworkComponents of those two evals, as in Rust.
@@ -17,7 +20,7 @@ The main trace (ORIGINAL_TRACE_IDX) is read at row offsets; preprocessed columns
 columns per secure column, the last one at offsets -1 and 0) and add secure-field (QM31) constraints.  The program path lowers a
 secure value to its 4 base coordinates (SecureExpr): a secure constraint is 4 ACCs whose coefficients are c, c i, c u, c iu for
 its random coefficient c, so the interpreter and its program encoding stay base-field.  The interaction trace itself is built on
-the device by logup.LogupTraceGenerator.
+the device by logup.LogupTraceGenerator, written by hand or derived from `evaluate` (logup.derive_interaction_trace).
 """
 from __future__ import annotations
 
@@ -35,8 +38,9 @@ from .logup import INTERACTION_TRACE_IDX, LogupTraceGenerator, LookupElements, R
 from .poly import evaluate_polynomials
 
 # include/tstwo_hip.h TSTWO_AIR_OP_* and TSTWO_AIR_PROGRAM_MAX_*
-OP_LOAD, OP_CONST, OP_ADD, OP_SUB, OP_MUL, OP_SQR, OP_NEG, OP_ACC = range(8)
+OP_LOAD, OP_CONST, OP_ADD, OP_SUB, OP_MUL, OP_SQR, OP_NEG, OP_ACC, OP_STORE = range(9)
 MAX_INSTR, MAX_REGS, MAX_CONSTRAINTS, MAX_COLS, MAX_OFFSET = 1536, 32, 256, 4096, 64
+MAX_OUT = 64                            # TSTWO_AIR_COLUMNS_MAX_OUT
 MAX_LOG_EXPAND = 4
 
 
@@ -466,8 +470,41 @@ class ProgramEvaluator(_SymbolicEval):
         return compile_program(roots, self.n_main if n_main is None else n_main, n_pre)
 
 
+class RelationEvaluator(_SymbolicEval):
+    """Keeps what `evaluate` says about LogUp and nothing else: per add_to_relation the raw (relation, multiplicity, values), before
+    relation.combine, in `entries`; per finalize_logup_* the batch of every entry, in `batching`.  Constraints are dropped.
+    Masks are handed out as every evaluator does, so an `evaluate` written for the prover runs unchanged."""
+
+    def __init__(self):
+        super().__init__()
+        self.entries, self.batching = [], []
+
+    def add_constraint(self, expr) -> None:
+        pass
+
+    def add_to_relation(self, entry: RelationEntry) -> None:
+        super().add_to_relation(entry)
+        self.entries.append((entry.relation, entry.multiplicity, list(entry.values)))
+
+    def finalize_logup_batched(self, batching) -> None:
+        batching = [int(b) for b in batching]
+        super().finalize_logup_batched(batching)
+        self.batching = batching
+
+
+def relation_entries(eval_) -> RelationEvaluator:
+    """`evaluate` run on a RelationEvaluator.  Raises ValueError when it adds no relation entry."""
+    ev = RelationEvaluator()
+    eval_.evaluate(ev)
+    ev.check_finished()
+    if not ev.entries:
+        raise ValueError("evaluate adds no relation entries: there is no interaction trace to derive")
+    return ev
+
+
 class Program:
-    """words: 2 per instruction (include/tstwo_hip.h); n_instr, n_regs (registers used), n_constraints, n_loads."""
+    """words: 2 per instruction (include/tstwo_hip.h); n_instr, n_regs (registers used), n_constraints (the ACCs of a constraint
+    program, the STOREs of a columns program: n_out), n_loads."""
 
     def __init__(self, words, n_regs, n_constraints, n_loads):
         self.words, self.n_regs, self.n_constraints, self.n_loads = list(words), n_regs, n_constraints, n_loads
@@ -476,21 +513,25 @@ class Program:
     def n_instr(self) -> int:
         return len(self.words) // 2
 
+    @property
+    def n_out(self) -> int:
+        return self.n_constraints
+
 
 def encode(op: int, dst: int = 0, x: int = 0, w1: int = 0) -> tuple:
     return (op | (dst << 8) | (x << 16), w1 & 0xffffffff)
 
 
-def compile_program(constraints: list, n_main: int, n_pre: int = 0) -> Program:
-    """Straight-line program of the constraint DAG over the columns main (n_main), preprocessed (n_pre), interaction, in that order.
-    Nodes are merged structurally (same operation on the same merged operands;
-    loads by column and offset; constants by value).  Instructions are ordered by a depth-first walk of each constraint in turn
-    (the operand that needs more registers first), each value gets the lowest free register at its definition and frees it
-    after its last use (an instruction may write the register its last operand read).  Raises ValueError when the program
-    needs more than MAX_REGS registers or MAX_INSTR instructions."""
-    canon = {}                # structural key -> canonical node
+class Canonical:
+    """Structural merging of Expr nodes: canonical(e) is the one node that stands for every expression built like e (the same
+    operation on the same merged operands; loads by column and offset; constants by value), so `is` on canonical nodes is
+    structural equality."""
 
-    def canonical(e: Expr) -> Expr:
+    def __init__(self):
+        self.canon = {}             # structural key -> canonical node
+
+    def __call__(self, e: Expr) -> Expr:
+        canon = self.canon
         # iterative post-order: expressions can be deep chains
         stack, done = [(e, False)], {}
         while stack:
@@ -511,6 +552,31 @@ def compile_program(constraints: list, n_main: int, n_pre: int = 0) -> Program:
             done[id(n)] = canon[key]
         return done[id(e)]
 
+
+def compile_program(constraints: list, n_main: int, n_pre: int = 0) -> Program:
+    """The program of tstwo_air_eval_program: constraint k is the k-th ACC (see _compile)."""
+    program = _compile(constraints, n_main, n_pre, lambda k, r: encode(OP_ACC, 0, r))
+    if program.n_constraints > MAX_CONSTRAINTS:
+        raise ValueError(f"more than {MAX_CONSTRAINTS} constraints in one component")
+    return program
+
+
+def compile_columns(exprs: list, n_main: int, n_pre: int = 0) -> Program:
+    """The program of tstwo_air_eval_columns: expression k is stored to output column k (STORE k in place of the k-th ACC)."""
+    if not 1 <= len(exprs) <= MAX_OUT:
+        raise ValueError(f"a columns program has 1 to {MAX_OUT} outputs")
+    return _compile([Expr._lift(e) for e in exprs], n_main, n_pre, lambda k, r: encode(OP_STORE, 0, r, k))
+
+
+def _compile(constraints: list, n_main: int, n_pre: int, terminal) -> Program:
+    """Straight-line program of the DAG of `constraints` (the roots) over the columns main (n_main), preprocessed (n_pre),
+    interaction, in that order; terminal(k, register) encodes the instruction that consumes root k (ACC or STORE).
+    Nodes are merged structurally (same operation on the same merged operands;
+    loads by column and offset; constants by value).  Instructions are ordered by a depth-first walk of each constraint in turn
+    (the operand that needs more registers first), each value gets the lowest free register at its definition and frees it
+    after its last use (an instruction may write the register its last operand read).  Raises ValueError when the program
+    needs more than MAX_REGS registers or MAX_INSTR instructions."""
+    canonical = Canonical()
     roots = [canonical(c) for c in constraints]
     # registers a subtree needs (Sethi-Ullman, on the tree view of the DAG): evaluate the heavier operand first
     need = {}
@@ -558,7 +624,7 @@ def compile_program(constraints: list, n_main: int, n_pre: int = 0) -> Program:
             uses.setdefault(id(a), []).append(i)
     if len(order) > MAX_INSTR:
         raise ValueError(f"the constraints compile to {len(order)} instructions, more than {MAX_INSTR}")
-    reg, held, free, n_regs, words, n_loads = {}, {}, [], 0, [], 0      # reg: value -> register, held: register -> value
+    reg, held, free, n_regs, words, n_loads, n_done = {}, {}, [], 0, [], 0, 0   # reg: value -> register, held: register -> value
 
     def next_use(a, i):
         u = uses[id(a)]
@@ -611,7 +677,8 @@ def compile_program(constraints: list, n_main: int, n_pre: int = 0) -> Program:
             if id(a) not in reg:
                 emit_leaf(a, i, protect)
         if kind == "acc":
-            words.extend(encode(OP_ACC, 0, reg[id(n)]))
+            words.extend(terminal(n_done, reg[id(n)]))
+            n_done += 1
             release([n], i)
             continue
         if n.op in ("load", "const"):
@@ -625,8 +692,6 @@ def compile_program(constraints: list, n_main: int, n_pre: int = 0) -> Program:
         reg[id(n)], held[d] = d, n
     if len(words) // 2 > MAX_INSTR:
         raise ValueError(f"the constraints compile to {len(words) // 2} instructions, more than {MAX_INSTR}")
-    if len(roots) > MAX_CONSTRAINTS:
-        raise ValueError(f"more than {MAX_CONSTRAINTS} constraints in one component")
     return Program(words, n_regs, len(roots), n_loads)
 
 
@@ -678,7 +743,9 @@ def point_constraints(eval_, main: list, pre: list, inter: list = (), claimed_su
     eval_.evaluate(ev)
     ev.check_finished()
     return [PointValue._q(c) for c in ev.constraints]
-# ------------------------------------------------------------------ the device entry point
+
+
+# ------------------------------------------------------------------ the device entry points
 def evaluate_program(cols, trace_log_size: int, log_expand: int, program: Program, coeffs, denom_inv, accum: SecureColumnByCoords) -> None:
     """tstwo_air_eval_program: accum[r] += sum_k coeffs[k] e_k(r) * denom_inv[r >> trace_log_size] over the columns `cols`
     (HipColumns on the evaluation domain of log size trace_log_size + log_expand, bit-reversed)."""
@@ -687,6 +754,21 @@ def evaluate_program(cols, trace_log_size: int, log_expand: int, program: Progra
     dinv = L.u32x([d.value if isinstance(d, M31) else int(d) for d in denom_inv])
     L.call("tstwo_air_eval_program", L.ptr_array([c.ptr for c in cols]), len(cols), trace_log_size, log_expand, words,
            program.n_instr, cw, len(coeffs), dinv, accum.ptrs())
+
+
+def evaluate_columns(cols, log_size: int, program: Program, n_out: int) -> list:
+    """tstwo_air_eval_columns: the n_out output columns (new HipColumns of 2^log_size values) of a compile_columns program over
+    `cols`, HipColumns on CanonicCoset(log_size).circle_domain() in storage order (main, then preprocessed).  Asynchronous."""
+    from .backend import HipColumn
+    if n_out != program.n_out:
+        raise ValueError(f"the program stores {program.n_out} outputs, {n_out} were asked for")
+    n = 1 << log_size
+    if any(c.len() != n for c in cols):
+        raise ValueError("every column must hold 2^log_size values")
+    out = [HipColumn.uninitialized(n) for _ in range(n_out)]
+    L.call("tstwo_air_eval_columns", L.ptr_array([c.ptr for c in cols]), len(cols), log_size, L.u32x(program.words), program.n_instr,
+           L.ptr_array([c.ptr for c in out]), n_out)
+    return out
 
 
 # ------------------------------------------------------------------ FrameworkComponent (Rust constraint_framework/component.rs)
@@ -1025,6 +1107,41 @@ class RangeCheckValuesEval:
 
     logSize = log_size
     maxConstraintLogDegreeBound = max_constraint_log_degree_bound
+
+
+class StateMachineEval:
+    """stwo's state-machine example: columns x, y; the row uses the state (x, y) and yields the state (x + 1, y): entries
+    (+1, [x, y]) and (-1, [x + 1, y]) in one batch (finalize_logup_in_pairs).  Over the trace of state_machine_trace the sum
+    telescopes to 1 / combine([x0, y0]) - 1 / combine([x0 + 2^log, y0]).  The value x + 1 is an expression of a column: the
+    interaction trace comes from logup.derive_interaction_trace.  Degree 3: log_size + 2."""
+
+    def __init__(self, log_n_rows: int, lookup_elements: LookupElements):
+        self.log_n_rows, self.lookup_elements = log_n_rows, lookup_elements
+
+    def log_size(self) -> int:
+        return self.log_n_rows
+
+    def max_constraint_log_degree_bound(self) -> int:
+        return self.log_n_rows + 2
+
+    def evaluate(self, eval):
+        x, y = eval.next_trace_mask(), eval.next_trace_mask()
+        eval.add_to_relation(RelationEntry(self.lookup_elements, 1, [x, y]))
+        eval.add_to_relation(RelationEntry(self.lookup_elements, -1, [x + 1, y]))
+        eval.finalize_logup_in_pairs()
+        return eval
+
+    logSize = log_size
+    maxConstraintLogDegreeBound = max_constraint_log_degree_bound
+
+
+def state_machine_trace(log_n_rows: int, x0: int, y0: int):
+    """(x, y) as numpy uint32 columns in storage order: coset row k holds (x0 + k, y0)."""
+    import numpy as np
+    n = 1 << log_n_rows
+    x, y = np.empty(n, dtype=np.uint32), np.full(n, int(y0) % P, dtype=np.uint32)
+    x[_coset_positions(log_n_rows)] = ((int(x0) % P + np.arange(n, dtype=np.uint64)) % P).astype(np.uint32)
+    return x, y
 
 
 def _col(x):

@@ -8,6 +8,10 @@
 //   k_air_program<W>  any constraints, as a straight-line program (tstwo_amd/constraint_framework.py compiles a FrameworkEval's
 //     `evaluate` into it) interpreted for every row, with loads at row offsets (Rust stwo constraint_framework:
 //     next_interaction_mask with offsets, utils.rs offset_bit_reversed_circle_domain_index).
+//   k_air_columns<W>  the same programs on the trace domain itself, with STORE in place of ACC: every stored register becomes
+//     one output column (tstwo_air_eval_columns: the numerators and denominator terms of a LogUp interaction trace, derived
+//     from `evaluate` by tstwo_amd/logup.py derive_interaction_trace).  It shares the interpreter with k_air_program
+//     (fetch, exec_op, the LDS register file) and has no accumulators, coefficients or denominators.
 // Row r (bit-reversed order on CanonicCoset(trace_log + log_expand).circle_domain()):
 //   row_res = sum_i coeff_i c_i(r),   accum[r] += row_res * denom_inv[r >> trace_log]
 //
@@ -63,6 +67,14 @@ struct ProgArgs {
     Soa4 acc;
     u32 n_instr, n_rows, trace_log, eval_log, log_expand, n_denoms;
 };
+
+struct ColArgs {
+    const u32 *prog;                         // device: 2 words per instruction
+    u32 n_instr, n_rows, log;
+};
+// k_air_columns(ColPtrs cols, ColPtrs out, ColArgs): the output table is the second kernel argument (kSecondTableOff)
+static_assert(2 * sizeof(ColPtrs) + sizeof(ColArgs) <= 4096, "kernel arguments exceed 4 KiB");
+static_assert(TSTWO_AIR_COLUMNS_MAX_OUT <= kMaxColsPerLaunch, "the output table travels by value");
 
 // ---------------------------------------------------------------- shared by both kernels
 template <int W>
@@ -245,6 +257,21 @@ __device__ __forceinline__ u32 neighbour_row(u32 r, u32 eval_log, u32 log_expand
     return __builtin_bitreverse32(j) >> (32 - eval_log);
 }
 
+// The same on the trace domain itself (the eval_log == trace_log case of offset_bit_reversed_circle_domain_index): one trace step
+// crosses between the two halves of the circle domain, so the shift above does not apply.  In coset order the neighbour of row k
+// is row (k + off) mod 2^log.  With L = log - 1 and rev the bit reversal over L bits, coset row k = 2 j + odd sits at position
+// 2 t + odd where t = rev(j) for even k and ~rev(j) (over L bits) for odd k (csrc/logup.hip); the inverse is the same two steps
+// backwards, so a neighbour costs two bit reversals.
+__device__ __forceinline__ u32 rev_bits(u32 x, u32 bits) { return bits ? __builtin_bitreverse32(x) >> (32 - bits) : 0; }
+__device__ __forceinline__ u32 trace_neighbour_row(u32 r, u32 log, int off) {
+    const u32 L = log - 1, mask = (1u << L) - 1;
+    const u32 odd = r & 1, t = r >> 1;
+    const u32 k = 2 * rev_bits(odd ? ~t & mask : t, L) + odd;
+    const u32 k2 = (k + (u32)off) & ((1u << log) - 1);
+    const u32 odd2 = k2 & 1, t2 = rev_bits(k2 >> 1, L);
+    return 2 * (odd2 ? ~t2 & mask : t2) + odd2;
+}
+
 template <int W>
 __device__ __forceinline__ void lds_read(const u32 *regs, u32 reg, u32 (&v)[W]) {
     const u32 lane = threadIdx.x;
@@ -262,12 +289,75 @@ __device__ __forceinline__ void lds_write(u32 *regs, u32 reg, const u32 (&v)[W])
     else regs[reg * kWave + lane] = v[0];
 }
 
+// One instruction, fetched with scalar loads (wave-uniform program counter): w0 = op | dst << 8 | x << 16, w1.
+struct Instr { u32 op, dst, x, w1; };
+__device__ __forceinline__ Instr fetch(k32 prog, u32 pc) {
+    const u32 w0 = prog[uni(2 * pc)], w1 = prog[uni(2 * pc + 1)];
+    return {w0 & 0xffu, (w0 >> 8) & 0xffu, w0 >> 16, w1};
+}
+
+// The row a LOAD at a non-zero offset reads: on the evaluation domain (k_air_program) or on the trace domain (k_air_columns).
+struct EvalNeighbour {
+    u32 eval_log, log_expand;
+    __device__ __forceinline__ u32 operator()(u32 r, int off) const { return neighbour_row(r, eval_log, log_expand, off); }
+};
+struct TraceNeighbour {
+    u32 log;
+    __device__ __forceinline__ u32 operator()(u32 r, int off) const { return trace_neighbour_row(r, log, off); }
+};
+
+// Every instruction that writes a register (LOAD, CONST, ADD, SUB, MUL, SQR, NEG): r[dst] of rows [row, row + W).  The kernels
+// handle their own terminal instruction (ACC, STORE) before they come here.
+template <int W, class Neighbour>
+__device__ __forceinline__ void exec_op(const ColPtrs &cols, u32 *regs, const Instr &in, u32 row, const Neighbour &nb) {
+    const u32 op = in.op, x = in.x, w1 = in.w1;
+    u32 v[W];
+    if (op == TSTWO_AIR_OP_LOAD) {
+        const u32 *col = colp_u(cols, x);
+        const int off = (int)w1;
+        if (off == 0) {
+            load_rows<W>(col, row, v);
+        } else {
+#pragma unroll
+            for (int e = 0; e < W; e++) v[e] = gload1(col, nb(row + e, off));
+        }
+    } else if (op == TSTWO_AIR_OP_CONST) {
+#pragma unroll
+        for (int e = 0; e < W; e++) v[e] = w1;
+    } else {
+        u32 p[W];
+        lds_read<W>(regs, x, p);
+        if (op == TSTWO_AIR_OP_SQR) {
+#pragma unroll
+            for (int e = 0; e < W; e++) v[e] = m31_sqr(p[e]);
+        } else if (op == TSTWO_AIR_OP_NEG) {
+#pragma unroll
+            for (int e = 0; e < W; e++) v[e] = m31_neg(p[e]);
+        } else {
+            u32 q[W];
+            lds_read<W>(regs, w1, q);
+            if (op == TSTWO_AIR_OP_ADD) {
+#pragma unroll
+                for (int e = 0; e < W; e++) v[e] = m31_add(p[e], q[e]);
+            } else if (op == TSTWO_AIR_OP_SUB) {
+#pragma unroll
+                for (int e = 0; e < W; e++) v[e] = m31_sub(p[e], q[e]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < W; e++) v[e] = m31_mul(p[e], q[e]);
+            }
+        }
+    }
+    lds_write<W>(regs, in.dst, v);
+}
+
 template <int W>
 __global__ void __launch_bounds__(kWave) k_air_program(ColPtrs cols, ProgArgs a) {
     extern __shared__ u32 regs[];
     const k32 prog = (k32)a.prog;
     const u32 coeff_base = 2 * a.n_instr;
     const u32 stride = gridDim.x * kWave;
+    const EvalNeighbour nb = {a.eval_log, a.log_expand};
     for (u32 t = blockIdx.x * kWave + threadIdx.x; t < a.n_rows / W; t += stride) {
         const u32 row = t * W;
         u64 acc[W][4];
@@ -278,23 +368,10 @@ __global__ void __launch_bounds__(kWave) k_air_program(ColPtrs cols, ProgArgs a)
         u32 n_acc = 0;
 #pragma unroll 1
         for (u32 pc = 0; pc < a.n_instr; pc++) {
-            const u32 w0 = prog[uni(2 * pc)], w1 = prog[uni(2 * pc + 1)];
-            const u32 op = w0 & 0xffu, dst = (w0 >> 8) & 0xffu, x = w0 >> 16;
-            u32 v[W];
-            if (op == TSTWO_AIR_OP_LOAD) {
-                const u32 *col = colp_u(cols, x);
-                const int off = (int)w1;
-                if (off == 0) {
-                    load_rows<W>(col, row, v);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < W; e++) v[e] = gload1(col, neighbour_row(row + e, a.eval_log, a.log_expand, off));
-                }
-            } else if (op == TSTWO_AIR_OP_CONST) {
-#pragma unroll
-                for (int e = 0; e < W; e++) v[e] = w1;
-            } else if (op == TSTWO_AIR_OP_ACC) {
-                lds_read<W>(regs, x, v);
+            const Instr in = fetch(prog, pc);
+            if (in.op == TSTWO_AIR_OP_ACC) {
+                u32 v[W];
+                lds_read<W>(regs, in.x, v);
                 const u32 k = uni(coeff_base + 4 * n_acc);
                 const u32 q0 = prog[k], q1 = prog[k + 1], q2 = prog[k + 2], q3 = prog[k + 3];
 #pragma unroll
@@ -306,33 +383,37 @@ __global__ void __launch_bounds__(kWave) k_air_program(ColPtrs cols, ProgArgs a)
                 }
                 if ((++n_acc & 3) == 0) fold_all<W>(acc);
                 continue;
-            } else {
-                u32 p[W];
-                lds_read<W>(regs, x, p);
-                if (op == TSTWO_AIR_OP_SQR) {
-#pragma unroll
-                    for (int e = 0; e < W; e++) v[e] = m31_sqr(p[e]);
-                } else if (op == TSTWO_AIR_OP_NEG) {
-#pragma unroll
-                    for (int e = 0; e < W; e++) v[e] = m31_neg(p[e]);
-                } else {
-                    u32 q[W];
-                    lds_read<W>(regs, w1, q);
-                    if (op == TSTWO_AIR_OP_ADD) {
-#pragma unroll
-                        for (int e = 0; e < W; e++) v[e] = m31_add(p[e], q[e]);
-                    } else if (op == TSTWO_AIR_OP_SUB) {
-#pragma unroll
-                        for (int e = 0; e < W; e++) v[e] = m31_sub(p[e], q[e]);
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < W; e++) v[e] = m31_mul(p[e], q[e]);
-                    }
-                }
             }
-            lds_write<W>(regs, dst, v);
+            exec_op<W>(cols, regs, in, row, nb);
         }
         TSTWO_AIR_ADD_ROWS(W, a, row, acc);
+    }
+}
+
+// The interpreter on the trace domain: STORE writes r[x] of the lane's W rows to output column w1 (16 bytes per lane at W = 4,
+// coalesced: a wave writes 1 KiB of one column).  An output is never an input (the host refuses it), so a load at an offset
+// never reads a row another lane has stored.
+template <int W>
+__global__ void __launch_bounds__(kWave) k_air_columns(ColPtrs cols, ColPtrs out, ColArgs a) {
+    extern __shared__ u32 regs[];
+    const k32 prog = (k32)a.prog;
+    const u32 stride = gridDim.x * kWave;
+    const TraceNeighbour nb = {a.log};
+    for (u32 t = blockIdx.x * kWave + threadIdx.x; t < a.n_rows / W; t += stride) {
+        const u32 row = t * W;
+#pragma unroll 1
+        for (u32 pc = 0; pc < a.n_instr; pc++) {
+            const Instr in = fetch(prog, pc);
+            if (in.op == TSTWO_AIR_OP_STORE) {
+                u32 v[W];
+                lds_read<W>(regs, in.x, v);
+                u32 *dst = colp_u<kSecondTableOff>(out, in.w1);
+                if constexpr (W == 4) gstore4(dst, row, make_uint4(v[0], v[1], v[2], v[3]));
+                else gstore1(dst, row, v[0]);
+                continue;
+            }
+            exec_op<W>(cols, regs, in, row, nb);
+        }
     }
 }
 
@@ -373,10 +454,61 @@ int take_coeffs_and_denoms(const u32 *coeffs, size_t n_constraints, u32 *coeff_d
 }
 
 // W = 4 rows per lane when the rows split into fours and every column and accumulator is 16-byte aligned
-bool four_rows_per_lane(u32 n_rows, const u32 *const *cols, size_t n_cols, u32 *const accum[4]) {
-    bool vec = n_rows % 4 == 0 && table_aligned16(cols, n_cols);
-    for (int j = 0; j < 4; j++) vec = vec && aligned16(accum[j]);
-    return vec;
+// (for tstwo_air_eval_columns: its n_out output columns)
+bool four_rows_per_lane(u32 n_rows, const u32 *const *cols, size_t n_cols, u32 *const *accum, size_t n_accum) {
+    return n_rows % 4 == 0 && table_aligned16(cols, n_cols) && table_aligned16((const u32 *const *)accum, n_accum);
+}
+
+// Validates every instruction of a straight-line program: opcodes, registers (each read one written before), columns, offsets,
+// constants.  `terminal` is the entry's own opcode that reads r[x] and writes no register (ACC or STORE; the other one is a bad
+// opcode); on_terminal(w1) checks and counts it.  n_regs: the highest register written + 1.  `prefix` starts each error text.
+template <class F>
+int check_program(const char *prefix, const u32 *program, size_t program_len, size_t n_cols, u32 terminal, u32 &n_regs, F on_terminal) {
+    const std::string pre(prefix);
+    bool written[TSTWO_AIR_PROGRAM_MAX_REGS] = {};
+    n_regs = 0;
+    auto reg_ok = [&](u32 reg) { return reg < TSTWO_AIR_PROGRAM_MAX_REGS && written[reg]; };
+    for (size_t pc = 0; pc < program_len; pc++) {
+        const u32 w0 = program[2 * pc], w1 = program[2 * pc + 1];
+        const u32 op = w0 & 0xffu, dst = (w0 >> 8) & 0xffu, x = w0 >> 16;
+        switch (op) {
+            case TSTWO_AIR_OP_LOAD: {
+                if (x >= n_cols) return bad(pre + "column out of range");
+                const int off = (int)w1;
+                if (off > TSTWO_AIR_PROGRAM_MAX_OFFSET || off < -TSTWO_AIR_PROGRAM_MAX_OFFSET) return bad(pre + "row offset beyond the limit");
+                break;
+            }
+            case TSTWO_AIR_OP_CONST:
+                if (w1 >= M31_P) return bad(pre + "constant out of range");
+                break;
+            case TSTWO_AIR_OP_ADD: case TSTWO_AIR_OP_SUB: case TSTWO_AIR_OP_MUL:
+                if (!reg_ok(x) || !reg_ok(w1)) return bad(pre + "register out of range or read before written");
+                break;
+            case TSTWO_AIR_OP_SQR: case TSTWO_AIR_OP_NEG:
+                if (!reg_ok(x)) return bad(pre + "register out of range or read before written");
+                break;
+            case TSTWO_AIR_OP_ACC: case TSTWO_AIR_OP_STORE:
+                if (op != terminal) return bad(pre + "bad opcode");
+                if (!reg_ok(x)) return bad(pre + "register out of range or read before written");
+                if (int rc = on_terminal(w1)) return rc;
+                continue;                   // writes no register
+            default:
+                return bad(pre + "bad opcode");
+        }
+        if (dst >= TSTWO_AIR_PROGRAM_MAX_REGS) return bad(pre + "register out of range or read before written");
+        written[dst] = true;
+        if (dst + 1 > n_regs) n_regs = dst + 1;
+    }
+    return TSTWO_OK;
+}
+
+// The launch shape of both interpreter kernels: one-wave workgroups, n_regs KiB of LDS at W = 4, at most n_cus * 32 workgroups
+// (the kernels stride over the rest).
+size_t interpreter_lds(u32 n_regs, bool vec) { return (size_t)(n_regs ? n_regs : 1) * kWave * (vec ? 4 : 1) * sizeof(u32); }
+unsigned interpreter_grid(u32 n_rows, bool vec) {
+    unsigned grid = ceil_div((size_t)n_rows / (vec ? 4 : 1), kWave);
+    const unsigned cap = (unsigned)ctx().n_cus * 32;
+    return grid > cap ? cap : grid;
 }
 
 template <int KIND>
@@ -431,7 +563,7 @@ int tstwo_air_constraint_quotients(u32 kind, const u32 *const *cols, size_t n_co
     a.n_rows = 1u << (trace_log_size + log_expand);
     ColPtrs cp;
     if (int rc = fill_col_table(cp, cols, n_cols, 0)) return rc;
-    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, accum);
+    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, accum, 4);
     return kind == TSTWO_AIR_WIDE_FIB ? launch_quotients<TSTWO_AIR_WIDE_FIB>(cp, a, vec) : launch_quotients<TSTWO_AIR_MUL_ADD>(cp, a, vec);
 }
 
@@ -448,41 +580,9 @@ int tstwo_air_eval_program(const u32 *const *cols, size_t n_cols, u32 trace_log_
     TSTWO_REQUIRE_TABLE(accum, 4);
     // the program and coefficient words travel through the small-upload ring, which a captured graph cannot replay
     if (stream_is_capturing()) return bad("host-array upload during graph capture (the air program and its coefficients cannot be recorded)");
-    // validate every instruction: opcodes, registers (each read one written before), columns, offsets, constants; count ACCs
-    bool written[TSTWO_AIR_PROGRAM_MAX_REGS] = {};
     u32 n_regs = 0;
     size_t n_acc = 0;
-    auto reg_ok = [&](u32 reg) { return reg < TSTWO_AIR_PROGRAM_MAX_REGS && written[reg]; };
-    for (size_t pc = 0; pc < program_len; pc++) {
-        const u32 w0 = program[2 * pc], w1 = program[2 * pc + 1];
-        const u32 op = w0 & 0xffu, dst = (w0 >> 8) & 0xffu, x = w0 >> 16;
-        switch (op) {
-            case TSTWO_AIR_OP_LOAD: {
-                if (x >= n_cols) return bad("air program: column out of range");
-                const int off = (int)w1;
-                if (off > TSTWO_AIR_PROGRAM_MAX_OFFSET || off < -TSTWO_AIR_PROGRAM_MAX_OFFSET) return bad("air program: row offset beyond the limit");
-                break;
-            }
-            case TSTWO_AIR_OP_CONST:
-                if (w1 >= M31_P) return bad("air program: constant out of range");
-                break;
-            case TSTWO_AIR_OP_ADD: case TSTWO_AIR_OP_SUB: case TSTWO_AIR_OP_MUL:
-                if (!reg_ok(x) || !reg_ok(w1)) return bad("air program: register out of range or read before written");
-                break;
-            case TSTWO_AIR_OP_SQR: case TSTWO_AIR_OP_NEG:
-                if (!reg_ok(x)) return bad("air program: register out of range or read before written");
-                break;
-            case TSTWO_AIR_OP_ACC:
-                if (!reg_ok(x)) return bad("air program: register out of range or read before written");
-                n_acc++;
-                continue;                   // writes no register
-            default:
-                return bad("air program: bad opcode");
-        }
-        if (dst >= TSTWO_AIR_PROGRAM_MAX_REGS) return bad("air program: register out of range or read before written");
-        written[dst] = true;
-        if (dst + 1 > n_regs) n_regs = dst + 1;
-    }
+    if (int rc = check_program("air program: ", program, program_len, n_cols, TSTWO_AIR_OP_ACC, n_regs, [&](u32) { n_acc++; return TSTWO_OK; })) return rc;
     if (n_acc != n_constraints) return bad("air program: the number of ACC instructions differs from n_constraints");
     // upload: program words, then coefficient words (at most 16 KiB: one slot of the ring, no host synchronisation)
     static_assert((2 * TSTWO_AIR_PROGRAM_MAX_INSTR + 4 * TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS) * 4 <= kUpSlotBytes, "program upload exceeds one ring slot");
@@ -502,15 +602,63 @@ int tstwo_air_eval_program(const u32 *const *cols, size_t n_cols, u32 trace_log_
     a.eval_log = trace_log_size + log_expand;
     a.log_expand = log_expand;
     a.n_rows = 1u << a.eval_log;
-    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, accum);
-    const int W = vec ? 4 : 1;
-    const size_t lds = (size_t)(n_regs ? n_regs : 1) * kWave * W * sizeof(u32);
-    const size_t work = a.n_rows / W;
-    unsigned grid = ceil_div(work, kWave);
-    const unsigned cap = (unsigned)ctx().n_cus * 32;
-    if (grid > cap) grid = cap;
+    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, accum, 4);
+    const size_t lds = interpreter_lds(n_regs, vec);
+    const unsigned grid = interpreter_grid(a.n_rows, vec);
     if (vec) hipLaunchKernelGGL(k_air_program<4>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, a);
     else hipLaunchKernelGGL(k_air_program<1>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, a);
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
+}
+
+int tstwo_air_eval_columns(const u32 *const *cols, size_t n_cols, u32 log_size, const u32 *program, size_t program_len,
+                           u32 *const *out, size_t n_out) {
+    TSTWO_REQUIRE_READY();
+    if (log_size < 1 || log_size > kMaxLog) return bad("air columns: log_size out of range");
+    if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return bad("air columns: number of columns out of range");
+    if (n_out == 0 || n_out > TSTWO_AIR_COLUMNS_MAX_OUT) return bad("air columns: number of outputs out of range");
+    if (program_len == 0 || program_len > TSTWO_AIR_PROGRAM_MAX_INSTR) return bad("air columns: program length out of range");
+    if (!program) return bad("null host argument");
+    TSTWO_REQUIRE_TABLE(cols, n_cols);
+    TSTWO_REQUIRE_TABLE(out, n_out);
+    // a load at an offset reads rows that other lanes store: no output may be an input (or another output)
+    for (size_t k = 0; k < n_out; k++) {
+        for (size_t i = 0; i < n_cols; i++)
+            if (out[k] == cols[i]) return bad("air columns: an output column is also an input column");
+        for (size_t i = 0; i < k; i++)
+            if (out[k] == out[i]) return bad("air columns: two outputs are the same column");
+    }
+    // the program words travel through the small-upload ring, which a captured graph cannot replay
+    if (stream_is_capturing()) return bad("host-array upload during graph capture (the air columns program cannot be recorded)");
+    bool stored[TSTWO_AIR_COLUMNS_MAX_OUT] = {};
+    size_t n_stored = 0;
+    u32 n_regs = 0;
+    auto on_store = [&](u32 k) {
+        if (k >= n_out) return bad("air columns: output index out of range");
+        if (stored[k]) return bad("air columns: output stored twice");
+        stored[k] = true;
+        n_stored++;
+        return (int)TSTWO_OK;
+    };
+    if (int rc = check_program("air columns: ", program, program_len, n_cols, TSTWO_AIR_OP_STORE, n_regs, on_store)) return rc;
+    if (n_stored != n_out) return bad("air columns: an output is never stored");
+    const size_t bytes = 2 * program_len * sizeof(u32);
+    static_assert(2 * TSTWO_AIR_PROGRAM_MAX_INSTR * 4 <= kUpSlotBytes, "program upload exceeds one ring slot");
+    if (int rc = ensure_scratch(bytes)) return rc;
+    if (int rc = small_h2d(ctx().scratch, program, bytes)) return rc;
+    ColPtrs cp, op;
+    if (int rc = fill_col_table(cp, cols, n_cols, 0)) return rc;
+    if (int rc = fill_col_table(op, (const u32 *const *)out, n_out, 1)) return rc;      // at most 64: by value
+    ColArgs a = {};
+    a.prog = ctx().scratch;
+    a.n_instr = (u32)program_len;
+    a.log = log_size;
+    a.n_rows = 1u << log_size;
+    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, out, n_out);
+    const size_t lds = interpreter_lds(n_regs, vec);
+    const unsigned grid = interpreter_grid(a.n_rows, vec);
+    if (vec) hipLaunchKernelGGL(k_air_columns<4>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, op, a);
+    else hipLaunchKernelGGL(k_air_columns<1>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, op, a);
     TSTWO_LAUNCH_CHECK();
     return TSTWO_OK;
 }

@@ -8,6 +8,11 @@ column j = column j - 1 + the batch's fractions (tstwo_logup_column, one fused l
 running sum over the coset order, shifted by claimed_sum / 2^log_size so that it ends at 0 (tstwo_logup_finalize_last), which
 also returns the claimed sum.
 
+derive_interaction_trace(eval, main, preprocessed) drives the generator from `evaluate` alone: the relation entries are recorded
+as they were added (constraint_framework.RelationEvaluator), every multiplicity or value that is an expression of columns becomes
+one output column of one tstwo_air_eval_columns program, and the batches are written in order.  The hand-written generators
+(constraint_framework.*_interaction_trace) are the same calls spelled out.
+
 Caller protocol (the verifier mirrors it): commit the preprocessed tree, commit the main tree, LookupElements.draw, generate the
 interaction trace, channel.mix_felts(claimed sums in component order), commit the interaction tree, prove.
 """
@@ -210,3 +215,105 @@ class LogupColGenerator:
 
     writeFrac = write_frac
     finalizeCol = finalize_col
+
+
+# ------------------------------------------------------------------ the interaction trace derived from `evaluate`
+class InteractionPlan:
+    """What derive_interaction_trace does for one eval, worked out on the host: `exprs`, the distinct expressions a columns
+    program evaluates (canonical nodes, in order of first use), and `batches`, per interaction column the fractions
+    (relation, numerator ref, value refs) in entry order.  A ref is ("const", value), ("col", ("main" | "pre", index)) for an
+    input column used as it is, or ("out", k) for exprs[k].  n_main / n_pre: the input columns `evaluate` reads."""
+
+    def __init__(self, exprs, batches, n_main, n_pre):
+        self.exprs, self.batches, self.n_main, self.n_pre = exprs, batches, n_main, n_pre
+
+
+def plan_interaction_trace(eval_) -> InteractionPlan:
+    """Runs `evaluate` on a RelationEvaluator and sorts every multiplicity and value into constants, input columns and
+    expressions.  No device work; raises the ValueErrors of derive_interaction_trace."""
+    from .constraint_framework import Canonical, Expr, SecureExpr, relation_entries
+    ev = relation_entries(eval_)
+    canonical, index, exprs = Canonical(), {}, []
+
+    def ref(v, what):
+        if isinstance(v, (SecureExpr, QM31)) and what == "multiplicity":
+            raise ValueError("a secure (QM31) multiplicity is not supported: numerators are M31 columns or constants")
+        if isinstance(v, SecureExpr):
+            raise ValueError("a secure (QM31) expression as a relation value is not supported: denominator terms are M31 columns")
+        if not isinstance(v, Expr):
+            return ("const", v if isinstance(v, QM31) else _m31(v))
+        node = canonical(v)
+        if node.op == "const":
+            return ("const", M31(node.args))
+        if node.op == "load":
+            column, offset = node.args
+            if column[0] == "int":
+                raise ValueError("a relation entry cannot read the interaction trace it defines")
+            if offset == 0:
+                return ("col", column)
+        if id(node) not in index:
+            index[id(node)] = len(exprs)
+            exprs.append(node)
+        return ("out", index[id(node)])
+
+    fracs = []
+    for relation, multiplicity, values in ev.entries:
+        values = relation._values(values)
+        num = ref(multiplicity, "multiplicity")
+        refs = [ref(v, "value") for v in values]
+        n_terms = sum(r[0] != "const" for r in refs)
+        if not 1 <= n_terms <= MAX_TERMS:
+            raise ValueError(f"a denominator needs 1 to {MAX_TERMS} column terms")
+        fracs.append((relation, num, refs))
+    batches = [[f for b, f in zip(ev.batching, fracs) if b == j] for j in range(max(ev.batching) + 1)]
+    if any(len(b) > MAX_FRACS for b in batches):
+        raise ValueError(f"at most {MAX_FRACS} fractions per column")
+    return InteractionPlan(exprs, batches, ev.n_main, max(ev.pre_used) + 1 if ev.pre_used else 0)
+
+
+def _m31(v) -> M31:
+    if isinstance(v, M31):
+        return v
+    if isinstance(v, int):
+        return M31(int(v) % P)
+    raise TypeError(f"a multiplicity or relation value is an int, M31, QM31 or an expression here, not {type(v).__name__}")
+
+
+def derive_interaction_trace(eval_, main, preprocessed=()):
+    """The interaction trace of a LogUp component from its `evaluate` alone: (HipCircleEvaluations, 4 per batch, claimed sum), the
+    return of LogupTraceGenerator.finalize_last().  main, preprocessed: the component's columns (HipColumns, or arrays in storage
+    order) in the order `evaluate` consumes them (next_trace_mask / next_interaction_mask, get_preprocessed_column(i)).
+      an int or M31 multiplicity is the fraction's constant numerator; a column read at offset 0 is used as it is;
+      every other expression of columns (x + 1, a * b - c, a value at another row, -multiplicity), as a multiplicity or as a value,
+      is one output of a tstwo_air_eval_columns program (equal expressions share one; more than 64 take several calls);
+      constant values fold into the denominator's constant as LookupElements.combine_columns folds them.
+    Nothing is read back before finalize_last.  Raises ValueError for an `evaluate` without relation entries, an entry without a
+    column among its values, a secure (QM31) multiplicity, more than 8 fractions in a batch or more than 16 column values."""
+    from .constraint_framework import MAX_OUT, compile_columns, evaluate_columns
+    plan = plan_interaction_trace(eval_)
+    log_size = eval_.log_size()
+    gen = LogupTraceGenerator(log_size)
+    main = [c if isinstance(c, HipColumn) else HipColumn(c) for c in main]
+    pre = [c if isinstance(c, HipColumn) else HipColumn(c) for c in preprocessed]
+    if len(main) != plan.n_main:
+        raise ValueError(f"evaluate reads {plan.n_main} main columns, {len(main)} given")
+    if len(pre) < plan.n_pre:
+        raise ValueError(f"evaluate reads {plan.n_pre} preprocessed columns, {len(pre)} given")
+    outs = []
+    for i in range(0, len(plan.exprs), MAX_OUT):
+        chunk = plan.exprs[i:i + MAX_OUT]
+        outs += evaluate_columns(main + pre, log_size, compile_columns(chunk, len(main), len(pre)), len(chunk))
+
+    def resolve(r):
+        kind, x = r
+        return x if kind == "const" else outs[x] if kind == "out" else (main if x[0] == "main" else pre)[x[1]]
+
+    for batch in plan.batches:
+        col = gen.new_col()
+        for relation, num, refs in batch:
+            col.write_frac(resolve(num), relation.combine_columns([resolve(r) for r in refs]))
+        col.finalize_col()
+    return gen.finalize_last()
+
+
+deriveInteractionTrace = derive_interaction_trace
