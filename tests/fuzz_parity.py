@@ -371,7 +371,11 @@ def case_merkle_big():
     layers = L.DeviceBuffer(32 * ((2 << mx) - 1))
     root = (C.c_uint8 * 32)()
     L.call("tstwo_merkle_commit", ptrs(d), L.u32x(logs), len(logs), vp(layers), root)
-    assert bytes(root) == orc.merkle_commit(cols, logs)[1], ("merkle big", logs)
+    olayers, oroot = orc.merkle_commit(cols, logs)
+    assert bytes(root) == oroot, ("merkle big", logs)
+    got = layers.download(np.uint8).reshape(-1, 32)
+    for lg in range(mx + 1):
+        assert (got[(1 << lg) - 1:(2 << lg) - 1] == olayers[lg]).all(), ("merkle big layer", lg, logs)
     return f"merkle_big {len(logs)} cols max log {mx}"
 
 

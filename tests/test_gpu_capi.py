@@ -944,12 +944,23 @@ def test_shipped_library_ignores_the_cfft_plan_knob():
     assert "experiments" in ver and passes == "5" and digest == want
 
 
-@pytest.mark.parametrize("shape", [(4, 32, 17), (8, 32, 18), (3, 16, 19), (2, 64, 17), (5, 48, 17), (2, 32, 12), (1, 32, 17), (3, 20, 17)], ids=str)
+_MANY_TAIL_SHAPES = [(5, 16, 19), (3, 64, 20)]
+@pytest.mark.parametrize("shape", [(4, 32, 17), (8, 32, 18), (3, 16, 19), (2, 64, 17), (5, 48, 17), (2, 32, 12), (1, 32, 17), (3, 20, 17)] + _MANY_TAIL_SHAPES,
+                         ids=str)
 def test_merkle_commit_many_equals_commits_one_by_one(shape):
     """tstwo_merkle_commit_many: every layer of every tree byte for byte what tstwo_merkle_commit writes for that tree alone —
     shapes the shared launches serve (16 / 32 / 48 / 64 columns of one log size >= 17, up to 8 trees) and shapes that fall back
-    to the tree-by-tree loop (small trees, other column counts, one tree); one root per tree against the oracle."""
+    to the tree-by-tree loop (small trees, other column counts, one tree); one root per tree against the oracle.
+    The last two shapes are the smallest at which the shipped library leaves tail lanes in a one-lane-per-node launch: five and
+    three trees share the cap of 32 workgroups per CU (1638 of 2048, 2730 of 4096 workgroups on 256 CUs), so a lane takes a second
+    node and the last row is partial, while the single-tree commit they are compared with stays under its cap."""
     n_trees, n_cols, n = shape
+    if shape in _MANY_TAIL_SHAPES:
+        import re
+        cus = int(re.search(r"(\d+) CUs", L.device_name()).group(1))
+        needed, cap = -(-(1 << n) // 256), cus * 32 // n_trees
+        assert needed > cap and (1 << n) % (cap * 256) != 0, f"{shape} on {cus} CUs: no tail lanes ({needed} workgroups, cap {cap})"
+        assert needed <= cus * 32, f"{shape} on {cus} CUs: the single-tree commit is capped as well"
     rng = np.random.default_rng(n_trees * 1000 + n_cols * 10 + n)
     base = [dev(rng.integers(0, P, size=1 << n, dtype=np.uint32)) for _ in range(min(n_cols + n_trees, 40))]
     trees = [[base[(t * 7 + k) % len(base)] for k in range(n_cols)] for t in range(n_trees)]       # overlapping column sets: inputs are read only
