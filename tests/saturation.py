@@ -14,10 +14,11 @@ Families (words are canonical M31 values, P = 2^31 - 1):
         words on the other rows: the rows of a 4-row or 8-row lane differ, and a row mix-up cannot hide behind constant columns
 All inputs come from fixed seeds.
 
-quotient_kernels(), inverse_kernel() and inverse_slot() restate in Python which launch the host side of csrc/quotients.hip and
-csrc/field_ops.hip picks for a shape, and which of a lane's elements an index is.  Nothing ties them to the C++: whoever changes
-that dispatch must update them here, or the coverage assertions of tests/test_cpu_saturation.py stay green while the GPU cases
-stop reaching a kernel."""
+quotient_kernels(), inverse_kernel() and inverse_slot() restate in Python which launch the host side of the quotients
+(csrc/quotients_plan.h) and of csrc/field_ops.hip picks for a shape, and which of a lane's elements an index is.  quotient_kernels()
+is compared with the compiled header by tests/test_cpu_saturation.py; nothing ties the other two to the C++: whoever changes that
+dispatch must update them here, or the coverage assertions of tests/test_cpu_saturation.py stay green while the GPU cases stop
+reaching a kernel."""
 from __future__ import annotations
 
 import itertools
@@ -247,7 +248,8 @@ def _shape(name, log):
 
 
 def quotient_kernels(log, lists, out_aligned):
-    """the launches tstwo_quotients_accumulate takes (csrc/quotients.hip), as names"""
+    """the launches tstwo_quotients_accumulate takes, as names: the tests' own statement of quotients_plan() in csrc/quotients_plan.h
+    (test_cpu_saturation.py::test_quotient_plan_matches_the_library compiles that header and compares the two)"""
     if log < 3 or not out_aligned:
         return ["row"]
     n_entries = sum(len(b) for b in lists)

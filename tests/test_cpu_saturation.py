@@ -7,6 +7,10 @@ exact Python integers and the reference models,
     maximum the C ABI can reach (4 (P-1)^2 + the folded remainder; bit 63 set at the reduce<true> sites; within 2^35 below 2^63 at the
     reduce<false> sites) and never passes 2^64.
 The restatements follow the kernels' own grouping (csrc/air.hip, logup.hip, quotients.hip, field_ops.hip, fri.hip)."""
+import os
+import shutil
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -205,6 +209,48 @@ def test_quotient_kernel_coverage():
             "rp<4,true>"} | {f"q8<{s},{z}>" for s in ("true", "false") for z in ("true", "false")}
     assert seen == want
     assert {len(b) for _, _, lists, _ in S.QUOTIENT_SHAPES for b in lists} >= {1, 3, 4, 5, 8, 9, 33}
+
+
+def _plan_inputs():
+    """(log, lists, out_aligned): every quotient shape of the suite, and logs 1..12 x aligned / unaligned x k = 1..12 batches over one
+    list of 1, 4, 5 entries, three disjoint lists, and two lists of 10 union columns with 13 and 14 entries (1.3 and 1.4 per column)"""
+    out = [(log, lists, al) for _, log, lists, al in S.QUOTIENT_SHAPES]
+    shapes = [[list(range(e))] * k for k in range(1, 13) for e in (1, 4, 5)]
+    shapes += [[[0], [1, 2, 3], [4, 5, 6, 7, 8]], [list(range(10)), [0, 1, 2]], [list(range(10)), [0, 1, 2, 3]]]
+    return out + [(log, lists, al) for log in range(1, 13) for al in (True, False) for lists in shapes]
+
+
+def test_quotient_plan_matches_the_library(tmp_path):
+    """S.quotient_kernels is the tests' own statement of the launch plan; csrc/quotients_plan.h is the library's.  A stand-alone
+    program that includes only that header prints the library's plan for every input of _plan_inputs: the two agree, the sweeps over
+    a shared list are consecutive and cover every batch, and none of them holds a single batch."""
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "quotients_plan_main")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-I", os.path.join(here, "..", "tstwo_amd", "csrc"),
+                           os.path.join(here, "quotients_plan_main.cpp"), "-o", exe])
+    inputs = _plan_inputs()
+    text = "".join(f"{log} {int(al)} {len({c for b in lists for c in b})} {' '.join(str(len(b)) for b in lists)}\n" for log, lists, al in inputs)
+    got = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(got) == len(inputs)
+    shared = 0
+    for (log, lists, al), line in zip(inputs, got):
+        launches = line.split()
+        assert [l.split("@")[0] for l in launches] == S.quotient_kernels(log, lists, al), (log, lists, al, line)
+        if "@" in line:
+            shared += 1
+            done = 0
+            for l in launches:
+                nb = int(l[l.index("<") + 1])
+                assert nb >= 2 and int(l.split("@")[1]) == done, (log, lists, al, line)
+                done += nb
+            assert done == len(lists), (log, lists, al, line)
+    assert shared > 100
+    names = {l.split("@")[0] for line in got for l in line.split()}
+    assert names == {"row", "multi<2,false>", "multi<2,true>", "multi<3,false>", "multi<3,true>", "rp<3,false>", "rp<3,true>", "rp<4,false>",
+                     "rp<4,true>"} | {f"q8<{s},{z}>" for s in ("true", "false") for z in ("true", "false")}
 
 
 def test_saturated_sample_constants_are_rejected_at_log_2():

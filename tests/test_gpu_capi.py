@@ -486,7 +486,7 @@ def test_quotients_golden(golden):
     assert [g.tolist() for g in got] == e0["out"]
 
 
-@pytest.mark.parametrize("log", [1, 2, 3, 6, 12, 16])
+@pytest.mark.parametrize("log", [1, 2, 3, 6, 12, 16, 8])
 def test_quotients_vs_oracle(log, golden):
     px, py = golden["eval_at_point"][0]["point"]
     n_cols = 5
@@ -1033,7 +1033,7 @@ def test_download_many_errors():
     assert len(L.download_many([])) == 0
 
 
-@pytest.mark.parametrize("log,n_cols", [(3, 2), (9, 5), (10, 4), (12, 9), (14, 33)])
+@pytest.mark.parametrize("log,n_cols", [(3, 2), (9, 5), (10, 4), (12, 9), (14, 33), (8, 5)])
 def test_quotients_two_batches_over_one_column_list(log, n_cols, golden):
     """Every column opened at two points (two sample batches over the same column list): the kernel that loads the column words
     once for both batches (k_quotients8_multi<2>) against the oracle's per-row reference loop — and the same input with the second
@@ -1060,7 +1060,8 @@ def test_quotients_two_batches_over_one_column_list(log, n_cols, golden):
             assert (host(out[k], 1 << log) == exp[k]).all(), (log, n_cols, second[:3], k)
 
 
-@pytest.mark.parametrize("log,n_cols,k", [(10, 5, 3), (12, 32, 3), (9, 4, 4), (13, 9, 4), (11, 6, 5), (12, 3, 7), (5, 4, 3)])
+@pytest.mark.parametrize("log,n_cols,k", [(10, 5, 3), (12, 32, 3), (9, 4, 4), (13, 9, 4), (11, 6, 5), (12, 3, 7), (5, 4, 3),
+                                          (3, 4, 5), (8, 5, 7), (9, 4, 7), (9, 3, 5)])          # log 3: one lane; 8 | 9: the last bsel = 2 | first bsel = 8 and row-pair size
 def test_quotients_k_batches_over_one_column_list(log, n_cols, k, golden):
     """Every column opened at k points (k sample batches over the SAME column list): sweeps of 3 or 2 batches that load the column
     words once per sweep and continue from the rows the previous sweep wrote (k_quotients8_multi<NB, ACCUM>), against the oracle's
@@ -1099,7 +1100,7 @@ def test_quotients_k_batches_over_one_column_list(log, n_cols, k, golden):
             assert (host(out[c], 1 << log) == exp[c]).all(), (log, n_cols, k, permuted, c)
 
 
-@pytest.mark.parametrize("log,n_cols", [(10, 8), (12, 33), (6, 5)])
+@pytest.mark.parametrize("log,n_cols", [(10, 8), (12, 33), (6, 5), (3, 5), (9, 8)])
 def test_quotients_batches_over_overlapping_column_lists(log, n_cols, golden):
     """Batches whose column lists overlap without being equal — every column at the first point, every second one also at a
     second point, a few (one of them listed twice) at a third — are served from the UNION list with zero coefficients where a
