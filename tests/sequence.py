@@ -28,8 +28,8 @@ synchronisation on any path the shapes here take):
   cfft.hip       tstwo_cfft_evaluate, _interpolate, _interpolate_to, _evaluate_extended, tstwo_poly_extend: launches; beyond 64
                  columns fill_col_table uploads the pointer table through small_h2d, whose ring path (<= 16 KiB) copies into a
                  page-locked slot and enqueues -- it waits for a slot's event only when the ring wraps onto a copy still pending.
-  fri.hip        tstwo_fri_fold_line_dev / _tw / _rows, tstwo_fri_fold_circle_into_line_dev / _tw / _rows: launches, alpha by
-                 value or read on the device.
+  fri.hip        tstwo_fri_fold_line_dev / _tw / _rows, tstwo_fri_fold_circle_into_line_dev / _tw / _rows: argument checks and one
+                 launch (fold_line / fold_circle, the one path of all eight fold entries), alpha by value or read on the device.
   merkle.hip     tstwo_merkle_commit and tstwo_merkle_commit_many with root(s) NULL ("then nothing is synchronised"),
                  tstwo_merkle_commit_layer; poseidon.hip tstwo_poseidon252_merkle_commit with root NULL.  Up to 64 columns the
                  tables travel by value.

@@ -6,7 +6,7 @@ exact Python integers and the reference models,
   * it reaches the bound: the unreduced 64-bit sum of the kernel, restated here in integers, takes on at least one row the documented
     maximum the C ABI can reach (4 (P-1)^2 + the folded remainder; bit 63 set at the reduce<true> sites; within 2^35 below 2^63 at the
     reduce<false> sites) and never passes 2^64.
-The restatements follow the kernels' own grouping (csrc/air.hip, logup.hip, quotients.hip, field_ops.hip, fri.hip)."""
+The restatements follow the kernels' own grouping (csrc/air.hip, logup.hip, quotients.hip, field_ops.hip, fri.hip, poly_eval.hip)."""
 import os
 import shutil
 import subprocess

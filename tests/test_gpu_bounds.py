@@ -1188,26 +1188,52 @@ def test_channel_mix_root_draw_felt(what):
     assert eq(got["chan"], _chan_words(ref))
 
 
-@pytest.mark.parametrize("log", [10, 14])
-def test_fri_commit_layers(log):
-    """The whole commit loop on one circle evaluation (log 10: every line layer in the one-workgroup tail; log 14: four layers of
-    separate launches first), down to a last layer of 4 rows.  The columns, the twiddles, the 10-word channel and the alphas
-    (capacity = trees + 3) are regions; the loop is replayed on the CPU -- the oracle's trees and folds, the host channel -- and the
-    channel, every alpha, every returned evaluation and tree must match; the alpha entries past the count keep the sentinel."""
+# (col_logs, last, the step kinds of tests/fri_plan.py the schedule holds beside the first tree and the first fold): the two
+# single columns first, then the smallest inputs that take each branch of the schedule
+FRI_COMMIT_CASES = [
+    pytest.param([10], 2, {"TAIL"}, id="10"),                                       # every line layer in the one-workgroup tail
+    pytest.param([14], 2, {"COMMIT", "FOLD_COMMIT", "TAIL+pre"}, id="14"),          # four layers of separate launches first
+    pytest.param([3], 2, set(), id="3-last2"),                                      # no inner layer
+    pytest.param([4], 2, {"TAIL"}, id="4-last2"),                                   # tail at once, no pre-fold
+    pytest.param([4, 3], 2, {"COMMIT", "FOLD_LINE", "CIRCLE_ACCUM"}, id="4.3-last2"),          # separate commit, line fold, a column joining at the last layer
+    pytest.param([6, 4], 2, {"COMMIT", "FOLD_COMMIT", "FOLD_LINE", "CIRCLE_ACCUM", "TAIL"}, id="6.4-last2"),       # fused at 2^4 rows, join, tail without pre-fold
+    pytest.param([11], 9, {"COMMIT", "FOLD_LINE"}, id="11-last9"),                  # no tail at all
+    pytest.param([12], 9, {"COMMIT", "FOLD_COMMIT", "FOLD_LINE"}, id="12-last9"),   # fused, then a plain fold into the last layer
+    pytest.param([13, 12], 2, {"COMMIT", "FOLD_LINE", "CIRCLE_ACCUM", "FOLD_COMMIT", "TAIL+pre"}, id="13.12-last2"),   # join at the first inner layer, fused, tail with pre-fold
+]
+
+
+def _fri_commit_arena(col_logs, tw_log, cap):
+    """(regions, names of the 4 n coordinate columns, the columns, the host channel) of a commit over circle columns of col_logs"""
+    ref = _host_channel()
+    cols = [soa(8100 + 40 * j + c, 1 << c) for j, c in enumerate(col_logs)]
+    c_ = [x for j in range(len(col_logs)) for x in names(f"col{j}_")]
+    regs = [rin(x, c) for x, c in zip(c_, [c for col in cols for c in col])]
+    regs += [rin("itw", otwiddles(tw_log)[1]), rinout("chan", _chan_words(ref)), rout("alphas", 4 * cap)]
+    return regs, c_, cols, ref
+
+
+@pytest.mark.parametrize("col_logs,last,kinds", FRI_COMMIT_CASES)
+def test_fri_commit_layers(col_logs, last, kinds):
+    """The whole commit loop on circle evaluations of col_logs (log 10: every line layer in the one-workgroup tail; log 14: four
+    layers of separate launches first; the others: the smallest inputs that take each branch of the schedule, which the case first
+    checks it takes, by tests/fri_plan.py), down to a last layer of 2^last rows.  The columns, the twiddles, the 10-word channel and
+    the alphas (capacity = trees + 3) are regions; the loop is replayed on the CPU -- the oracle's trees and folds, a joining column
+    folded into the current layer with the same alpha, the host channel -- and the channel, every alpha, every returned evaluation
+    and tree must match; the alpha entries past the count keep the sentinel."""
     from arena import SENTINEL
-    last = 2
+    import fri_plan
+    assert fri_plan.kinds(col_logs, last) == kinds | {"FIRST_TREE", "CIRCLE_WRITE"}
+    log = col_logs[0]
     tw_log = log + 1
-    half_initial = (half_odds(tw_log) << 2) & 0x7FFFFFFF
-    cols = soa(8100 + log, 1 << log)
+    half_initial = lambda c: (half_odds(tw_log) << (tw_log - c + 1)) & 0x7FFFFFFF      # of the canonic domain of log c
     n_trees = 1 + (log - 1 - last)
     cap = n_trees + 3
-    ref = _host_channel()
-    c_ = names("col")
-    regs = [rin(x, c) for x, c in zip(c_, cols)] + [rin("itw", otwiddles(tw_log)[1]), rinout("chan", _chan_words(ref)), rout("alphas", 4 * cap)]
+    regs, c_, cols, ref = _fri_commit_arena(col_logs, tw_log, cap)
     outs, n_out, first = (L.FriLayerOut * (n_trees + 1))(), C.c_size_t(0), L.vp()
     with Arena(regs) as A:
-        L.call("tstwo_fri_commit_layers", A.ptrs(c_), L.u32x([log]), 1, A.ptr("itw"), tw_log, last, A.ptr("chan"), A.ptr("alphas"), cap,
-               C.byref(first), outs, n_trees + 1, C.byref(n_out))
+        L.call("tstwo_fri_commit_layers", A.ptrs(c_), L.u32x(col_logs), len(col_logs), A.ptr("itw"), tw_log, last, A.ptr("chan"),
+               A.ptr("alphas"), cap, C.byref(first), outs, n_trees + 1, C.byref(n_out))
         got = A.check()
         owned = [L.DeviceBuffer.adopt(first.value, layers_bytes(log))]
         dev_layers = []
@@ -1222,11 +1248,12 @@ def test_fri_commit_layers(log):
             b.free()
     # the same loop on the CPU
     alphas = []
-    olayers, oroot = orc.merkle_commit(cols, [log] * 4)
+    olayers, oroot = orc.merkle_commit([c for col in cols for c in col], [c for c in col_logs for _ in range(4)])
     assert eq(first_tree, np.concatenate(olayers))
     ref.mix_root(oroot)
     alphas.append(ref.draw_felt().tup())
-    cur = orc.fold_circle_into_line(orc.soa_alloc(1 << (log - 1)), cols, log, half_initial, alphas[-1])
+    cur = orc.fold_circle_into_line(orc.soa_alloc(1 << (log - 1)), cols[0], log, half_initial(log), alphas[-1])
+    joining = {c - 1: col for c, col in zip(col_logs[1:], cols[1:])}          # line layer log -> the circle column that joins it
     assert n_out.value == n_trees
     for i, lg in enumerate(range(log - 1, last, -1)):
         dlg, dev_ev, dev_tree = dev_layers[i]
@@ -1236,9 +1263,31 @@ def test_fri_commit_layers(log):
         ref.mix_root(oroot)
         alphas.append(ref.draw_felt().tup())
         cur = orc.fold_line(cur, lg, (half_odds(tw_log) << (tw_log - lg)) & 0x7FFFFFFF, alphas[-1])
+        if lg - 1 in joining:
+            cur = orc.fold_circle_into_line(cur, joining.pop(lg - 1), lg, half_initial(lg), alphas[-1])
+    assert not joining
     dlg, dev_ev, dev_tree = dev_layers[-1]
     assert dlg == last and dev_tree is None and all(eq(dev_ev[k], cur[k]) for k in range(4))
     assert len(alphas) == n_trees
     assert eq(got["alphas"][:4 * n_trees], np.array(alphas, dtype=np.uint32).reshape(-1))
     assert (got["alphas"][4 * n_trees:] == SENTINEL).all()
     assert eq(got["chan"], _chan_words(ref))
+
+
+def test_fri_commit_layers_too_few_twiddles():
+    """a twiddle tree one level short of the first fold (tw_log = col_logs[0] - 2): the error comes back before anything is
+    allocated or launched -- the channel is bit for bit its input, every alpha entry the sentinel, nothing is returned"""
+    from arena import SENTINEL
+    col_logs, last = [13, 12], 2
+    tw_log = col_logs[0] - 2
+    n_trees = 1 + (col_logs[0] - 1 - last)
+    regs, c_, _, ref = _fri_commit_arena(col_logs, tw_log, n_trees + 3)
+    outs, n_out, first = (L.FriLayerOut * (n_trees + 1))(), C.c_size_t(7), L.vp(1)
+    with Arena(regs) as A:
+        with pytest.raises(L.TstwoError, match="Not enough twiddles!"):
+            L.call("tstwo_fri_commit_layers", A.ptrs(c_), L.u32x(col_logs), len(col_logs), A.ptr("itw"), tw_log, last, A.ptr("chan"),
+                   A.ptr("alphas"), n_trees + 3, C.byref(first), outs, n_trees + 1, C.byref(n_out))
+        got = A.check()
+    assert eq(got["chan"], _chan_words(ref))
+    assert (got["alphas"] == SENTINEL).all()
+    assert n_out.value == 0 and not first.value

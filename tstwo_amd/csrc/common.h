@@ -7,6 +7,7 @@
 #include <string>
 
 #include "../../include/tstwo_hip.h"
+#include "host_field.h"
 #include "m31.cuh"
 
 namespace tstwo {
@@ -259,5 +260,9 @@ inline bool table_has_null(T *const *t, size_t n) {
 #define TSTWO_REQUIRE_PTRS(...) do { if (::tstwo::has_null({__VA_ARGS__})) return set_error(TSTWO_ERR_BAD_ARG, "null device pointer"); } while (0)
 #define TSTWO_REQUIRE_TABLE(t, n) do { if (::tstwo::table_has_null((t), (n))) return set_error(TSTWO_ERR_BAD_ARG, "null device pointer in table"); } while (0)
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+// host scalars (host_field.h) <-> the QM31 a kernel takes as an argument
+inline qm31 to_q(const u32 a[4]) { return {a[0], a[1], a[2], a[3]}; }
+inline qm31 to_q(host::Q a) { return {a.v[0], a.v[1], a.v[2], a.v[3]}; }
+inline host::Q to_hq(const u32 a[4]) { host::Q q; for (int i = 0; i < 4; i++) q.v[i] = a[i]; return q; }
 
 }  // namespace tstwo
