@@ -536,6 +536,30 @@ int tstwo_air_constraint_quotients(uint32_t kind, const uint32_t *const *cols, s
 int tstwo_air_eval_program(const uint32_t *const *cols, size_t n_cols, uint32_t trace_log_size, uint32_t log_expand,
                            const uint32_t *program, size_t program_len, const uint32_t *coeffs, size_t n_constraints,
                            const uint32_t *denom_inv, uint32_t *const accum[4]);
+/* The same programs compiled to native kernels at run time, opt-in: tstwo_air_eval_compiled computes bit for bit what
+ * tstwo_air_eval_program computes for the program the kernel was compiled from.
+ * tstwo_air_program_compile: validates the program (the checks and texts of tstwo_air_eval_program), writes it as HIP source
+ *   (straight-line code on local variables: no LDS register file, column and coefficient indices are constants), compiles that
+ *   with hipRTC for the architecture of the current device and loads the code object.  *kernel_id names the kernel: an id into
+ *   a table of the library, handed out once per process.  trace_log_size and log_expand are not part of a kernel: one kernel
+ *   serves every domain size.  hipRTC is loaded at the first call (TSTWO_ERR_HIP "hipRTC is not available" without it); a
+ *   compile failure is TSTWO_ERR_HIP with the compiler's log in tstwo_last_error.  Synchronous (seconds for programs of
+ *   hundreds of instructions); refused during graph capture.
+ * tstwo_air_eval_compiled: the arguments, limits and error texts of tstwo_air_eval_program without the program; n_cols and
+ *   n_constraints must be those the kernel was compiled for.  An id that is unknown, destroyed or from before tstwo_shutdown is
+ *   TSTWO_ERR_BAD_ARG "unknown air kernel".  The coefficients are uploaded through the small-upload ring: refused during graph
+ *   capture.  Asynchronous.
+ * tstwo_air_kernel_info: info[0..2] = VGPRs, SGPRs and private-segment bytes per lane of the kernel for 16-byte aligned columns
+ *   (4 rows per lane), info[3..5] the same for the one-row kernel, info[6] the size of the code object in bytes.
+ * tstwo_air_program_destroy: unloads one kernel (synchronises the stream first; refused during graph capture).  tstwo_shutdown
+ *   unloads every kernel still alive. */
+#define TSTWO_AIR_KERNEL_INFO_WORDS 7
+int tstwo_air_program_compile(const uint32_t *program, size_t program_len, size_t n_cols, size_t n_constraints, uint64_t *kernel_id);
+int tstwo_air_eval_compiled(uint64_t kernel_id, const uint32_t *const *cols, size_t n_cols, uint32_t trace_log_size,
+                            uint32_t log_expand, const uint32_t *coeffs, size_t n_constraints, const uint32_t *denom_inv,
+                            uint32_t *const accum[4]);
+int tstwo_air_kernel_info(uint64_t kernel_id, uint32_t info[TSTWO_AIR_KERNEL_INFO_WORDS]);
+int tstwo_air_program_destroy(uint64_t kernel_id);
 /* The same programs evaluated on the trace domain itself into output columns (the numerators and denominator terms of a LogUp
  * interaction trace derived from `evaluate`: tstwo_amd/logup.py derive_interaction_trace).
  *   cols: n_cols device columns of 2^log_size M31 words on CanonicCoset(log_size).circle_domain(), bit-reversed order (the

@@ -116,6 +116,10 @@ const lib = dlopen(process.env.TSTWO_HIP_LIB ?? "libtstwo_hip.so", {
   tstwo_air_wide_fib_trace: { args: [u64, u64, u32, P, u64], returns: i32 },
   tstwo_air_constraint_quotients: { args: [u32, P, u64, u32, u32, P, u64, P, P], returns: i32 },
   tstwo_air_eval_program: { args: [P, u64, u32, u32, P, u64, P, u64, P, P], returns: i32 },
+  tstwo_air_program_compile: { args: [P, u64, u64, u64, P], returns: i32 },
+  tstwo_air_eval_compiled: { args: [u64, P, u64, u32, u32, P, u64, P, P], returns: i32 },
+  tstwo_air_kernel_info: { args: [u64, P], returns: i32 },
+  tstwo_air_program_destroy: { args: [u64], returns: i32 },
   tstwo_air_eval_columns: { args: [P, u64, u32, P, u64, P, u64], returns: i32 },
   tstwo_logup_column: { args: [P, u64, P, u32, P], returns: i32 },
   tstwo_logup_finalize_last: { args: [P, u32, P], returns: i32 },

@@ -22,9 +22,9 @@ OBJ = os.path.join(CSRC, "obj")
 LIB = os.path.join(HERE, "libtstwo_hip.so")
 OBJ_EXP = os.path.join(CSRC, "obj", "exp")
 LIB_EXP = os.path.join(HERE, "libtstwo_hip_exp.so")
-SOURCES = ["context.hip", "field_ops.hip", "cfft.hip", "fri.hip", "poly_eval.hip", "merkle.hip", "decommit.hip", "quotients.hip", "comm.hip", "gkr.hip", "poseidon.hip", "air.hip", "logup.hip"]
-# every header under csrc/ (globbed: a new .cuh / .h marks all objects stale without having to be listed) + the public one
-HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".cuh", ".h"))) + [os.path.join("..", "..", "include", "tstwo_hip.h")]
+SOURCES = ["context.hip", "field_ops.hip", "cfft.hip", "fri.hip", "poly_eval.hip", "merkle.hip", "decommit.hip", "quotients.hip", "comm.hip", "gkr.hip", "poseidon.hip", "air.hip", "air_native.hip", "logup.hip"]
+# every header under csrc/ (globbed: a new .cuh / .h / .inc marks all objects stale without having to be listed) + the public one
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".cuh", ".h", ".inc"))) + [os.path.join("..", "..", "include", "tstwo_hip.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

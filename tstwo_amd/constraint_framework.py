@@ -13,7 +13,8 @@ their batching: logup.derive_interaction_trace builds the interaction trace from
 (tstwo_air_eval_columns) for every multiplicity or value that is an expression of columns.
 The prover evaluates a component's constraints on the whole evaluation domain with one launch: WideFibonacciEval and MulAddEval
 (exactly these types, not subclasses) run on the hand-written kernel of tstwo_air_constraint_quotients, every other eval on the
-program interpreter.  WideFibonacciComponent and MulAddComponent are FrameworkComponents of those two evals, as in Rust.
+program interpreter or, for a FrameworkComponent made with native=True, on a kernel compiled from the program at construction
+(compile_native, tstwo_air_program_compile).  WideFibonacciComponent and MulAddComponent are FrameworkComponents of those two evals, as in Rust.
 
 The main trace (ORIGINAL_TRACE_IDX) is read at row offsets; preprocessed columns are read at offset 0 (as in Rust).  LogUp
 (tstwo_amd/logup.py, Rust logup.rs): add_to_relation / finalize_logup_* read the interaction trace (INTERACTION_TRACE_IDX, 4 base
@@ -26,6 +27,7 @@ from __future__ import annotations
 
 import bisect
 import ctypes as C
+import time
 
 from . import _lib as L
 from .air import (AIR_MUL_ADD, AIR_WIDE_FIB, ORIGINAL_TRACE_IDX, PREPROCESSED_TRACE_IDX, DomainEvaluationAccumulator,
@@ -756,6 +758,53 @@ def evaluate_program(cols, trace_log_size: int, log_expand: int, program: Progra
            program.n_instr, cw, len(coeffs), dinv, accum.ptrs())
 
 
+class NativeKernel:
+    """A program compiled to a native kernel (tstwo_air_program_compile): `id` names it in the library's table, n_cols and
+    n_constraints are what it was compiled for, compile_seconds the wall time of the compilation."""
+
+    def __init__(self, id_: int, n_cols: int, n_constraints: int, compile_seconds: float):
+        self.id, self.n_cols, self.n_constraints, self.compile_seconds = id_, n_cols, n_constraints, compile_seconds
+
+    def info(self) -> dict:
+        """tstwo_air_kernel_info: VGPRs, SGPRs and private-segment bytes of both widths, the code-object size, the compile time."""
+        w = (C.c_uint32 * 7)()
+        L.call("tstwo_air_kernel_info", self.id, w)
+        width = lambda k: {"vgprs": w[3 * k], "sgprs": w[3 * k + 1], "private_bytes": w[3 * k + 2]}
+        return {"w4": width(0), "w1": width(1), "code_bytes": w[6], "compile_seconds": self.compile_seconds}
+
+
+_native_kernels: dict = {}              # (program words, n_cols) -> NativeKernel: one compilation per program and process
+
+
+def compile_native(program: Program, n_cols: int) -> NativeKernel:
+    """The native kernel of a constraint program over n_cols columns, compiled once per process: programs with the same words
+    (the same eval at any size) share it.  A cached kernel the library no longer knows (tstwo_shutdown unloads every kernel,
+    and so does tstwo_init on another device) is compiled again."""
+    key = (tuple(program.words), n_cols)
+    kernel = _native_kernels.get(key)
+    if kernel is not None:
+        try:
+            kernel.info()
+            return kernel
+        except L.TstwoError:
+            del _native_kernels[key]
+    L.ensure_init()
+    kid = C.c_uint64(0)
+    t0 = time.perf_counter()
+    L.call("tstwo_air_program_compile", L.u32x(program.words), program.n_instr, n_cols, program.n_constraints, C.byref(kid))
+    kernel = _native_kernels[key] = NativeKernel(kid.value, n_cols, program.n_constraints, time.perf_counter() - t0)
+    return kernel
+
+
+def evaluate_program_native(cols, trace_log_size: int, log_expand: int, kernel: NativeKernel, coeffs, denom_inv,
+                            accum: SecureColumnByCoords) -> None:
+    """tstwo_air_eval_compiled: what evaluate_program computes, bit for bit, by the kernel compile_native made of the program."""
+    cw = (C.c_uint32 * max(4 * len(coeffs), 4))(*[w for c in coeffs for w in c.tup()])
+    dinv = L.u32x([d.value if isinstance(d, M31) else int(d) for d in denom_inv])
+    L.call("tstwo_air_eval_compiled", kernel.id, L.ptr_array([c.ptr for c in cols]), len(cols), trace_log_size, log_expand,
+           cw, len(coeffs), dinv, accum.ptrs())
+
+
 def evaluate_columns(cols, log_size: int, program: Program, n_out: int) -> list:
     """tstwo_air_eval_columns: the n_out output columns (new HipColumns of 2^log_size values) of a compile_columns program over
     `cols`, HipColumns on CanonicCoset(log_size).circle_domain() in storage order (main, then preprocessed).  Asynchronous."""
@@ -778,10 +827,12 @@ class FrameworkComponent:
     preprocessed tree (tree 0) of the column `get_preprocessed_column(i)` reads.  `kind` is the TSTWO_AIR_* kind of the
     hand-written kernel for the eval's exact type (None: the program path, and `program` holds the compiled constraints).
     claimed_sum: the LogUp sum of the component's interaction trace (LogupTraceGenerator.finalize_last), required exactly when
-    `evaluate` adds relation entries; its interaction columns are then allocated in tree INTERACTION_TRACE_IDX, 4 per batch."""
+    `evaluate` adds relation entries; its interaction columns are then allocated in tree INTERACTION_TRACE_IDX, 4 per batch.
+    native=True (opt-in, and only on the program path): the program is compiled to a native kernel here, at construction, and
+    evaluate_constraint_quotients_on_domain runs that kernel instead of the interpreter, with identical results."""
 
     def __init__(self, eval_, location_allocator: TraceLocationAllocator | None = None, preprocessed_column_indices=None, *,
-                 claimed_sum: QM31 | None = None):
+                 claimed_sum: QM31 | None = None, native: bool = False):
         self.eval = eval_
         self.log_size = eval_.log_size()
         if self.log_size < 1:
@@ -821,6 +872,16 @@ class FrameworkComponent:
             eval_.evaluate(pe)
             pe.check_finished()
             self.program = pe.compile(self.n_columns, len(self.preprocessed_column_indices))
+        self.native = None
+        if native and self.program is not None and self.n_constraints:
+            self.native = compile_native(self.program, self._n_program_columns())
+
+    def _n_program_columns(self) -> int:
+        return self.n_columns + len(self.preprocessed_column_indices) + self.n_interaction_columns
+
+    def native_info(self) -> dict | None:
+        """NativeKernel.info() of the component's kernel; None for a component that does not run one."""
+        return self.native.info() if self.native is not None else None
 
     # --- Component
     def max_constraint_log_degree_bound(self) -> int:
@@ -902,7 +963,17 @@ class FrameworkComponent:
         else:
             if any(self.secure_flags):
                 coeffs = expand_coeffs(coeffs, self.secure_flags)
-            evaluate_program(cols, self.log_size, eval_log - self.log_size, self.program, coeffs, denom_inv, column_acc.col)
+            if self.native is None:
+                evaluate_program(cols, self.log_size, eval_log - self.log_size, self.program, coeffs, denom_inv, column_acc.col)
+                return
+            try:
+                evaluate_program_native(cols, self.log_size, eval_log - self.log_size, self.native, coeffs, denom_inv, column_acc.col)
+            except L.TstwoError as e:
+                if "unknown air kernel" not in str(e):
+                    raise
+                # the library was shut down since construction: compile_native notices and compiles again
+                self.native = compile_native(self.program, len(cols))
+                evaluate_program_native(cols, self.log_size, eval_log - self.log_size, self.native, coeffs, denom_inv, column_acc.col)
 
 
 # ------------------------------------------------------------------ evals: wide Fibonacci, mul-add, Fibonacci over rows

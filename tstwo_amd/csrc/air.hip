@@ -12,6 +12,8 @@
 //     one output column (tstwo_air_eval_columns: the numerators and denominator terms of a LogUp interaction trace, derived
 //     from `evaluate` by tstwo_amd/logup.py derive_interaction_trace).  It shares the interpreter with k_air_program
 //     (fetch, exec_op, the LDS register file) and has no accumulators, coefficients or denominators.
+//   tstwo_air_eval_compiled  the contract and argument checks of k_air_program's entry, run by a kernel that air_native.hip
+//     compiled from the program (air_codegen.h writes its source; the program validator of all three entries lives there).
 // Row r (bit-reversed order on CanonicCoset(trace_log + log_expand).circle_domain()):
 //   row_res = sum_i coeff_i c_i(r),   accum[r] += row_res * denom_inv[r >> trace_log]
 //
@@ -36,6 +38,8 @@
 #include <algorithm>
 #include <string>
 
+#include "air_codegen.h"
+#include "air_native.h"
 #include "common.h"
 
 using namespace tstwo;
@@ -459,49 +463,6 @@ bool four_rows_per_lane(u32 n_rows, const u32 *const *cols, size_t n_cols, u32 *
     return n_rows % 4 == 0 && table_aligned16(cols, n_cols) && table_aligned16((const u32 *const *)accum, n_accum);
 }
 
-// Validates every instruction of a straight-line program: opcodes, registers (each read one written before), columns, offsets,
-// constants.  `terminal` is the entry's own opcode that reads r[x] and writes no register (ACC or STORE; the other one is a bad
-// opcode); on_terminal(w1) checks and counts it.  n_regs: the highest register written + 1.  `prefix` starts each error text.
-template <class F>
-int check_program(const char *prefix, const u32 *program, size_t program_len, size_t n_cols, u32 terminal, u32 &n_regs, F on_terminal) {
-    const std::string pre(prefix);
-    bool written[TSTWO_AIR_PROGRAM_MAX_REGS] = {};
-    n_regs = 0;
-    auto reg_ok = [&](u32 reg) { return reg < TSTWO_AIR_PROGRAM_MAX_REGS && written[reg]; };
-    for (size_t pc = 0; pc < program_len; pc++) {
-        const u32 w0 = program[2 * pc], w1 = program[2 * pc + 1];
-        const u32 op = w0 & 0xffu, dst = (w0 >> 8) & 0xffu, x = w0 >> 16;
-        switch (op) {
-            case TSTWO_AIR_OP_LOAD: {
-                if (x >= n_cols) return bad(pre + "column out of range");
-                const int off = (int)w1;
-                if (off > TSTWO_AIR_PROGRAM_MAX_OFFSET || off < -TSTWO_AIR_PROGRAM_MAX_OFFSET) return bad(pre + "row offset beyond the limit");
-                break;
-            }
-            case TSTWO_AIR_OP_CONST:
-                if (w1 >= M31_P) return bad(pre + "constant out of range");
-                break;
-            case TSTWO_AIR_OP_ADD: case TSTWO_AIR_OP_SUB: case TSTWO_AIR_OP_MUL:
-                if (!reg_ok(x) || !reg_ok(w1)) return bad(pre + "register out of range or read before written");
-                break;
-            case TSTWO_AIR_OP_SQR: case TSTWO_AIR_OP_NEG:
-                if (!reg_ok(x)) return bad(pre + "register out of range or read before written");
-                break;
-            case TSTWO_AIR_OP_ACC: case TSTWO_AIR_OP_STORE:
-                if (op != terminal) return bad(pre + "bad opcode");
-                if (!reg_ok(x)) return bad(pre + "register out of range or read before written");
-                if (int rc = on_terminal(w1)) return rc;
-                continue;                   // writes no register
-            default:
-                return bad(pre + "bad opcode");
-        }
-        if (dst >= TSTWO_AIR_PROGRAM_MAX_REGS) return bad(pre + "register out of range or read before written");
-        written[dst] = true;
-        if (dst + 1 > n_regs) n_regs = dst + 1;
-    }
-    return TSTWO_OK;
-}
-
 // The launch shape of both interpreter kernels: one-wave workgroups, n_regs KiB of LDS at W = 4, at most n_cus * 32 workgroups
 // (the kernels stride over the rest).
 size_t interpreter_lds(u32 n_regs, bool vec) { return (size_t)(n_regs ? n_regs : 1) * kWave * (vec ? 4 : 1) * sizeof(u32); }
@@ -509,6 +470,21 @@ unsigned interpreter_grid(u32 n_rows, bool vec) {
     unsigned grid = ceil_div((size_t)n_rows / (vec ? 4 : 1), kWave);
     const unsigned cap = (unsigned)ctx().n_cus * 32;
     return grid > cap ? cap : grid;
+}
+
+// What tstwo_air_eval_program and tstwo_air_eval_compiled ask of everything but the program itself.
+int check_eval_args(const u32 *const *cols, size_t n_cols, u32 trace_log_size, u32 log_expand, const u32 *coeffs, size_t n_constraints,
+                    const u32 *denom_inv, u32 *const accum[4]) {
+    if (log_expand < 1) return bad("air program: log_expand must be at least 1 (the neighbour index needs eval > trace)");
+    if (int rc = check_domain("air program: ", trace_log_size, log_expand)) return rc;
+    if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return bad("air program: number of columns out of range");
+    if (n_constraints == 0 || n_constraints > TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS) return bad("air program: number of constraints out of range");
+    if (!coeffs || !denom_inv) return bad("null host argument");
+    TSTWO_REQUIRE_TABLE(cols, n_cols);
+    TSTWO_REQUIRE_TABLE(accum, 4);
+    // the coefficient words (and the interpreter's program) travel through the small-upload ring, which a captured graph cannot replay
+    if (stream_is_capturing()) return bad("host-array upload during graph capture (the air program and its coefficients cannot be recorded)");
+    return TSTWO_OK;
 }
 
 template <int KIND>
@@ -570,20 +546,11 @@ int tstwo_air_constraint_quotients(u32 kind, const u32 *const *cols, size_t n_co
 int tstwo_air_eval_program(const u32 *const *cols, size_t n_cols, u32 trace_log_size, u32 log_expand, const u32 *program,
                            size_t program_len, const u32 *coeffs, size_t n_constraints, const u32 *denom_inv, u32 *const accum[4]) {
     TSTWO_REQUIRE_READY();
-    if (log_expand < 1) return bad("air program: log_expand must be at least 1 (the neighbour index needs eval > trace)");
-    if (int rc = check_domain("air program: ", trace_log_size, log_expand)) return rc;
-    if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return bad("air program: number of columns out of range");
     if (program_len == 0 || program_len > TSTWO_AIR_PROGRAM_MAX_INSTR) return bad("air program: program length out of range");
-    if (n_constraints == 0 || n_constraints > TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS) return bad("air program: number of constraints out of range");
-    if (!program || !coeffs || !denom_inv) return bad("null host argument");
-    TSTWO_REQUIRE_TABLE(cols, n_cols);
-    TSTWO_REQUIRE_TABLE(accum, 4);
-    // the program and coefficient words travel through the small-upload ring, which a captured graph cannot replay
-    if (stream_is_capturing()) return bad("host-array upload during graph capture (the air program and its coefficients cannot be recorded)");
+    if (!program) return bad("null host argument");
+    if (int rc = check_eval_args(cols, n_cols, trace_log_size, log_expand, coeffs, n_constraints, denom_inv, accum)) return rc;
     u32 n_regs = 0;
-    size_t n_acc = 0;
-    if (int rc = check_program("air program: ", program, program_len, n_cols, TSTWO_AIR_OP_ACC, n_regs, [&](u32) { n_acc++; return TSTWO_OK; })) return rc;
-    if (n_acc != n_constraints) return bad("air program: the number of ACC instructions differs from n_constraints");
+    if (const char *why = check_acc_program(program, program_len, n_cols, n_constraints, n_regs)) return bad(std::string("air program: ") + why);
     // upload: program words, then coefficient words (at most 16 KiB: one slot of the ring, no host synchronisation)
     static_assert((2 * TSTWO_AIR_PROGRAM_MAX_INSTR + 4 * TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS) * 4 <= kUpSlotBytes, "program upload exceeds one ring slot");
     u32 staged[2 * TSTWO_AIR_PROGRAM_MAX_INSTR + 4 * TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS];
@@ -611,6 +578,35 @@ int tstwo_air_eval_program(const u32 *const *cols, size_t n_cols, u32 trace_log_
     return TSTWO_OK;
 }
 
+int tstwo_air_eval_compiled(uint64_t kernel_id, const u32 *const *cols, size_t n_cols, u32 trace_log_size, u32 log_expand,
+                            const u32 *coeffs, size_t n_constraints, const u32 *denom_inv, u32 *const accum[4]) {
+    TSTWO_REQUIRE_READY();
+    u32 for_cols = 0, for_constraints = 0;
+    if (int rc = air_native_shape(kernel_id, for_cols, for_constraints)) return rc;
+    if (int rc = check_eval_args(cols, n_cols, trace_log_size, log_expand, coeffs, n_constraints, denom_inv, accum)) return rc;
+    if (n_cols != for_cols) return bad("air kernel: compiled for another number of columns");
+    if (n_constraints != for_constraints) return bad("air kernel: compiled for another number of constraints");
+    // upload: the coefficient words (at most 4 KiB: one slot of the ring, no host synchronisation)
+    u32 staged[4 * TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS];
+    NativeArgs a = {};
+    if (int rc = take_coeffs_and_denoms(coeffs, n_constraints, staged, denom_inv, log_expand, a)) return rc;
+    if (int rc = ensure_scratch(4 * n_constraints * sizeof(u32))) return rc;
+    if (int rc = small_h2d(ctx().scratch, staged, 4 * n_constraints * sizeof(u32))) return rc;
+    ColPtrs cp;
+    if (int rc = fill_col_table(cp, cols, n_cols, 0)) return rc;
+    for (int j = 0; j < 4; j++) a.acc.p[j] = accum[j];
+    a.coeff = ctx().scratch;
+    a.trace_log = trace_log_size;
+    a.eval_log = trace_log_size + log_expand;
+    a.log_expand = log_expand;
+    a.n_rows = 1u << a.eval_log;
+    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, accum, 4);
+    static_assert(kAirNativeThreads == kThreads, "grid_for counts workgroups of kThreads lanes");
+    const unsigned grid = grid_for(a.n_rows / (vec ? 4 : 1));
+    a.stride = grid * kThreads;
+    return air_native_launch(kernel_id, vec, grid, cp, a);
+}
+
 int tstwo_air_eval_columns(const u32 *const *cols, size_t n_cols, u32 log_size, const u32 *program, size_t program_len,
                            u32 *const *out, size_t n_out) {
     TSTWO_REQUIRE_READY();
@@ -633,14 +629,14 @@ int tstwo_air_eval_columns(const u32 *const *cols, size_t n_cols, u32 log_size, 
     bool stored[TSTWO_AIR_COLUMNS_MAX_OUT] = {};
     size_t n_stored = 0;
     u32 n_regs = 0;
-    auto on_store = [&](u32 k) {
-        if (k >= n_out) return bad("air columns: output index out of range");
-        if (stored[k]) return bad("air columns: output stored twice");
+    auto on_store = [&](u32 k) -> const char * {
+        if (k >= n_out) return "output index out of range";
+        if (stored[k]) return "output stored twice";
         stored[k] = true;
         n_stored++;
-        return (int)TSTWO_OK;
+        return (const char *)nullptr;
     };
-    if (int rc = check_program("air columns: ", program, program_len, n_cols, TSTWO_AIR_OP_STORE, n_regs, on_store)) return rc;
+    if (const char *why = check_program(program, program_len, n_cols, TSTWO_AIR_OP_STORE, n_regs, on_store)) return bad(std::string("air columns: ") + why);
     if (n_stored != n_out) return bad("air columns: an output is never stored");
     const size_t bytes = 2 * program_len * sizeof(u32);
     static_assert(2 * TSTWO_AIR_PROGRAM_MAX_INSTR * 4 <= kUpSlotBytes, "program upload exceeds one ring slot");

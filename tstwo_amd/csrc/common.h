@@ -238,6 +238,8 @@ int launch_fri_tail(u32 *const (*eval)[4], uint8_t *const *trees, u32 n_layers, 
 // read-back.  Hidden, unlike the older internal entries above, which are exported only because nothing ever hid them: the
 // library's dynamic symbol list is part of what callers see and does not grow for a function no caller may use.
 __attribute__((visibility("hidden"))) int download_roots(const uint8_t *const *layers, size_t n_trees, uint8_t *roots);
+// air_native.hip: tstwo_shutdown unloads the module of every compiled AIR program still alive; their ids are unknown afterwards
+__attribute__((visibility("hidden"))) void air_native_shutdown();
 // Host: describe columns [0, n_cols) of `cols` in `out`; slot 0/1 = which of the two device tables to use when a launch needs two.
 int fill_col_table(ColPtrs &out, const u32 *const *cols, size_t n_cols, int slot);
 constexpr int kMaxHashCols = 256;        // Merkle: columns absorbed per launch (multiple of 16)

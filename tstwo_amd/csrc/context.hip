@@ -407,6 +407,7 @@ int tstwo_shutdown(void) {
     if (!c.ready) return TSTWO_OK;
     (void)hipStreamSynchronize(c.stream);
     (void)tstwo_comm_destroy();          // communicator and collective stream, if any
+    air_native_shutdown();               // the modules of compiled AIR programs
     {
         std::lock_guard<std::mutex> lock(g_pool.mu);
         (void)trim_locked();
