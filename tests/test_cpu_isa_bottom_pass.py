@@ -17,7 +17,7 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 BOTTOM, BOTTOM_STREAM = r"k_cfft_bILb0ELi13ELb0E", r"k_cfft_b_streamILi13E"
 STRIDED, STRIDED_STREAM = r"k_cfft_aILb0ELi9ELi0ELi15E", r"k_cfft_a_streamILi9E"
 LOGT = 13
-DYNAMIC_LDS = ((1 << LOGT) + (1 << (LOGT - 5)) + (1 << (LOGT - 4))) * 4      # padded tile + twiddle heap (cfft.hip: launch_fast)
+DYNAMIC_LDS = ((1 << LOGT) + (1 << (LOGT - 5)) + (1 << (LOGT - 4))) * 4      # padded tile + twiddle heap (cfft_plan.h: cfft_plan)
 CU_LDS = 160 * 1024
 
 

@@ -24,6 +24,7 @@
 #include <unordered_map>
 #include <unordered_set>
 
+#include "cfft_plan.h"
 #include "common.h"
 #include "host_field.h"
 #include <stdlib.h>
@@ -32,11 +33,7 @@ using namespace tstwo;
 
 namespace {
 
-constexpr u32 kMaxLogTileB = 13;   // contiguous (bottom) tile: 2^13 words = 32 KiB + pad, 256 lanes
-constexpr u32 kLogTileA = 14;      // strided tile: 2^k rows x 2^(14-k) words = 64 KiB + pad, 512 lanes
-constexpr u32 kMaxLogSize = 30;    // MAX_CIRCLE_DOMAIN_LOG_SIZE (poly/circle/domain.ts:4): a 4 GiB column; word offsets stay below 2^30
-constexpr u32 kMaxKA = 9;          // at most 9 layers per strided pass (rows of >= 32 words = 128 B)
-constexpr int kThreadsB = 256, kThreadsA = 512;
+constexpr int kThreads = (int)kCfftGenericThreads;     // lanes of the generic kernel (k_cfft_pass)
 constexpr int kMaxV4 = 8;          // 16-byte vectors per lane per tile (32 words)
 
 struct PassParams {
@@ -144,10 +141,10 @@ namespace {
 // One register stage: G consecutive layers on LDS bits [q, q+G).  Twiddles come from the tile's LDS
 // heap `twl` (doubled values): layer bit b lives at twl[2^(logt-1-b) + (e >> (b+1))].
 // CIRCLE: bit 0 of this stage is the circle layer (only when q == 0 and lo == 0; needs G >= 3).
-template <int G, bool INV, bool CIRCLE, int THREADS>
+template <int G, bool INV, bool CIRCLE>
 __device__ __forceinline__ void run_stage(u32 *lds, const u32 *twl, const u32 q, const u32 logt) {
     const u32 ngroups = 1u << (logt - G);
-    for (u32 gid = threadIdx.x; gid < ngroups; gid += THREADS) {
+    for (u32 gid = threadIdx.x; gid < ngroups; gid += kThreads) {
         const u32 low = gid & ((1u << q) - 1u), high = gid >> q;
         const u32 e0 = (high << (q + G)) | low;
         u32 v[1 << G];
@@ -186,14 +183,14 @@ __device__ __forceinline__ void run_stage(u32 *lds, const u32 *twl, const u32 q,
     }
 }
 
-template <bool INV, bool CIRCLE, int THREADS>
+template <bool INV, bool CIRCLE>
 __device__ __forceinline__ void dispatch_stage(int g, u32 *lds, const u32 *twl, u32 q, u32 logt) {
     switch (g) {
-        case 5: run_stage<5, INV, CIRCLE, THREADS>(lds, twl, q, logt); break;
-        case 4: run_stage<4, INV, CIRCLE, THREADS>(lds, twl, q, logt); break;
-        case 3: run_stage<3, INV, CIRCLE, THREADS>(lds, twl, q, logt); break;
-        case 2: if (!CIRCLE) run_stage<2, INV, false, THREADS>(lds, twl, q, logt); break;
-        case 1: if (!CIRCLE) run_stage<1, INV, false, THREADS>(lds, twl, q, logt); break;
+        case 5: run_stage<5, INV, CIRCLE>(lds, twl, q, logt); break;
+        case 4: run_stage<4, INV, CIRCLE>(lds, twl, q, logt); break;
+        case 3: run_stage<3, INV, CIRCLE>(lds, twl, q, logt); break;
+        case 2: if (!CIRCLE) run_stage<2, INV, false>(lds, twl, q, logt); break;
+        case 1: if (!CIRCLE) run_stage<1, INV, false>(lds, twl, q, logt); break;
         default: break;
     }
 }
@@ -220,10 +217,9 @@ __device__ __forceinline__ int plan_stages(const PassParams &pp, int *g_out) {
 // One workgroup = one tile position x `cols_per_wg` columns.  The tile's twiddles are staged once
 // in LDS and reused for every column; the next column's tile is prefetched into registers while
 // the current one is transformed, so HBM latency overlaps the butterflies inside the workgroup.
-template <bool INV, int THREADS>
-// (512 lanes = the strided passes of the generic route, which no plan takes while every size with a strided pass is tiled: asked for 2
-// waves per SIMD it keeps its radix-32 stage in registers; at 4 it spilled 120-132 bytes per lane at 128 VGPRs)
-__global__ void __launch_bounds__(THREADS, (THREADS == 512 ? 2 : 3)) k_cfft_pass(ColPtrs cols, u32 n_cols, PassParams pp) {
+// Only the bottom pass of a column that is one tile (3 <= n <= 12: lo = 0, c = 0) is ever launched; its tile and heap stay below 64 KiB.
+template <bool INV>
+__global__ void __launch_bounds__(kThreads, 3) k_cfft_pass(ColPtrs cols, u32 n_cols, PassParams pp) {
     extern __shared__ __attribute__((aligned(16))) u32 lds[];
     const u32 tile_words = 1u << pp.logt;
     u32 *twl = lds + ((tile_words + (tile_words >> 5) + 3u) & ~3u);     // twiddle heap behind the padded tile
@@ -247,7 +243,7 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 512 ? 2 : 3)) k_cfft_pass
         const u32 *__restrict__ data = colp_u(cols, col0);
 #pragma unroll
         for (int it = 0; it < kMaxV4; it++) {
-            const u32 e = 4u * (threadIdx.x + (u32)it * THREADS);
+            const u32 e = 4u * (threadIdx.x + (u32)it * kThreads);
             if (e < tile_words) pf[it] = gload4(data + base + ((size_t)(e >> pp.c) << pp.lo) + (e & cmask));
         }
     }
@@ -256,7 +252,7 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 512 ? 2 : 3)) k_cfft_pass
     {
         const u32 skip = (pp.lo == 0) ? 1u : 0u;            // the circle layer has no entries of its own
         const u32 heap = 1u << (pp.k - skip);
-        for (u32 idx = threadIdx.x + 1; idx < heap; idx += THREADS) {
+        for (u32 idx = threadIdx.x + 1; idx < heap; idx += kThreads) {
             const u32 lv = 31u - (u32)__clz(idx);
             const u32 b = pp.logt - 1u - lv;
             const u32 i = pp.lo + b - pp.c;
@@ -272,7 +268,7 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 512 ? 2 : 3)) k_cfft_pass
         // ---- registers -> LDS
 #pragma unroll
         for (int it = 0; it < kMaxV4; it++) {
-            const u32 e = 4u * (threadIdx.x + (u32)it * THREADS);
+            const u32 e = 4u * (threadIdx.x + (u32)it * kThreads);
             if (e < tile_words) {
                 const u32 p = phys(e);
                 lds[p] = pf[it].x; lds[p + 1] = pf[it].y; lds[p + 2] = pf[it].z; lds[p + 3] = pf[it].w;
@@ -284,7 +280,7 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 512 ? 2 : 3)) k_cfft_pass
             const u32 *__restrict__ next = colp_u(cols, col + 1);
 #pragma unroll
             for (int it = 0; it < kMaxV4; it++) {
-                const u32 e = 4u * (threadIdx.x + (u32)it * THREADS);
+                const u32 e = 4u * (threadIdx.x + (u32)it * kThreads);
                 if (e < tile_words) pf[it] = gload4(next + base + ((size_t)(e >> pp.c) << pp.lo) + (e & cmask));
             }
         }
@@ -292,15 +288,15 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 512 ? 2 : 3)) k_cfft_pass
             u32 q = pp.logt;
             for (int s = n_stages - 1; s >= 0; s--) {
                 q -= (u32)gs[s];
-                if (pp.lo == 0 && q == 0) dispatch_stage<false, true, THREADS>(gs[s], lds, twl, q, pp.logt);
-                else dispatch_stage<false, false, THREADS>(gs[s], lds, twl, q, pp.logt);
+                if (pp.lo == 0 && q == 0) dispatch_stage<false, true>(gs[s], lds, twl, q, pp.logt);
+                else dispatch_stage<false, false>(gs[s], lds, twl, q, pp.logt);
                 __syncthreads();
             }
         } else {
             u32 q = pp.c;
             for (int s = 0; s < n_stages; s++) {
-                if (pp.lo == 0 && q == 0) dispatch_stage<true, true, THREADS>(gs[s], lds, twl, q, pp.logt);
-                else dispatch_stage<true, false, THREADS>(gs[s], lds, twl, q, pp.logt);
+                if (pp.lo == 0 && q == 0) dispatch_stage<true, true>(gs[s], lds, twl, q, pp.logt);
+                else dispatch_stage<true, false>(gs[s], lds, twl, q, pp.logt);
                 q += (u32)gs[s];
                 __syncthreads();
             }
@@ -309,7 +305,7 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 512 ? 2 : 3)) k_cfft_pass
         u32 *__restrict__ data = colp_u(cols, col);
 #pragma unroll
         for (int it = 0; it < kMaxV4; it++) {
-            const u32 e = 4u * (threadIdx.x + (u32)it * THREADS);
+            const u32 e = 4u * (threadIdx.x + (u32)it * kThreads);
             if (e < tile_words) {
                 const u32 p = phys(e);
                 uint4 x = make_uint4(lds[p], lds[p + 1], lds[p + 2], lds[p + 3]);
@@ -350,95 +346,30 @@ __global__ void k_cfft_small(ColPtrs cols, u32 n_cols, u32 n, u32 tx, u32 ty, u3
     }
 }
 
-struct Pass { u32 lo, k, c; };
-// passes low -> high.  kb = layers of the bottom pass (contiguous tile), the rest is cut into strided passes of <= ka_max.
-int plan_passes(u32 n, Pass *out, u32 kb = kMaxLogTileB, u32 ka_max = kMaxKA, u32 logta = kLogTileA) {
-    int cnt = 0;
-    if (n <= kb) {
-        out[cnt++] = {0, n, 0};
-        return cnt;
-    }
-    out[cnt++] = {0, kb, 0};
-    u32 rem = n - kb, lo = kb;
-    u32 np = (rem + ka_max - 1) / ka_max;
-    u32 base = rem / np, extra = rem % np;
-    for (u32 s = 0; s < np; s++) {
-        u32 k = base + (s < extra ? 1 : 0);
-        u32 c = logta - k;
-        if (c > lo) c = lo;
-        out[cnt++] = {lo, k, c};
-        lo += k;
-    }
-    return cnt;
-}
+// ---- host.  cfft_plan.h decides what is launched — route, passes, kernels, tiles, LDS — before anything is; what follows
+// checks the arguments, sizes the grids and launches.
 
-// The default plan of a many-column transform (evaluate / interpolate / interpolate_to / evaluate_extended share it):
-//   n <= 13, n = 14      ONE pass on the contiguous tile (2^14 words at n = 14: 256 columns 16.4 against 21.2 us for 13 + 1);
-//   15 <= n <= 20        13 bottom layers + one strided pass on 2^14-word tiles (n = 19, 20 on the 2^15 tile measured equal or 1 % slower);
-//   n = 21               13 + 8 on the 2^15-word tile (512-byte rows) from two workgroups per CU on: 512 x 2^21 3.60 against 3.64 ms,
-//                        interpolate 3.78 against 3.85 (128 columns: 0.930 / 0.976 against 0.938 / 0.989);
-//   n = 22, 23           13 + 9 / 13 + 10 with the strided pass on the 2^15-word tile (k_cfft_a<., K, ., 15>: two virtual lanes per
-//                        lane, 256- / 128-byte rows) when the launch still has two workgroups per CU — round 4, same box, 256 x 2^22:
-//                        3.775 against 3.805 ms forward, 3.985 against 4.027 inverse; 128 x 2^23: 3.815 against 3.895 (14 + 9 on
-//                        2^14-word tiles, round 3's two-pass plan, which stays for few columns) and 4.02 against 4.08;
-//   n = 24               14 + 10, the strided pass on the 2^15-word tile: TWO passes instead of 13 + 6 + 5 (round 4: 32 x 2^24
-//                        2.09 against 2.66 ms, 64 columns 4.08 against 5.29);
-//   n >= 25              13 bottom layers + two strided passes (a 2^14-word bottom tile changes nothing there).
-// 12 + 10 at n = 22 (a layer moved from the issue-bound bottom pass to the HBM-bound strided one) measured 3.86 against 3.78.
-struct PlanShape { u32 kb, ka_max, logta; };
-inline PlanShape default_shape(u32 n, size_t n_cols) {
-    const bool wide = n >= 15 && (((size_t)1 << (n - 15)) * n_cols) >= (size_t)2 * (size_t)ctx().n_cus;     // the 2^15 tile halves the workgroup count
-    if (n == 24) return {14u, 10u, 15u};
-    if (n == 23) return wide ? PlanShape{13u, 10u, 15u} : PlanShape{14u, kMaxKA, kLogTileA};
-    if ((n == 22 || n == 21) && wide) return {13u, 9u, 15u};
-    if (n == 14) return {14u, kMaxKA, kLogTileA};
-    return {kMaxLogTileB, kMaxKA, kLogTileA};
+// The kernel of one (kind, K, LOGT) of kCfftShapes, and the walk over the table that finds a pass's: only shapes of the table
+// are instantiated, and the planner names no other.
+template <CfftKind KIND, int K, int LOGT>
+const void *shape_kernel(bool inverse, u32 ext) {
+    if constexpr (KIND == CFFT_BOTTOM) return inverse ? (const void *)fast::k_cfft_b<true, LOGT> : (const void *)fast::k_cfft_b<false, LOGT>;
+    else if constexpr (KIND == CFFT_BOTTOM_STREAM) return (const void *)fast::k_cfft_b_stream<LOGT>;
+    else if constexpr (KIND == CFFT_BOTTOM_OOP) return (const void *)fast::k_cfft_b<true, LOGT, true>;
+    else if constexpr (KIND == CFFT_STRIDED) return inverse ? (const void *)fast::k_cfft_a<true, K, 0, LOGT> : (const void *)fast::k_cfft_a<false, K, 0, LOGT>;
+    else if constexpr (KIND == CFFT_STRIDED_STREAM) { static_assert(LOGT == 15, "k_cfft_a_stream is the 2^15 tile"); return (const void *)fast::k_cfft_a_stream<K>; }
+    else return ext == 1 ? (const void *)fast::k_cfft_a<false, K, 1, LOGT> : (const void *)fast::k_cfft_a<false, K, 2, LOGT>;
 }
-inline int plan_default(u32 n, size_t n_cols, Pass *out) {
-    const PlanShape sh = default_shape(n, n_cols);
-    return plan_passes(n, out, sh.kb, sh.ka_max, sh.logta);
-}
-
-template <bool INV, int THREADS>
-int launch_pass_t(u32 *const *cols, size_t n_cols, const PassParams &pp0) {
-    Context &c = ctx();
-    PassParams pp = pp0;
-    const size_t tile_words = (size_t)1 << pp.logt;
-    const size_t heap_words = (size_t)1 << (pp.k - (pp.lo == 0 ? 1 : 0));
-    const size_t lds_bytes = (((tile_words + (tile_words >> 5) + 3) & ~(size_t)3) + heap_words + 4) * sizeof(u32);
-    static bool lds_attr_set = false;   // tiles above 64 KiB need the opt-in (160 KiB LDS per CU on gfx950)
-    if (!lds_attr_set) {
-        TSTWO_HIP(hipFuncSetAttribute((const void *)k_cfft_pass<INV, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        lds_attr_set = true;
+constexpr int first_k(size_t row) { return row < kCfftShapeRows ? kCfftShapes[row].k_lo : 0; }
+template <size_t ROW = 0, int K = first_k(0)>
+const void *kernel_for(const CfftPass &ps, bool inverse, u32 ext) {
+    if constexpr (ROW == kCfftShapeRows) return nullptr;
+    else {
+        constexpr CfftShape S = kCfftShapes[ROW];
+        if (ps.kind == S.kind && ps.logt == S.logt && ps.k == (u32)K) return shape_kernel<S.kind, K, S.logt>(inverse, ext);
+        if constexpr (K < S.k_hi) return kernel_for<ROW, K + 1>(ps, inverse, ext);
+        else return kernel_for<ROW + 1, first_k(ROW + 1)>(ps, inverse, ext);
     }
-    const size_t tiles = (size_t)1 << (pp.n - pp.logt);
-    {   // every column in one launch (more than 64: pointer table in device memory)
-        const size_t cnt = n_cols;
-        ColPtrs cp;
-        int rc_tab = fill_col_table(cp, cols, n_cols, 0);
-        if (rc_tab) return rc_tab;
-        // columns per workgroup: amortise the twiddle staging, but keep >= ~6 workgroups per CU in the grid
-        u32 cpw = 4;
-        while (cpw > 1 && tiles * ((cnt + cpw - 1) / cpw) < (size_t)c.n_cus * 6) cpw >>= 1;
-        if (cpw > cnt) cpw = (u32)cnt;
-        pp.cols_per_wg = cpw;
-        size_t blocks = tiles * ((cnt + cpw - 1) / cpw);
-        if (blocks > 0x7fffffffu) return set_error(TSTWO_ERR_BAD_ARG, "cfft: grid too large");
-        hipLaunchKernelGGL((k_cfft_pass<INV, THREADS>), dim3((unsigned)blocks), dim3(THREADS), lds_bytes, c.stream, cp, (u32)cnt, pp);
-    }
-    TSTWO_LAUNCH_CHECK();
-    return TSTWO_OK;
-}
-
-template <bool INV>
-int launch_pass(u32 *const *cols, size_t n_cols, u32 n, const Pass &ps, const u32 *tw, u32 tw_log, u32 scale) {
-    PassParams pp;
-    pp.n = n; pp.lo = ps.lo; pp.k = ps.k; pp.c = ps.c; pp.logt = ps.c + ps.k; pp.scale = scale; pp.cols_per_wg = 1;
-    pp.tw_end = tw + ((size_t)1 << tw_log);
-    for (size_t i = 0; i < n_cols; i++)
-        if (((uintptr_t)cols[i]) & 15) return set_error(TSTWO_ERR_BAD_ARG, "cfft: columns must be 16-byte aligned");
-    if (ps.lo == 0) return launch_pass_t<INV, kThreadsB>(cols, n_cols, pp);
-    return launch_pass_t<INV, kThreadsA>(cols, n_cols, pp);
 }
 
 // Grid of a pass kernel: its (tile, column) work items are dealt in equal contiguous shares to as many workgroups as the
@@ -473,242 +404,122 @@ int allow_big_lds(const void *kernel) {
     return TSTWO_OK;
 }
 
-template <typename KernelT, typename... Args>
-int launch_fast_kernel(KernelT kernel, int threads, size_t lds_bytes, size_t tiles, u32 *const *cols, size_t n_cols, Args... args) {
-    // kernel signature: (ColPtrs cols, NoSrc, n_cols, total_items, args...)
-    Context &c = ctx();
-    lds_bytes += (size_t)knobs().cfft_lds_pad;     // experiments: extra (unused) dynamic LDS per workgroup lowers the resident workgroups per CU
-    { int rc_attr = allow_big_lds((const void *)kernel); if (rc_attr) return rc_attr; }
+// What every launch shares: the pointer table of `cols` (more than 64 columns: in device memory) and, where the kernel reads a
+// second one, of `src`; the grid (`blocks` for the small and generic routes; for a tiled kernel plan_grid sizes it for the
+// ps.tiles x n_cols work items); the launch and its check.  `args` are the kernel's arguments behind tables and counts.
+template <typename... Args>
+int launch(const void *kernel, const CfftPass &ps, unsigned blocks, u32 *const *cols, const u32 *const *src, size_t n_cols, Args... args) {
+    const bool tiled = ps.kind != CFFT_WHOLE;
+    size_t lds_bytes = ps.lds_bytes;
+    if (tiled) {
+        lds_bytes += (size_t)knobs().cfft_lds_pad;     // experiments: extra (unused) dynamic LDS per workgroup lowers the resident workgroups per CU
+        if (int rc = allow_big_lds(kernel)) return rc;
+    }
     if (knobs().cfft_trace) {
         hipFuncAttributes fa;
-        hipError_t e = hipFuncGetAttributes(&fa, (const void *)kernel);
-        fprintf(stderr, "[cfft] kernel %p threads %d lds %zu: getattr=%d maxDynamicSharedSizeBytes=%d sharedSizeBytes=%zu numRegs=%d maxThreadsPerBlock=%d\n",
-                (const void *)kernel, threads, lds_bytes, (int)e, fa.maxDynamicSharedSizeBytes, fa.sharedSizeBytes, fa.numRegs, fa.maxThreadsPerBlock);
+        hipError_t e = hipFuncGetAttributes(&fa, kernel);
+        fprintf(stderr, "[cfft] kernel %p threads %u lds %zu: getattr=%d maxDynamicSharedSizeBytes=%d sharedSizeBytes=%zu numRegs=%d maxThreadsPerBlock=%d\n",
+                kernel, ps.threads, lds_bytes, (int)e, fa.maxDynamicSharedSizeBytes, fa.sharedSizeBytes, fa.numRegs, fa.maxThreadsPerBlock);
     }
-    {
-        const size_t cnt = n_cols;
-        ColPtrs cp;
-        int rc_tab = fill_col_table(cp, cols, n_cols, 0);
-        if (rc_tab) return rc_tab;
-        const size_t items = tiles * cnt;
-        if (items > 0xffffffffu) return set_error(TSTWO_ERR_BAD_ARG, "cfft: too many (tile, column) work items");
-        const unsigned blocks = plan_grid((const void *)kernel, threads, lds_bytes, items);
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds_bytes, c.stream, cp, fast::NoSrc{}, (u32)cnt, (u32)items, args...);
-    }
+    ColPtrs cp, sp;
+    fast::NoSrc none;
+    int rc = fill_col_table(cp, cols, n_cols, 0);
+    if (!rc && src) rc = fill_col_table(sp, src, n_cols, 1);
+    if (rc) return rc;
+    u32 cnt = (u32)n_cols, items = (u32)(ps.tiles * n_cols);         // (the planner refused what does not fit 32 bits)
+    if (tiled) blocks = plan_grid(kernel, (int)ps.threads, lds_bytes, items);
+    // kernel signatures: tiled (ColPtrs cols, <ColPtrs | NoSrc> src, n_cols, total_items, args...); the others (ColPtrs cols, n_cols, args...)
+    void *argv[4 + sizeof...(Args)], *behind[] = {(void *)&args...};
+    int na = 0;
+    argv[na++] = &cp;
+    if (tiled) argv[na++] = src ? (void *)&sp : (void *)&none;
+    argv[na++] = &cnt;
+    if (tiled) argv[na++] = &items;
+    for (void *a : behind) argv[na++] = a;
+    (void)hipLaunchKernel(kernel, dim3(blocks), dim3(ps.threads), argv, lds_bytes, ctx().stream);
     TSTWO_LAUNCH_CHECK();
-    if (knobs().cfft_sync) TSTWO_HIP(hipStreamSynchronize(c.stream));
+    if (knobs().cfft_sync) TSTWO_HIP(hipStreamSynchronize(ctx().stream));
     return TSTWO_OK;
 }
 
-// Whether the tile accesses of a pass carry the non-temporal policy (cfft_fast.cuh: k_cfft_b_stream / k_cfft_a_stream): forward
-// transforms of a column set of 1 GiB and more — several times the 256 MiB cache, where the in-place read-modify-write gains with
-// it (tools/microbench7.hip) and 256 x 2^22 is 2 % faster; 32 x 2^22 (512 MiB) measures the same either way, 128 MiB and less lose.
-inline bool streams_past_cache(size_t n_cols, u32 n) { return (n_cols << n) >= ((size_t)1 << 28); }
-
-template <bool INV, int K, int LOGTA = 14, int V = (LOGTA == 15 ? 2 : 1)>
-int launch_a(u32 *const *cols, size_t n_cols, u32 n, u32 lo, const u32 *tw_end, u32 scale) {
-    const size_t tiles = (size_t)1 << (n - LOGTA);
-    if constexpr (!INV && LOGTA == 15 && V == 2)
-        if (streams_past_cache(n_cols, n))
-            return launch_fast_kernel(fast::k_cfft_a_stream<K>, (1 << (LOGTA - 4)) / V,
-                                      ((size_t)(1 << LOGTA) + (1 << (LOGTA - 5)) + ((size_t)1 << K)) * sizeof(u32), tiles, cols, n_cols, n, lo, tw_end, scale);
-    return launch_fast_kernel(fast::k_cfft_a<INV, K, 0, LOGTA, V>, (1 << (LOGTA - 4)) / V,
-                              ((size_t)(1 << LOGTA) + (1 << (LOGTA - 5)) + ((size_t)1 << K)) * sizeof(u32), tiles, cols, n_cols, n, lo, tw_end, scale);
+// log_size 1 and 2: the twiddles are coordinates of the half coset's initial point, inverted here for the inverse
+int run_small(const CfftPlan &plan, bool inverse, u32 *const *cols, size_t n_cols, u32 n, u32 half_initial, u32 n_inv) {
+    u32 px, py;
+    host::point(half_initial, &px, &py);
+    u32 tx = px, ty = py, scale = 1;
+    if (inverse) {
+        if (py == 0 || (n == 2 && px == 0)) return set_error(TSTWO_ERR_ZERO_INVERSE, "0 has no inverse");
+        ty = host::inv(py);
+        tx = n == 2 ? host::inv(px) : 0;
+        scale = n_inv;
+    }
+    const void *kernel = inverse ? (const void *)k_cfft_small<true> : (const void *)k_cfft_small<false>;
+    return launch(kernel, plan.pass[0], plan.blocks, cols, nullptr, n_cols, n, tx, ty, scale);
 }
 
-// First forward pass of an evaluation whose input is a smaller polynomial (log size n - EXT) in its own buffers.
-template <int K, int EXT, int LOGTA = 14>
-int launch_a_ext(u32 *const *cols, const u32 *const *src, size_t n_cols, u32 n, u32 lo, const u32 *tw_end) {
-    Context &c = ctx();
-    const size_t tiles = (size_t)1 << (n - LOGTA);
-    const size_t lds_bytes = ((size_t)(1 << LOGTA) + (1 << (LOGTA - 5)) + ((size_t)1 << K)) * sizeof(u32);
-    auto kernel = fast::k_cfft_a<false, K, EXT, LOGTA>;
-    { int rc_attr = allow_big_lds((const void *)kernel); if (rc_attr) return rc_attr; }
-    {
-        const size_t cnt = n_cols;
-        ColPtrs cp, sp;
-        int rc_tab = fill_col_table(cp, cols, n_cols, 0);
-        if (!rc_tab) rc_tab = fill_col_table(sp, src, n_cols, 1);
-        if (rc_tab) return rc_tab;
-        const size_t items = tiles * cnt;
-        if (items > 0xffffffffu) return set_error(TSTWO_ERR_BAD_ARG, "cfft: too many (tile, column) work items");
-        const unsigned blocks = plan_grid((const void *)kernel, 1024, lds_bytes, items);
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(1024), lds_bytes, c.stream, cp, sp, (u32)cnt, (u32)items, n, lo, tw_end, 0u);
+// Runs a plan of the generic or the tiled route on `cols`; the first pass of interpolate_to / evaluate_extended reads `src`.
+// All columns go through a pass in one launch.  (Measured on MI355X, 32 x 2^22: running the passes back to back
+// on Infinity-Cache-sized column groups is slower — 688 us ungrouped vs 724/771/879 us for groups of 16/8/4 —
+// the extra launch tails cost more than MALL residency of the intermediate returns.)
+int run_plan(const CfftPlan &plan, bool inverse, u32 ext, u32 *const *cols, const u32 *const *src, size_t n_cols, u32 n, const u32 *tw, u32 tw_log, u32 n_inv) {
+    const u32 *tw_end = tw + ((size_t)1 << tw_log);
+    if (plan.route == CFFT_GENERIC) {
+        const PassParams pp = {n, 0, n, 0, n, inverse ? n_inv : 0, plan.cols_per_wg, tw_end};
+        const void *kernel = inverse ? (const void *)k_cfft_pass<true> : (const void *)k_cfft_pass<false>;
+        return launch(kernel, plan.pass[0], plan.blocks, cols, nullptr, n_cols, pp);
     }
-    TSTWO_LAUNCH_CHECK();
+    for (u32 i = 0; i < plan.n_passes; i++) {       // execution order: high -> low layers forward, low -> high inverse
+        const CfftPass &ps = plan.pass[i];
+        const void *kernel = kernel_for(ps, inverse, ext);
+        const u32 *const *from = ps.kind == CFFT_BOTTOM_OOP || ps.kind == CFFT_STRIDED_EXT ? src : nullptr;
+        const u32 scale = ps.scale ? n_inv : 0;
+        const int rc = ps.lo == 0 ? launch(kernel, ps, 0, cols, from, n_cols, n, tw_end, scale) : launch(kernel, ps, 0, cols, from, n_cols, n, ps.lo, tw_end, scale);
+        if (rc) return rc;
+    }
     return TSTWO_OK;
 }
-template <int EXT>
-int launch_a_ext_k(u32 k, u32 logta, u32 *const *cols, const u32 *const *src, size_t n_cols, u32 n, u32 lo, const u32 *tw_end) {
-    if (logta == 15) {
-        if (k == 10) return launch_a_ext<10, EXT, 15>(cols, src, n_cols, n, lo, tw_end);
-        if (k == 9) return launch_a_ext<9, EXT, 15>(cols, src, n_cols, n, lo, tw_end);
-        if (k == 8) return launch_a_ext<8, EXT, 15>(cols, src, n_cols, n, lo, tw_end);
-        return set_error(TSTWO_ERR_BAD_ARG, "cfft: unsupported pass shape");
-    }
-    switch (k) {
-        case 2: return launch_a_ext<2, EXT>(cols, src, n_cols, n, lo, tw_end);
-        case 3: return launch_a_ext<3, EXT>(cols, src, n_cols, n, lo, tw_end);
-        case 4: return launch_a_ext<4, EXT>(cols, src, n_cols, n, lo, tw_end);
-        case 5: return launch_a_ext<5, EXT>(cols, src, n_cols, n, lo, tw_end);
-        case 6: return launch_a_ext<6, EXT>(cols, src, n_cols, n, lo, tw_end);
-        case 7: return launch_a_ext<7, EXT>(cols, src, n_cols, n, lo, tw_end);
-        case 8: return launch_a_ext<8, EXT>(cols, src, n_cols, n, lo, tw_end);
-        case 9: return launch_a_ext<9, EXT>(cols, src, n_cols, n, lo, tw_end);
-        case 10: return launch_a_ext<10, EXT>(cols, src, n_cols, n, lo, tw_end);
-        default: return set_error(TSTWO_ERR_BAD_ARG, "cfft: unsupported pass shape");
-    }
+
+const char *plan_for(CfftEntry entry, u32 ext, u32 n, size_t n_cols, CfftPlan &plan) {
+    const Knobs &kn = knobs();      // experiments build only: bottom-pass size, strided-pass limit, strided tile
+    return cfft_plan(entry, ext, n, n_cols, (u32)ctx().n_cus, {(u32)kn.cfft_kb, (u32)kn.cfft_ka, (u32)kn.cfft_logta}, plan);
 }
 
-template <bool INV>
-int launch_fast(u32 *const *cols, size_t n_cols, u32 n, const Pass &ps, const u32 *tw_end, u32 scale) {
-    if (ps.lo == 0) {
-        const size_t tiles = (size_t)1 << (n - ps.k);
-        const size_t lds = (((size_t)1 << ps.k) + ((size_t)1 << (ps.k - 5)) + ((size_t)1 << (ps.k - 4))) * sizeof(u32);
-        if constexpr (!INV)
-            if (streams_past_cache(n_cols, n) && (ps.k == 13 || ps.k == 14))
-                return ps.k == 13 ? launch_fast_kernel(fast::k_cfft_b_stream<13>, 512, lds, tiles, cols, n_cols, n, tw_end, scale)
-                                  : launch_fast_kernel(fast::k_cfft_b_stream<14>, 1024, lds, tiles, cols, n_cols, n, tw_end, scale);
-        switch (ps.k) {
-            case 14: return launch_fast_kernel(fast::k_cfft_b<INV, 14>, 1024, lds, tiles, cols, n_cols, n, tw_end, scale);
-            case 13: return launch_fast_kernel(fast::k_cfft_b<INV, 13>, 512, lds, tiles, cols, n_cols, n, tw_end, scale);
-            case 12: return launch_fast_kernel(fast::k_cfft_b<INV, 12>, 256, lds, tiles, cols, n_cols, n, tw_end, scale);
-            case 11: return launch_fast_kernel(fast::k_cfft_b<INV, 11>, 128, lds, tiles, cols, n_cols, n, tw_end, scale);
-            default: return set_error(TSTWO_ERR_BAD_ARG, "cfft: unsupported bottom pass");
-        }
-    }
-    const u32 logta = ps.c + ps.k;
-    if (logta == 12) {          // small strided tiles (few columns): 256 lanes, rows of 2^(12-K) >= 16 words
-        switch (ps.k) {
-            case 1: return launch_a<INV, 1, 12>(cols, n_cols, n, ps.lo, tw_end, scale);
-            case 2: return launch_a<INV, 2, 12>(cols, n_cols, n, ps.lo, tw_end, scale);
-            case 3: return launch_a<INV, 3, 12>(cols, n_cols, n, ps.lo, tw_end, scale);
-            case 4: return launch_a<INV, 4, 12>(cols, n_cols, n, ps.lo, tw_end, scale);
-            case 5: return launch_a<INV, 5, 12>(cols, n_cols, n, ps.lo, tw_end, scale);
-            case 6: return launch_a<INV, 6, 12>(cols, n_cols, n, ps.lo, tw_end, scale);
-            case 7: return launch_a<INV, 7, 12>(cols, n_cols, n, ps.lo, tw_end, scale);
-            case 8: return launch_a<INV, 8, 12>(cols, n_cols, n, ps.lo, tw_end, scale);
-            default: return set_error(TSTWO_ERR_BAD_ARG, "cfft: unsupported pass shape");
-        }
-    }
-    if (logta == 13) {
-        if (ps.k == 9) return launch_a<INV, 9, 13>(cols, n_cols, n, ps.lo, tw_end, scale);
-        return set_error(TSTWO_ERR_BAD_ARG, "cfft: unsupported pass shape");
-    }
-    if (logta == 15) {          // the 128 KiB tile (two virtual lanes per lane): 10 layers on 128-byte rows, 9 on 256-byte rows
-        switch (ps.k) {
-            case 8: return launch_a<INV, 8, 15>(cols, n_cols, n, ps.lo, tw_end, scale);
-            case 9: return launch_a<INV, 9, 15>(cols, n_cols, n, ps.lo, tw_end, scale);
-            case 10: return launch_a<INV, 10, 15>(cols, n_cols, n, ps.lo, tw_end, scale);
-            default: return set_error(TSTWO_ERR_BAD_ARG, "cfft: unsupported pass shape");
-        }
-    }
-    if (logta != 14) return set_error(TSTWO_ERR_BAD_ARG, "cfft: unsupported pass shape");
-    switch (ps.k) {
-        case 1: return launch_a<INV, 1>(cols, n_cols, n, ps.lo, tw_end, scale);
-        case 2: return launch_a<INV, 2>(cols, n_cols, n, ps.lo, tw_end, scale);
-        case 3: return launch_a<INV, 3>(cols, n_cols, n, ps.lo, tw_end, scale);
-        case 4: return launch_a<INV, 4>(cols, n_cols, n, ps.lo, tw_end, scale);
-        case 5: return launch_a<INV, 5>(cols, n_cols, n, ps.lo, tw_end, scale);
-        case 6: return launch_a<INV, 6>(cols, n_cols, n, ps.lo, tw_end, scale);
-        case 7: return launch_a<INV, 7>(cols, n_cols, n, ps.lo, tw_end, scale);
-        case 8: return launch_a<INV, 8>(cols, n_cols, n, ps.lo, tw_end, scale);
-        case 9: return launch_a<INV, 9>(cols, n_cols, n, ps.lo, tw_end, scale);
-        case 10: return launch_a<INV, 10>(cols, n_cols, n, ps.lo, tw_end, scale);
-        default: return set_error(TSTWO_ERR_BAD_ARG, "cfft: unsupported pass shape");
-    }
-}
-
-// bottom tile, strided-pass layer limit and strided tile of an in-place transform of n_cols columns of 2^n words (n >= 13)
-void choose_plan(u32 n, size_t n_cols, u32 &kb, u32 &ka_max, u32 &logta) {
-    Context &c = ctx();
-    const PlanShape shape = default_shape(n, n_cols);
-    kb = shape.kb; ka_max = shape.ka_max;
-    const Knobs &kn = knobs();
-    if (kn.cfft_kb) kb = (u32)kn.cfft_kb;           // experiments build only: bottom-pass size, strided-pass limit
-    if (kn.cfft_ka) ka_max = (u32)kn.cfft_ka;
-    logta = shape.logta;
-    if (n > kb && n >= kLogTileA && !kn.cfft_kb && !kn.cfft_ka) {     // n = 13 (and 14) is one bottom pass whatever the column count
-        // Few columns: the default tiles (2^13 contiguous, 2^14 strided) give 2^(n-13) x cols and 2^(n-14) x cols workgroups;
-        // below ~2 per CU pick the split with the most workgroups in its emptier pass (ties: the larger tiles).
-        // n = 20, one column: 12 + 8 layers on 2^12-word tiles = 256 + 256 workgroups instead of 128 + 64.
-        const size_t want = (size_t)2 * (size_t)c.n_cus;
-        if ((((size_t)1 << (n - kLogTileA)) * n_cols) < want && n - 13 <= ka_max) {
-            size_t best = 0;
-            for (u32 tb = 13; tb >= 11; tb--) {
-                const u32 k = n - tb;
-                if (k < 1 || k > ka_max) continue;        // one strided pass
-                const u32 ta = k <= 8 ? 12u : (k == 9 ? 13u : 14u);
-                if (ta > n) continue;
-                size_t wa = ((size_t)1 << (n - ta)) * n_cols, wb = ((size_t)1 << (n - tb)) * n_cols;
-                size_t score = wa < wb ? wa : wb;
-                if (score > want) score = want;
-                if (score > best) { best = score; kb = tb; logta = ta; }
-            }
-        }
-    }
-    if (kn.cfft_logta) logta = (u32)kn.cfft_logta;   // experiments
-}
-
-template <bool INV>
-int cfft(u32 *const *cols, size_t n_cols, u32 n, u32 half_initial, const u32 *tw, u32 tw_log) {
-    TSTWO_REQUIRE_READY();
-    if (n == 0 || n > 31) return set_error(TSTWO_ERR_BAD_ARG, "cfft: log_size out of range");
-    if (n > kMaxLogSize) return set_error(TSTWO_ERR_BAD_ARG, "cfft: log_size > 30 exceeds MAX_CIRCLE_DOMAIN_LOG_SIZE (poly/circle/domain.ts:4)");
-    if (n_cols == 0) return TSTWO_OK;
-    if (!cols) return set_error(TSTWO_ERR_BAD_ARG, "cfft: null column table");
-    Context &c = ctx();
-    TSTWO_REQUIRE_TABLE(cols, n_cols);
-    const u32 N = 1u << n;
-    const u32 n_inv = host::inv(N % M31_P);
-    if (n <= 2) {
-        u32 px, py;
-        host::point(half_initial, &px, &py);
-        u32 tx = px, ty = py, scale = 1;
-        if (INV) {
-            if (py == 0 || (n == 2 && px == 0)) return set_error(TSTWO_ERR_ZERO_INVERSE, "0 has no inverse");
-            ty = host::inv(py);
-            tx = n == 2 ? host::inv(px) : 0;
-            scale = n_inv;
-        }
-        {
-            ColPtrs cp;
-            int rc_tab = fill_col_table(cp, cols, n_cols, 0);
-            if (rc_tab) return rc_tab;
-            hipLaunchKernelGGL(k_cfft_small<INV>, dim3((unsigned)((n_cols + 63) / 64)), dim3(64), 0, c.stream, cp, (u32)n_cols, n, tx, ty, scale);
-        }
-        TSTWO_LAUNCH_CHECK();
-        return TSTWO_OK;
-    }
+// The arguments of every route that reads a twiddle tree; src: the read-only second table of the out-of-place entries, or null.
+int check_tiled_args(u32 *const *cols, const u32 *const *src, size_t n_cols, u32 n, const u32 *tw, u32 tw_log) {
     if (!tw) return set_error(TSTWO_ERR_BAD_ARG, "cfft: null twiddle buffer");
     if (tw_log > 31 || ((size_t)1 << (n - 1)) > ((size_t)1 << tw_log)) return set_error(TSTWO_ERR_TWIDDLES, "Not enough twiddles!");
-    Pass passes[8];
-    u32 kb, ka_max, logta;
-    choose_plan(n, n_cols, kb, ka_max, logta);
-    int np = n >= kMaxLogTileB ? plan_passes(n, passes, kb, ka_max, logta) : plan_passes(n, passes);
     for (size_t i = 0; i < n_cols; i++)
-        if (((uintptr_t)cols[i]) & 15) return set_error(TSTWO_ERR_BAD_ARG, "cfft: columns must be 16-byte aligned");
-    if (((uintptr_t)tw) & 15) return set_error(TSTWO_ERR_BAD_ARG, "cfft: twiddle buffer must be 16-byte aligned");
-    const u32 *tw_end = tw + ((size_t)1 << tw_log);
-    const bool fast_path = n >= kMaxLogTileB && n <= kMaxLogSize;
-    // All columns go through a pass in one launch.  (Measured on MI355X, 32 x 2^22: running the passes back to back
-    // on Infinity-Cache-sized column groups is slower — 688 us ungrouped vs 724/771/879 us for groups of 16/8/4 —
-    // the extra launch tails cost more than MALL residency of the intermediate returns.)
-    if (!INV) {
-        for (int s = np - 1; s >= 0; s--) {
-            int rc = fast_path ? launch_fast<false>(cols, n_cols, n, passes[s], tw_end, 0)
-                               : launch_pass<false>(cols, n_cols, n, passes[s], tw, tw_log, 0);
-            if (rc) return rc;
-        }
-    } else {
-        for (int s = 0; s < np; s++) {
-            const u32 sc = s == np - 1 ? n_inv : 0;
-            int rc = fast_path ? launch_fast<true>(cols, n_cols, n, passes[s], tw_end, sc)
-                               : launch_pass<true>(cols, n_cols, n, passes[s], tw, tw_log, sc);
-            if (rc) return rc;
-        }
-    }
+        if (!aligned16(cols[i]) || (src && !aligned16(src[i]))) return set_error(TSTWO_ERR_BAD_ARG, "cfft: columns must be 16-byte aligned");
+    if (!aligned16(tw)) return set_error(TSTWO_ERR_BAD_ARG, "cfft: twiddle buffer must be 16-byte aligned");
     return TSTWO_OK;
+}
+int check_log_size(u32 n) {
+    if (n == 0 || n > 31) return set_error(TSTWO_ERR_BAD_ARG, "cfft: log_size out of range");
+    if (n > kCfftMaxLog) return set_error(TSTWO_ERR_BAD_ARG, "cfft: log_size > 30 exceeds MAX_CIRCLE_DOMAIN_LOG_SIZE (poly/circle/domain.ts:4)");
+    return TSTWO_OK;
+}
+
+// Arguments, then the plan's own refusal, then the launches: an entry that fails has launched nothing.
+int cfft_planned(CfftEntry entry, u32 ext, u32 *const *cols, const u32 *const *src, size_t n_cols, u32 n, u32 half_initial, const u32 *tw, u32 tw_log,
+                 const CfftPlan &plan, const char *refused) {
+    const bool inverse = entry == CFFT_INTERPOLATE || entry == CFFT_INTERPOLATE_TO;
+    const u32 n_inv = host::inv((1u << n) % M31_P);
+    if (!refused && plan.route == CFFT_SMALL) return run_small(plan, inverse, cols, n_cols, n, half_initial, n_inv);
+    if (int rc = check_tiled_args(cols, src, n_cols, n, tw, tw_log)) return rc;
+    if (refused) return set_error(TSTWO_ERR_BAD_ARG, refused);
+    return run_plan(plan, inverse, ext, cols, src, n_cols, n, tw, tw_log, n_inv);
+}
+
+int cfft(bool inverse, u32 *const *cols, size_t n_cols, u32 n, u32 half_initial, const u32 *tw, u32 tw_log) {
+    TSTWO_REQUIRE_READY();
+    if (int rc = check_log_size(n)) return rc;
+    if (n_cols == 0) return TSTWO_OK;
+    if (!cols) return set_error(TSTWO_ERR_BAD_ARG, "cfft: null column table");
+    TSTWO_REQUIRE_TABLE(cols, n_cols);
+    const CfftEntry entry = inverse ? CFFT_INTERPOLATE : CFFT_EVALUATE;
+    CfftPlan plan;
+    const char *refused = plan_for(entry, 0, n, n_cols, plan);
+    return cfft_planned(entry, 0, cols, nullptr, n_cols, n, half_initial, tw, tw_log, plan, refused);
 }
 
 }  // namespace
@@ -716,21 +527,20 @@ int cfft(u32 *const *cols, size_t n_cols, u32 n, u32 half_initial, const u32 *tw
 extern "C" {
 
 int tstwo_cfft_evaluate(u32 *const *cols, size_t n_cols, u32 log_size, u32 half_initial, const u32 *tw, u32 tw_log) {
-    return cfft<false>(cols, n_cols, log_size, half_initial, tw, tw_log);
+    return cfft(false, cols, n_cols, log_size, half_initial, tw, tw_log);
 }
 int tstwo_cfft_interpolate(u32 *const *cols, size_t n_cols, u32 log_size, u32 half_initial, const u32 *itw, u32 tw_log) {
-    return cfft<true>(cols, n_cols, log_size, half_initial, itw, tw_log);
+    return cfft(true, cols, n_cols, log_size, half_initial, itw, tw_log);
 }
 
+// The launches of an in-place transform (bench.py takes its launch count from here): the count of the plan cfft() runs.
 int tstwo_cfft_plan_passes(u32 log_size, size_t n_cols, u32 *n_passes) {
     TSTWO_REQUIRE_READY();          // (the planner asks the context for the CU count)
     if (!n_passes) return set_error(TSTWO_ERR_BAD_ARG, "cfft: null output");
-    if (log_size == 0 || log_size > kMaxLogSize) return set_error(TSTWO_ERR_BAD_ARG, "cfft: log_size out of range");
-    if (log_size < kMaxLogTileB) { *n_passes = 1; return TSTWO_OK; }
-    Pass passes[8];
-    u32 kb, ka_max, logta;
-    choose_plan(log_size, n_cols, kb, ka_max, logta);
-    *n_passes = (u32)plan_passes(log_size, passes, kb, ka_max, logta);
+    if (log_size == 0 || log_size > kCfftMaxLog) return set_error(TSTWO_ERR_BAD_ARG, "cfft: log_size out of range");
+    CfftPlan plan;
+    if (const char *refused = plan_for(CFFT_EVALUATE, 0, log_size, n_cols, plan)) return set_error(TSTWO_ERR_BAD_ARG, refused);
+    *n_passes = plan.n_passes;
     return TSTWO_OK;
 }
 
@@ -741,53 +551,16 @@ int tstwo_cfft_interpolate_to(const u32 *const *src, u32 *const *dst, size_t n_c
     if (n_cols == 0) return TSTWO_OK;
     if (!src || !dst) return set_error(TSTWO_ERR_BAD_ARG, "cfft: null column table");
     TSTWO_REQUIRE_TABLE(src, n_cols); TSTWO_REQUIRE_TABLE(dst, n_cols);
-    if (log_size == 0 || log_size > 31) return set_error(TSTWO_ERR_BAD_ARG, "cfft: log_size out of range");
-    const Knobs &kn = knobs();
-    const bool tiled = log_size >= kMaxLogTileB && log_size <= kMaxLogSize && !kn.cfft_kb && !kn.cfft_ka;
-    if (tiled) {
-        if (!itw) return set_error(TSTWO_ERR_BAD_ARG, "cfft: null twiddle buffer");
-        if (tw_log > 31 || ((size_t)1 << (log_size - 1)) > ((size_t)1 << tw_log)) return set_error(TSTWO_ERR_TWIDDLES, "Not enough twiddles!");
-        for (size_t i = 0; i < n_cols; i++)
-            if ((((uintptr_t)dst[i]) & 15) || (((uintptr_t)src[i]) & 15)) return set_error(TSTWO_ERR_BAD_ARG, "cfft: columns must be 16-byte aligned");
-        if (((uintptr_t)itw) & 15) return set_error(TSTWO_ERR_BAD_ARG, "cfft: twiddle buffer must be 16-byte aligned");
-        Context &c = ctx();
-        Pass passes[8];
-        const int np = plan_default(log_size, n_cols, passes);
-        const u32 kb = passes[0].k;
-        const u32 *tw_end = itw + ((size_t)1 << tw_log);
-        const u32 n_inv = host::inv((1u << log_size) % M31_P);
-        // bottom pass, out of place
-        {
-            const size_t tiles = (size_t)1 << (log_size - kb);
-            const size_t lds = (((size_t)1 << kb) + ((size_t)1 << (kb - 5)) + ((size_t)1 << (kb - 4))) * sizeof(u32);
-            const unsigned threads = 1u << (kb - 4);
-            auto kernel = kb == 14 ? fast::k_cfft_b<true, 14, true> : fast::k_cfft_b<true, 13, true>;
-            { int rc_attr = allow_big_lds((const void *)kernel); if (rc_attr) return rc_attr; }
-            {
-                const size_t cnt = n_cols;
-                ColPtrs cp, sp;
-                int rc_tab = fill_col_table(cp, dst, n_cols, 0);
-                if (!rc_tab) rc_tab = fill_col_table(sp, src, n_cols, 1);
-                if (rc_tab) return rc_tab;
-                const size_t items = tiles * cnt;
-                if (items > 0xffffffffu) return set_error(TSTWO_ERR_BAD_ARG, "cfft: too many (tile, column) work items");
-                const unsigned blocks = plan_grid((const void *)kernel, (int)threads, lds, items);
-                hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, c.stream, cp, sp, (u32)cnt, (u32)items, log_size, tw_end,
-                                   np == 1 ? n_inv : 0u);
-            }
-            TSTWO_LAUNCH_CHECK();
-        }
-        for (int s = 1; s < np; s++) {
-            int rc = launch_fast<true>(dst, n_cols, log_size, passes[s], tw_end, s == np - 1 ? n_inv : 0u);
-            if (rc) return rc;
-        }
-        return TSTWO_OK;
-    }
+    if (int rc = check_log_size(log_size)) return rc;
+    CfftPlan plan;
+    const char *refused = plan_for(CFFT_INTERPOLATE_TO, 0, log_size, n_cols, plan);
+    if (refused || plan.route != CFFT_FALLBACK)
+        return cfft_planned(CFFT_INTERPOLATE_TO, 0, dst, src, n_cols, log_size, half_initial, itw, tw_log, plan, refused);
     for (size_t i = 0; i < n_cols; i++) {
         int rc = tstwo_copy(dst[i], src[i], (size_t)4 << log_size);
         if (rc) return rc;
     }
-    return cfft<true>(dst, n_cols, log_size, half_initial, itw, tw_log);
+    return cfft(true, dst, n_cols, log_size, half_initial, itw, tw_log);
 }
 
 // CirclePoly.extend + evaluate (backend/cpu/circle.ts:71-134) in one call: polys[i] holds 2^log_poly coefficients,
@@ -801,35 +574,17 @@ int tstwo_cfft_evaluate_extended(const u32 *const *polys, u32 log_poly, u32 *con
     if (!polys || !out) return set_error(TSTWO_ERR_BAD_ARG, "cfft: null column table");
     TSTWO_REQUIRE_TABLE(polys, n_cols); TSTWO_REQUIRE_TABLE(out, n_cols);
     if (log_size < log_poly) return set_error(TSTWO_ERR_LOG_SIZE, "log size too small");
-    if (log_size == 0 || log_size > 31) return set_error(TSTWO_ERR_BAD_ARG, "cfft: log_size out of range");
+    if (int rc = check_log_size(log_size)) return rc;
     const u32 ext = log_size - log_poly;
-    Pass passes[8];
-    int np = 0;
-    const Knobs &kn = knobs();
-    const bool tiled = log_size >= kMaxLogTileB && log_size <= kMaxLogSize && !kn.cfft_kb && !kn.cfft_ka;
-    if (tiled) np = log_size == 14 ? plan_passes(log_size, passes, kMaxLogTileB) : plan_default(log_size, n_cols, passes);   // (n = 14: 13 + 1 keeps the fused extension)
-    if (tiled && np >= 2 && (ext == 1 || ext == 2) && passes[np - 1].k >= 2) {
-        if (!tw) return set_error(TSTWO_ERR_BAD_ARG, "cfft: null twiddle buffer");
-        if (tw_log > 31 || ((size_t)1 << (log_size - 1)) > ((size_t)1 << tw_log)) return set_error(TSTWO_ERR_TWIDDLES, "Not enough twiddles!");
-        for (size_t i = 0; i < n_cols; i++)
-            if ((((uintptr_t)out[i]) & 15) || (((uintptr_t)polys[i]) & 15)) return set_error(TSTWO_ERR_BAD_ARG, "cfft: columns must be 16-byte aligned");
-        if (((uintptr_t)tw) & 15) return set_error(TSTWO_ERR_BAD_ARG, "cfft: twiddle buffer must be 16-byte aligned");
-        const u32 *tw_end = tw + ((size_t)1 << tw_log);
-        const Pass &top = passes[np - 1];
-        int rc = ext == 1 ? launch_a_ext_k<1>(top.k, top.c + top.k, out, polys, n_cols, log_size, top.lo, tw_end)
-                          : launch_a_ext_k<2>(top.k, top.c + top.k, out, polys, n_cols, log_size, top.lo, tw_end);
-        if (rc) return rc;
-        for (int s = np - 2; s >= 0; s--) {
-            rc = launch_fast<false>(out, n_cols, log_size, passes[s], tw_end, 0);
-            if (rc) return rc;
-        }
-        return TSTWO_OK;
-    }
+    CfftPlan plan;
+    const char *refused = plan_for(CFFT_EVALUATE_EXTENDED, ext, log_size, n_cols, plan);
+    if (refused || plan.route != CFFT_FALLBACK)
+        return cfft_planned(CFFT_EVALUATE_EXTENDED, ext, out, polys, n_cols, log_size, half_initial, tw, tw_log, plan, refused);
     for (size_t i = 0; i < n_cols; i++) {
         int rc = tstwo_poly_extend(polys[i], log_poly, out[i], log_size);
         if (rc) return rc;
     }
-    return cfft<false>(out, n_cols, log_size, half_initial, tw, tw_log);
+    return cfft(false, out, n_cols, log_size, half_initial, tw, tw_log);
 }
 
 }  // extern "C"
