@@ -606,6 +606,32 @@ int tstwo_logup_column(const tstwo_logup_frac *fracs, size_t n_fracs, const uint
  * the 4 words of claimed.  1 <= log_size <= 28.  Synchronous; refused during graph capture. */
 int tstwo_logup_finalize_last(uint32_t *const col[4], uint32_t log_size, uint32_t claimed_sum[4]);
 
+/* ---------------------------------------------------------------- Lookup multiplicities
+ * The multiplicity column of a lookup table, counted on the device: a histogram of M31 columns into a column of 2^log_range
+ * words (tstwo_amd/logup.py lookup_multiplicities; the host version is constraint_framework.range_check_multiplicities). */
+#define TSTWO_LOOKUP_ORDER_NATURAL 0   /* bin k at word k (an MLE / GKR LogUpMultiplicities numerator column) */
+#define TSTWO_LOOKUP_ORDER_COSET   1   /* bin k at the storage position of coset row k: coset_pos(k) of coset_order.cuh,
+                                          the order of range_check_table_column / range_check_multiplicities */
+#define TSTWO_LOOKUP_MAX_COLS 64
+#define TSTWO_LOOKUP_MAX_LOG  28
+/* out[place(k)] = the number of words equal to k over all columns, k < 2^log_range.
+ *   cols: a host array of n_cols device columns, column c of lens[c] words (lens: host; any length, 0 and lengths that are no
+ *   power of two or multiple of 4 included; any 4-byte alignment);  out: 2^log_range device words, overwritten completely (the
+ *   entry zeroes it itself).
+ * A word >= 2^log_range is counted in no bin and never used as an index.  n_rejected (a device word, or NULL) receives the
+ * number of such words, 0 when there are none; with NULL they are skipped silently.
+ * Limits (TSTWO_ERR_BAD_ARG, text "lookup: ..." in tstwo_last_error): 1 <= log_range <= TSTWO_LOOKUP_MAX_LOG ("log_range must
+ * be 1 to 28"), 1 <= n_cols <= TSTWO_LOOKUP_MAX_COLS ("1 to 64 columns"), sum(lens) <= 2^31 - 2 so that every count is a
+ * canonical M31 value ("more than 2^31 - 2 values"), order 0 or 1 ("order must be 0 (natural) or 1 (coset)"), no null pointer
+ * except n_rejected ("null ..."), out overlaps no column ("out is one of the columns") and does not hold n_rejected.
+ * Counts are integer atomics: the result is the same bit for bit on every run.  The column table is uploaded through the
+ * small-upload ring: refused during graph capture.  Asynchronous. */
+int tstwo_lookup_multiplicities(const uint32_t *const *cols, const size_t *lens, size_t n_cols, uint32_t log_range, uint32_t order,
+                                uint32_t *out, uint32_t *n_rejected);
+/* out[coset_pos(k)] = k for k < 2^log_size: the preprocessed column of a range-check table (range_check_table_column).
+ * 1 <= log_size <= TSTWO_LOOKUP_MAX_LOG ("lookup: log_size must be 1 to 28").  Asynchronous; refused during graph capture. */
+int tstwo_coset_iota(uint32_t *out, uint32_t log_size);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,7 @@ from .constraint_framework import (FrameworkComponent, MulAddComponent, MulAddEv
                                    WideFibonacciComponent, WideFibonacciEval, compile_columns, evaluate_columns,
                                    state_machine_trace)
 from .logup import (INTERACTION_TRACE_IDX, LogupColGenerator, LogupTraceGenerator, LookupElements,  # noqa: F401
-                    RelationEntry, derive_interaction_trace, deriveInteractionTrace)
+                    RelationEntry, coset_iota, derive_interaction_trace, deriveInteractionTrace, lookup_multiplicities)
 from .prover import (ConstraintsNotSatisfied, InvalidLogupSum, InvalidStructure, OodsNotMatching, StarkProof, prove,  # noqa: F401
                      verify)
 

@@ -175,6 +175,8 @@ _SIGS = {
     "tstwo_air_eval_columns": [C.POINTER(vp), C.c_size_t, C.c_uint32, u32p, C.c_size_t, C.POINTER(vp), C.c_size_t],
     "tstwo_logup_column": [C.POINTER(LogupFrac), C.c_size_t, C.POINTER(vp), C.c_uint32, P4],
     "tstwo_logup_finalize_last": [P4, C.c_uint32, u32p],
+    "tstwo_lookup_multiplicities": [C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp],
+    "tstwo_coset_iota": [vp, C.c_uint32],
 }
 ALLOC_POOL, ALLOC_DIRECT, ALLOC_ASYNC, ALLOC_POISON = 0, 1, 2, 0x10
 # c_void_p arguments above are DEVICE addresses, except these (host memory of any element type)

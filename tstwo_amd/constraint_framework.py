@@ -1264,6 +1264,19 @@ def range_check_multiplicities(log_range: int, *value_columns):
     return m
 
 
+def range_check_table_column_device(log_range: int):
+    """range_check_table_column built on the device (logup.coset_iota): a HipColumn."""
+    from .logup import coset_iota
+    return coset_iota(log_range)
+
+
+def range_check_multiplicities_device(log_range: int, *value_columns, check: bool = True):
+    """range_check_multiplicities counted on the device (logup.lookup_multiplicities, coset order): a HipColumn.  value_columns:
+    HipColumns, which stay where they are, or arrays.  check=False skips the one-word read-back that raises the ValueError."""
+    from .logup import lookup_multiplicities
+    return lookup_multiplicities(log_range, *value_columns, order="coset", check=check)
+
+
 def range_check_table_interaction_trace(log_range: int, multiplicity, lookup_elements: LookupElements):
     """The interaction trace of RangeCheckTableEval: (4 HipCircleEvaluations, claimed sum); multiplicity: HipColumn or array."""
     import numpy as np

@@ -12,8 +12,7 @@
 //
 // Coset-order prefix sum (tstwo_logup_finalize_last).  Rows are stored bit-reversed on the circle domain; "previous row" (mask
 // offset -1) is the coset order.  With L = log_size - 1, j = k >> 1 and rev = bit reversal over L bits, coset row k lives at
-//   2 rev(j)                       for even k  (the A part of j)
-//   2 (2^L - 1 - rev(j)) + 1       for odd k   (the B part of j; 2^L - 1 - rev(j) = ~rev(j) over L bits)
+// coset_pos(k, L) (coset_order.cuh): 2 rev(j) for even k (the A part of j), 2 (2^L - 1 - rev(j)) + 1 for odd k (the B part).
 // A block is a run of 2^R consecutive j (2^(R+1) coset rows); with j = top 2^R + low its A parts sit at
 // rev(j) = rev_R(low) 2^(L-R) + rev_{L-R}(top), a stride of 2^(L-R).  A tile takes the G blocks whose rev(top) are g G + y, y < G:
 // 2^R runs of 2G contiguous words (G A parts and G B parts interleaved).  The B parts in those words belong to the blocks of the
@@ -28,6 +27,7 @@
 #include <string>
 
 #include "common.h"
+#include "coset_order.cuh"
 
 using namespace tstwo;
 
@@ -184,8 +184,6 @@ constexpr u32 kLanesPerBlock = 8;
 static_assert(kThreads == 2 * kG * kLanesPerBlock, "8 lanes per block, 2G blocks per workgroup");
 static_assert((1u << 4) == kG, "kMinTiledLog assumes G = 16");
 
-__device__ __forceinline__ u32 rev_bits(u32 x, u32 bits) { return bits ? __brev(x) >> (32 - bits) : 0u; }
-
 // 2^(-log) mod P = 2^(31 - log) (2^31 = 1 mod P)
 __device__ __forceinline__ u32 inv_pow2(u32 log) { return log == 0 ? 1u : (1u << (31 - log)); }
 
@@ -203,11 +201,6 @@ __device__ u32 wg_scan(u32 v, u32 *sh, u32 *total) {
     *total = sh[kThreads - 1];
     __syncthreads();
     return r;
-}
-
-__device__ __forceinline__ u32 coset_pos(u32 k, u32 L) {
-    const u32 r = rev_bits(k >> 1, L);
-    return (k & 1u) ? 2u * (((1u << L) - 1u) - r) + 1u : 2u * r;
 }
 
 // one workgroup per coordinate, the whole column (at most kSmallMax words) in LDS; claimed[coord] = its sum

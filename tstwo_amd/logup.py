@@ -158,6 +158,34 @@ def logup_finalize_last(col: SecureColumnByCoords, log_size: int) -> QM31:
     return QM31.from_u32_unchecked(*claimed)
 
 
+ORDERS = {"natural": 0, "coset": 1}     # include/tstwo_hip.h TSTWO_LOOKUP_ORDER_*
+
+
+def lookup_multiplicities(log_range: int, *value_columns, order: str = "coset", check: bool = True) -> HipColumn:
+    """tstwo_lookup_multiplicities: the column of 2^log_range counts, count of k = the number of words equal to k over
+    `value_columns` (HipColumns of any length, or arrays, which are uploaded).  order "coset": the count of k at the storage
+    position of coset row k, a trace column beside range_check_table_column; "natural": at word k (an MLE).
+    check=True reads one word back and raises ValueError when a value lies outside [0, 2^log_range); check=False reads nothing
+    back and skips such values."""
+    if order not in ORDERS:
+        raise ValueError(f"order is 'natural' or 'coset', not {order!r}")
+    cols = [c if isinstance(c, HipColumn) else HipColumn(c) for c in value_columns]
+    out = HipColumn.uninitialized(1 << log_range)
+    rejected = HipColumn.uninitialized(1) if check else None
+    L.call("tstwo_lookup_multiplicities", L.ptr_array([c.ptr for c in cols]), (C.c_size_t * max(len(cols), 1))(*[c.len() for c in cols]),
+           len(cols), log_range, ORDERS[order], out.ptr, rejected.ptr if check else None)
+    if check and int(rejected.to_numpy()[0]):
+        raise ValueError("a checked value lies outside the range")
+    return out
+
+
+def coset_iota(log_size: int) -> HipColumn:
+    """tstwo_coset_iota: value k at the storage position of coset row k (the preprocessed column of a range-check table)."""
+    out = HipColumn.uninitialized(1 << log_size)
+    L.call("tstwo_coset_iota", out.ptr, log_size)
+    return out
+
+
 # ------------------------------------------------------------------ the generator (Rust LogupTraceGenerator)
 class LogupTraceGenerator:
     """The interaction trace of one component on whole device columns: new_col() per batch, write_frac() per fraction of the
