@@ -112,7 +112,7 @@ int tstwo_zero(void *dev, size_t bytes);                                  /* asy
  * TSTWO_ERR_BAD_ARG "host-array upload during graph capture" and records nothing); allocations must hit the
  * library's caching allocator (run the sequence once eagerly first); all buffers the sequence uses must outlive the
  * graph, which addresses them by value.  The library's own scratch block (the ticket, partial sums and eq tables of
- * tstwo_gkr_sum_poly_async, tstwo_gkr_round and tstwo_gkr_gen_eq_evals live in it) is recorded by value too: a block that a
+ * tstwo_gkr_sum_poly_async, tstwo_gkr_round[_dev] and tstwo_gkr_gen_eq_evals live in it) is recorded by value too: a block that a
  * later call outgrows is retired, not freed, and stays mapped until tstwo_shutdown, so a graph may be replayed after any
  * eager call, however much scratch that call needed.  A captured call that would itself have to grow the block fails with
  * TSTWO_ERR_BAD_ARG "scratch growth during graph capture" and records nothing; the eager run of the sequence sizes it. */
@@ -483,6 +483,35 @@ int tstwo_gkr_round(uint32_t kind, const uint32_t *const eq[4], const uint32_t *
  * 2^(log_n-1) secure outputs.  The secure form may run in place (out == in). */
 int tstwo_mle_fix_first_variable_base(const uint32_t *in, uint32_t log_n, const uint32_t r[4], uint32_t *const out[4]);
 int tstwo_mle_fix_first_variable_secure(const uint32_t *const in[4], uint32_t log_n, const uint32_t r[4], uint32_t *const out[4]);
+/* The same three with the challenge r read from device memory: r_dev = 4 words, 16-byte aligned, written earlier on the stream
+ * (the challenge_out of tstwo_gkr_round_finish).  Same contracts and results as the by-value calls; lambda stays by value. */
+int tstwo_gkr_round_dev(uint32_t kind, const uint32_t *const eq[4], const uint32_t *const num[4], const uint32_t *const den[4],
+                        uint32_t *const out_num[4], uint32_t *const out_den[4], uint32_t n_vars, const uint32_t *r_dev,
+                        const uint32_t lambda[4], uint32_t *out_dev);
+int tstwo_mle_fix_first_variable_base_dev(const uint32_t *in, uint32_t log_n, const uint32_t *r_dev, uint32_t *const out[4]);
+int tstwo_mle_fix_first_variable_secure_dev(const uint32_t *const in[4], uint32_t log_n, const uint32_t *r_dev, uint32_t *const out[4]);
+/* The end of one round of the batched sum-check of prove_batch (sumcheck.ts:99-227 with the oracles of gkr_prover.ts:290-420), in
+ * one single-wave launch and without a read-back: everything the host does between the sums of a round and the launches of the
+ * next.  Asynchronous.
+ *   chan             device: the Blake2s channel, 10 words (digest[8], n_challenges, n_sent), Rust draw semantics; updated
+ *   sums             device: 8 words per instance, the (f(0), f(2)) slot of tstwo_gkr_sum_poly_async / tstwo_gkr_round[_dev]; read
+ *                    for active instances only
+ *   state            device: 8 words per instance, claim[4] then eq correction[4]; updated in place
+ *   n_instances      1 .. 64;  active_mask: bit i set = instance i's oracle takes part in this round (else it contributes the
+ *                    constant claim_i / 2)
+ *   y_k, inv_eq0     host words: y[n - k] and a = 1 / eq({0}^(n-k+1), y[:n-k+1]) of correctSumAsPolyInFirstVariable
+ *                    (gkr_prover.ts:609-660)
+ *   alpha            host words: the sum-check's batching challenge
+ *   round_poly_out   device, 20 words: word 0 = n_coeffs (index of the highest non-zero coefficient + 1: the coefficients the
+ *                    channel mixed), words 1-3 = 0, words 4..19 = the 4 coefficients of sum_i alpha^i p_i (zero from n_coeffs on)
+ *   challenge_out    device, 4 words: the challenge drawn after mixing the round polynomial (the next round's r_dev)
+ * Per instance: p_i = the corrected round polynomial through (0, r0), (1, claim - r0), (2, r2), (b, 0) or claim_i / 2;
+ * claim_i <- p_i(challenge); correction_i <- correction_i * eq(challenge, y_k) for active instances.  sums, state, round_poly_out
+ * and challenge_out are 16-byte aligned.  A y_k for which the reference divides by zero (0, 1, 1/2, 1/3) fails with
+ * TSTWO_ERR_BAD_ARG "sum-check: degenerate eq point" before anything is enqueued. */
+int tstwo_gkr_round_finish(uint32_t *chan, const uint32_t *sums, uint32_t *state, uint32_t n_instances, uint64_t active_mask,
+                           const uint32_t y_k[4], const uint32_t inv_eq0[4], const uint32_t alpha[4], uint32_t *round_poly_out,
+                           uint32_t *challenge_out);
 
 /* ---------------------------------------------------------------- AIR (constraint evaluation, composition polynomial)
  * Rust stwo constraint_framework/component.rs (the reference's constraint_framework/index.ts, air/accumulator.ts,

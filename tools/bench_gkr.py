@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """LogUp-GKR on one MI355X: per-op device time (HIP events, median of --reps after --warmup) at n = 20 and 24 with GB/s and
 the fraction of 8 TB/s, the VALU issue bound of each sum kernel (VALU instructions of its loop body, from the ISA, times the
-terms, at the one-port integer peak of DESIGN §4), and prove_batch wall time split into device time, synchronous read-backs
-and the host remainder.  Prints one JSON line.
+terms, at the one-port integer peak of DESIGN §4), and prove_batch wall time on each path (sum-check rounds on the device / the
+host loop, run alternately in one process) split into device time, synchronous read-backs and the host remainder.  Prints one
+JSON line.  The time of k_gkr_round_finish per launch comes from a separate `rocprofv3 --kernel-trace --stats -- python
+tools/bench_gkr.py --no-ops --sizes 20 --paths device` run.
 
-    python tools/bench_gkr.py [--sizes 20,24] [--reps 20] [--warmup 3] [--prove-reps 3]
+    python tools/bench_gkr.py [--sizes 20,24] [--reps 20] [--warmup 3] [--prove-reps 9] [--paths device,host] [--no-ops] [--out FILE]
 """
 from __future__ import annotations
 
@@ -148,45 +150,56 @@ def make_instance(rng, kind, n):
     return G.Layer.logup_singles(den)
 
 
-def bench_prove(layers, reps):
-    """Wall time of prove_batch split into: device time (HIP events from the first library call after a read-back to the next
-    read-back: the kernels of that stretch plus the host's launch gaps between them), the count of synchronous read-backs, and
-    the rest (host protocol work between a read-back and the next launch, the read-backs' own latency)."""
-    rec = []
+PATHS = {"device": {"device_rounds": True}, "host": {"device_rounds": False}, "default": {}}
+
+
+def bench_prove(layers, reps, paths=("device", "host")):
+    """Wall time of prove_batch on each of `paths` (PATHS: the sum-check rounds on the device, the host loop, or the call without
+    the keyword), run alternately in this process on the same layers, split into: device time (HIP events from the first library
+    call after a read-back to the next read-back: the kernels of that stretch plus the host's launch gaps between them), the count
+    of synchronous read-backs, and the rest (host protocol work between a read-back and the next launch, the read-backs' own
+    latency).  Per path: the median repetition, and the spread (min, max) of the wall time over the repetitions."""
+    rec = {p: [] for p in paths}
     orig_dm, orig_call = L.download_many, L.call
     for it in range(reps + 1):
-        st = {"readbacks": 0, "device_s": 0.0}
-        seg = [None]
+        for path in paths:
+            st = {"readbacks": 0, "device_s": 0.0}
+            seg = [None]
 
-        def call(name, *args, seg=seg):
-            if seg[0] is None and name.startswith(("tstwo_gkr_", "tstwo_mle_")):     # the first launch of the stretch
-                seg[0] = L.Event().record()
-            return orig_call(name, *args)
+            def call(name, *args, seg=seg):
+                if seg[0] is None and name.startswith(("tstwo_gkr_", "tstwo_mle_")):     # the first launch of the stretch
+                    seg[0] = L.Event().record()
+                return orig_call(name, *args)
 
-        def dm(pieces, st=st, seg=seg):
-            if seg[0] is not None:
-                stop = L.Event().record()
-                st["device_s"] += seg[0].elapsed_ms(stop) * 1e-3
-            res = orig_dm(pieces)
-            st["readbacks"] += 1
-            seg[0] = None
-            return res
-        L.sync()
-        L.download_many, L.call = dm, call
-        t0 = time.perf_counter()
-        try:
-            G.prove_batch(Blake2sChannel(), layers)
+            def dm(pieces, st=st, seg=seg):
+                if seg[0] is not None:
+                    stop = L.Event().record()
+                    st["device_s"] += seg[0].elapsed_ms(stop) * 1e-3
+                res = orig_dm(pieces)
+                st["readbacks"] += 1
+                seg[0] = None
+                return res
             L.sync()
-        finally:
-            L.download_many, L.call = orig_dm, orig_call
-        wall = time.perf_counter() - t0
-        if it:                              # the first run warms the allocator and the code paths
-            rec.append((wall, st))
-    wall, st = sorted(rec, key=lambda x: x[0])[len(rec) // 2]
-    return {"wall_ms": round(wall * 1e3, 2), "device_ms": round(st["device_s"] * 1e3, 2), "readbacks": st["readbacks"],
-            "outside_kernels_ms": round((wall - st["device_s"]) * 1e3, 2),
-            "outside_kernels_frac": round(1 - st["device_s"] / wall, 3),
-            "per_readback_outside_us": round((wall - st["device_s"]) / max(st["readbacks"], 1) * 1e6, 1)}
+            L.download_many, L.call = dm, call
+            t0 = time.perf_counter()
+            try:
+                G.prove_batch(Blake2sChannel(), layers, **PATHS[path])
+                L.sync()
+            finally:
+                L.download_many, L.call = orig_dm, orig_call
+            wall = time.perf_counter() - t0
+            if it:                              # the first run warms the allocator and the code paths
+                rec[path].append((wall, st))
+    out = {}
+    for path in paths:
+        runs = sorted(rec[path], key=lambda x: x[0])
+        wall, st = runs[len(runs) // 2]
+        out[path] = {"wall_ms": round(wall * 1e3, 2), "wall_ms_min": round(runs[0][0] * 1e3, 2), "wall_ms_max": round(runs[-1][0] * 1e3, 2),
+                     "reps": len(runs), "device_ms": round(st["device_s"] * 1e3, 2), "readbacks": st["readbacks"],
+                     "outside_kernels_ms": round((wall - st["device_s"]) * 1e3, 2),
+                     "outside_kernels_frac": round(1 - st["device_s"] / wall, 3),
+                     "per_readback_outside_us": round((wall - st["device_s"]) / max(st["readbacks"], 1) * 1e6, 1)}
+    return out
 
 
 def main():
@@ -194,23 +207,32 @@ def main():
     ap.add_argument("--sizes", default="20,24")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--prove-reps", type=int, default=3)
+    ap.add_argument("--prove-reps", type=int, default=9)
+    ap.add_argument("--paths", default="device,host", help="prove_batch paths, run alternately: " + ", ".join(PATHS))
+    ap.add_argument("--no-ops", action="store_true", help="skip the per-op timings")
+    ap.add_argument("--out", default=None, help="also write the JSON result to this file (profiles/gkr_device_rounds.json)")
     a = ap.parse_args()
+    paths = tuple(a.paths.split(","))
     L.init(0)
-    valu = sum_valu_counts()
     res = {"tool": "bench_gkr", "device": L.device_name(), "valu_one_port_lane_ops": VALU_ONE_PORT, "ops": {}, "prove_batch": {}}
+    valu = None if a.no_ops else sum_valu_counts()
     for n in [int(s) for s in a.sizes.split(",")]:
-        res["ops"][str(n)] = bench_ops(n, a.reps, a.warmup, valu)
-        L.call("tstwo_trim")
+        if not a.no_ops:
+            res["ops"][str(n)] = bench_ops(n, a.reps, a.warmup, valu)
+            L.call("tstwo_trim")
         rng = np.random.default_rng(1000 + n)
         single = [make_instance(rng, G.LOGUP_GENERIC, n)]
-        res["prove_batch"][f"logup_generic_{n}"] = bench_prove(single, a.prove_reps)
+        res["prove_batch"][f"logup_generic_{n}"] = bench_prove(single, a.prove_reps, paths)
         mixed = [make_instance(rng, G.LOGUP_GENERIC, n), make_instance(rng, G.GRAND_PRODUCT, n - 2),
                  make_instance(rng, G.LOGUP_MULTIPLICITIES, n - 4), make_instance(rng, G.LOGUP_SINGLES, n - 6)]
-        res["prove_batch"][f"mixed_{n}"] = bench_prove(mixed, a.prove_reps)
+        res["prove_batch"][f"mixed_{n}"] = bench_prove(mixed, a.prove_reps, paths)
         del single, mixed
         L.call("tstwo_trim")
-    print(json.dumps(res))
+    text = json.dumps(res)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(text)
 
 
 if __name__ == "__main__":

@@ -113,13 +113,16 @@ class DeviceChannel:
         self.buf = buf if buf is not None else L.DeviceBuffer(64)
         self.load(host)
 
-    def load(self, host: Blake2sChannel) -> None:
-        """(Re)start from the host channel's state (one 64-byte upload)."""
+    def load(self, host: Blake2sChannel, tail=None) -> None:
+        """(Re)start from the host channel's state (one 64-byte upload).  tail: words the owner of a larger buffer keeps behind the
+        16 state words, sent in the same upload."""
         import numpy as np
         if host.ts_compat:
             raise ValueError("the device channel implements the Rust draw semantics only")
         self.host = host
-        st = np.zeros(16, dtype=np.uint32)
+        st = np.zeros(16 + (0 if tail is None else len(tail)), dtype=np.uint32)
+        if tail is not None:
+            st[16:] = tail
         st[:8] = np.frombuffer(host.digest(), dtype="<u4")
         st[8], st[9] = host.n_challenges, host.n_sent
         self.buf.upload(st)

@@ -9,8 +9,12 @@
 //   sums            k_sum<KIND, FOLD>: (f(0), f(2)) of the round polynomial, block partials + a last-block ticket (one launch).
 //                   FOLD = the fused sumcheck round of prove_batch: the layer is first folded by the previous round's challenge
 //                   (written back, in place for secure columns) and the sum is taken over the folded values.
+//                   Fold and FOLD take their challenge by value or from 4 device words an earlier launch wrote (the _dev entries).
+//   round finish    k_gkr_round_finish: the O(instances) end of a sum-check round by one wave — round polynomials, combination,
+//                   Blake2s channel mix + draw, new claims — so that a layer of prove_batch is enqueued without a read-back.
 // M31 addition is exact, so the reduction order does not change a bit of the result.
 #include "common.h"
+#include "blake2s.cuh"
 
 using namespace tstwo;
 
@@ -116,11 +120,20 @@ __global__ void __launch_bounds__(kThreads) k_next_layer(CSoa4 num, CSoa4 den, S
     }
 }
 
+// A QM31 that an earlier launch on the stream left in device memory (16-byte aligned), the same for every lane: one load, then
+// scalar registers, so a kernel that takes its challenge this way keeps the register budget of the by-value form.
+__device__ __forceinline__ qm31 ld_uniform_q(const u32 *p) {
+    const uint4 v = gload4(p);
+    return {(u32)__builtin_amdgcn_readfirstlane((int)v.x), (u32)__builtin_amdgcn_readfirstlane((int)v.y),
+            (u32)__builtin_amdgcn_readfirstlane((int)v.z), (u32)__builtin_amdgcn_readfirstlane((int)v.w)};
+}
+
 // ---------------------------------------------------------------- fix_first_variable (mle.ts:68-130)
 // out[i] = in[i] + r (in[i + half] - in[i]); W = 4: 16-byte accesses.  In place (out == in) is safe: lane i reads i and
 // i + half and writes i only.
 template <bool BASE, int W>
-__global__ void __launch_bounds__(kThreads) k_fold(CSoa4 in, qm31 r, Soa4 out, u32 half) {
+__global__ void __launch_bounds__(kThreads) k_fold(CSoa4 in, qm31 r, const u32 *__restrict__ r_dev, Soa4 out, u32 half) {
+    if (r_dev) r = ld_uniform_q(r_dev);         // the challenge an earlier launch drew (tstwo_gkr_round_finish)
     const u32 stride = gridDim.x * kThreads;
     for (u32 t = blockIdx.x * kThreads + threadIdx.x; t < half / W; t += stride) {
         const u32 i = t * W;
@@ -161,6 +174,7 @@ struct SumArgs {
     CSoa4 num, den;      // GP: den = the product column
     Soa4 onum, oden;     // FOLD: where the folded layer goes (may alias num / den for secure columns)
     qm31 lambda, r;
+    const u32 *r_dev;    // FOLD: non-null = r is read from these 4 device words instead (tstwo_gkr_round_dev)
     u32 n_terms;
     u32 *slab, *ticket, *out;
 };
@@ -215,6 +229,7 @@ __global__ void __launch_bounds__(kThreads) k_sum(SumArgs a) {
     __shared__ u32 lds[8 * (kThreads / 64) + 1];       // wave partials; [last] = "this block is the last arriver"
     u32 acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const u32 nt = a.n_terms, stride = gridDim.x * kThreads;
+    if (FOLD && a.r_dev) a.r = ld_uniform_q(a.r_dev);
     for (u32 i = blockIdx.x * kThreads + threadIdx.x; i < nt; i += stride) {
         const u32 p0 = 2 * i, p1 = 2 * (nt + i);
         const qm31 n00 = num_at<KIND, FOLD>(a, p0), n01 = num_at<KIND, FOLD>(a, p0 + 1);
@@ -290,8 +305,9 @@ Soa4 soa(u32 *const c[4]) { return {{c[0], c[1], c[2], c[3]}}; }
 CSoa4 csoa1(const u32 *c) { return {{c, c, c, c}}; }
 
 // Checks and launches one sum (fold: the fused round); `out` = 8 device-visible words.
+// The fold's challenge is r (host words) or, when r_dev is given, 4 words of device memory written earlier on the stream.
 int gkr_sum(u32 kind, const u32 *const eq[4], const u32 *const num[4], const u32 *const den[4], u32 *const onum[4],
-            u32 *const oden[4], u32 n_vars, const u32 r[4], const u32 lambda[4], u32 *out, bool fold) {
+            u32 *const oden[4], u32 n_vars, const u32 r[4], const u32 *r_dev, const u32 lambda[4], u32 *out, bool fold) {
     if (!valid_kind(kind)) return set_error(TSTWO_ERR_BAD_ARG, "unknown GKR layer kind");
     if (n_vars == 0) return set_error(TSTWO_ERR_ZERO_VARIABLES, "Number of variables must not be zero");
     if (n_vars + 1 + (fold ? 1 : 0) > kMaxLog) return set_error(TSTWO_ERR_BAD_ARG, "GKR layer too large");
@@ -305,8 +321,10 @@ int gkr_sum(u32 kind, const u32 *const eq[4], const u32 *const num[4], const u32
     if (kind == TSTWO_GKR_LOGUP_GENERIC) { TSTWO_REQUIRE_TABLE(num, 4); a.num = csoa(num); }
     if (kind == TSTWO_GKR_LOGUP_MULTIPLICITIES) { TSTWO_REQUIRE_TABLE(num, 1); a.num = csoa1(num[0]); }
     if (fold) {
-        if (!r) return set_error(TSTWO_ERR_BAD_ARG, "null challenge");
-        a.r = qarg(r);
+        if (!r && !r_dev) return set_error(TSTWO_ERR_BAD_ARG, "null challenge");
+        if (!aligned16(r_dev)) return set_error(TSTWO_ERR_BAD_ARG, "device challenge is not 16-byte aligned");
+        if (r) a.r = qarg(r);
+        a.r_dev = r ? nullptr : r_dev;
         TSTWO_REQUIRE_TABLE(oden, 4);
         a.oden = soa(oden);
         if (kind == TSTWO_GKR_LOGUP_GENERIC || kind == TSTWO_GKR_LOGUP_MULTIPLICITIES) { TSTWO_REQUIRE_TABLE(onum, 4); a.onum = soa(onum); }
@@ -329,9 +347,195 @@ int gkr_sum(u32 kind, const u32 *const eq[4], const u32 *const num[4], const u32
     }
 }
 
+// Checks and launches one fold; base: in[0] is the one M31 column.  The challenge is r (host words) or, when r is null, the 4
+// device words at r_dev.
+int mle_fold(bool base, const u32 *const in[4], u32 log_n, const u32 r[4], const u32 *r_dev, u32 *const out[4]) {
+    if (log_n == 0) return TSTWO_OK;                 // a constant: midpoint 0, nothing to write (mle.ts:68-80)
+    if (log_n > kMaxLog) return set_error(TSTWO_ERR_BAD_ARG, "MLE too large");
+    if (!r && !r_dev) return set_error(TSTWO_ERR_BAD_ARG, "null assignment");
+    if (!r && !aligned16(r_dev)) return set_error(TSTWO_ERR_BAD_ARG, "device challenge is not 16-byte aligned");
+    if (base) TSTWO_REQUIRE_PTRS(in[0]);
+    else TSTWO_REQUIRE_TABLE(in, 4);
+    TSTWO_REQUIRE_TABLE(out, 4);
+    const u32 half = 1u << (log_n - 1);
+    const CSoa4 i4 = csoa(in);
+    const Soa4 o = soa(out);
+    const qm31 rv = r ? qarg(r) : qm31{0u, 0u, 0u, 0u};
+    const u32 *rd = r ? nullptr : r_dev;
+    const bool wide = half % 4 == 0 && all_aligned16(i4) && all_aligned16(o);
+    const dim3 g(wide ? grid_for(half / 4, 32) : grid_for(half, 32)), b(kThreads);
+    if (base && wide) hipLaunchKernelGGL((k_fold<true, 4>), g, b, 0, ctx().stream, i4, rv, rd, o, half);
+    else if (base) hipLaunchKernelGGL((k_fold<true, 1>), g, b, 0, ctx().stream, i4, rv, rd, o, half);
+    else if (wide) hipLaunchKernelGGL((k_fold<false, 4>), g, b, 0, ctx().stream, i4, rv, rd, o, half);
+    else hipLaunchKernelGGL((k_fold<false, 1>), g, b, 0, ctx().stream, i4, rv, rd, o, half);
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
+}
+
+// ---------------------------------------------------------------- the end of a sum-check round (gkr_prover.ts:609-660, sumcheck.ts:99-227)
+// Everything prove_batch's host loop does between the sums of one round and the launches of the next, by ONE wave: lane i owns
+// instance i (its claim, its eq correction, its round polynomial p_i); the combined polynomial, the channel and the challenge are
+// wave-uniform.
+//
+// An active instance's p_i is the cubic through (0, r0), (1, r1), (2, r2), (b, 0) with r0 = f0 c (1 - y) a, r1 = claim - r0,
+// r2 = f2 c (3y - 1) a, b = (1 - y) / (1 - 2y) (c = the instance's correction, a = inv_eq0, y = y_k).  Written as
+// p_i(x) = (x - b) (w0 (x-1)(x-2) + w1 x(x-2) + w2 x(x-1)) the Lagrange weights are w0 = r0 / (-2b), w1 = -r1 / (1 - b),
+// w2 = r2 / (2 (2 - b)); with D = 1 - 2y: 1/b = D / (1 - y), 1/(1 - b) = -D / y, 1/(2 - b) = D / (1 - 3y), so the factors
+// (1 - y) and (3y - 1) of r0 and r2 cancel and, with g0 = f0 c a D and g2 = f2 c a D,
+//     w0 = -g0 / 2,   w1 = (claim D - g0 (1 - y)) / y,   w2 = -g2 / 2.
+// Only y and D are inverted — wave-uniform, one qm31_inv for both (Montgomery) — and nothing per instance.  The field is exact, so
+// the coefficients are the host path's bit for bit.  The entry point refuses the y for which the host path divides by zero.
+struct FinishArgs {
+    u32 *chan;
+    const u32 *sums;
+    u32 *state;
+    u32 n;
+    u64 mask;
+    qm31 y, a, alpha;
+    u32 *poly_out, *ch_out;
+};
+__device__ __forceinline__ qm31 q_of(uint4 v) { return {v.x, v.y, v.z, v.w}; }
+__device__ __forceinline__ uint4 u4_of(qm31 v) { return make_uint4(v.a, v.b, v.c, v.d); }
+
+__global__ void __launch_bounds__(64) k_gkr_round_finish(FinishArgs f) {
+    using namespace b2s;
+    const u32 lane = threadIdx.x;
+    const bool in = lane < f.n, act = in && ((f.mask >> lane) & 1u);
+    const qm31 zero = {0u, 0u, 0u, 0u}, one = {1u, 0u, 0u, 0u};
+    constexpr u32 kHalf = 1u << 30;                                   // 1/2 in M31
+    // requested first: the channel words are needed last
+    u32 d[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) d[k] = gload1(f.chan, k);
+    u32 n_chal = gload1(f.chan, 8), n_sent = gload1(f.chan, 9);
+    qm31 claim = zero, corr = zero, f0 = zero, f2 = zero;
+    if (in) { claim = q_of(gload4(f.state, 8 * lane)); corr = q_of(gload4(f.state, 8 * lane + 4)); }
+    if (act) { f0 = q_of(gload4(f.sums, 8 * lane)); f2 = q_of(gload4(f.sums, 8 * lane + 4)); }
+
+    // wave-uniform: D = 1 - 2y, 1/y and 1/D from one inversion, b, A = a D
+    const qm31 y = f.y, one_y = qm31_sub(one, y), D = qm31_sub(one_y, y);
+    const qm31 inv_yd = qm31_inv(qm31_mul(y, D));
+    const qm31 inv_y = qm31_mul(inv_yd, D), inv_d = qm31_mul(inv_yd, y);
+    const qm31 b = qm31_mul(one_y, inv_d), A = qm31_mul(f.a, D);
+
+    // lane i: the coefficients of p_i
+    qm31 c0, c1 = zero, c2 = zero, c3 = zero;
+    if (act) {
+        const qm31 ca = qm31_mul(corr, A);
+        const qm31 g0 = qm31_mul(f0, ca), g2 = qm31_mul(f2, ca);
+        const qm31 w0 = qm31_neg(qm31_mul_m31(g0, kHalf)), w2 = qm31_neg(qm31_mul_m31(g2, kHalf));
+        const qm31 w1 = qm31_mul(qm31_sub(qm31_mul(claim, D), qm31_mul(g0, one_y)), inv_y);
+        const qm31 q2 = qm31_add(qm31_add(w0, w1), w2);
+        const qm31 w01 = qm31_add(w0, w1);                            // q1 = -(3 w0 + 2 w1 + w2) = -(w0 + (w0 + w1) + q2)
+        const qm31 q1 = qm31_neg(qm31_add(qm31_add(w0, w01), q2));
+        c0 = qm31_mul(b, g0);                                         // -b q0, q0 = 2 w0 = -g0
+        c1 = qm31_sub(qm31_neg(g0), qm31_mul(b, q1));
+        c2 = qm31_sub(q1, qm31_mul(b, q2));
+        c3 = q2;
+    } else {
+        c0 = qm31_mul_m31(claim, kHalf);                              // the constant claim / 2 (zero beyond the instances)
+    }
+
+    // rp = sum_i alpha^i p_i (sumcheck.ts combine): alpha^lane by square and multiply, then a sum over the wave
+    qm31 pw = one, sq = f.alpha;
+#pragma unroll 1
+    for (u32 k = 0; ((f.n - 1) >> k) != 0; k++) {
+        if ((lane >> k) & 1u) pw = qm31_mul(pw, sq);
+        sq = qm31_mul(sq, sq);
+    }
+    u32 rp[16];
+    {
+        const qm31 t0 = qm31_mul(c0, pw);
+        qm31 t1 = zero, t2 = zero, t3 = zero;
+        if (act) { t1 = qm31_mul(c1, pw); t2 = qm31_mul(c2, pw); t3 = qm31_mul(c3, pw); }
+        rp[0] = t0.a; rp[1] = t0.b; rp[2] = t0.c; rp[3] = t0.d; rp[4] = t1.a; rp[5] = t1.b; rp[6] = t1.c; rp[7] = t1.d;
+        rp[8] = t2.a; rp[9] = t2.b; rp[10] = t2.c; rp[11] = t2.d; rp[12] = t3.a; rp[13] = t3.b; rp[14] = t3.c; rp[15] = t3.d;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < 16; k++) rp[k] = m31_add(rp[k], (u32)__shfl_xor((int)rp[k], off, 64));
+#pragma unroll
+    for (int k = 0; k < 16; k++) rp[k] = (u32)__builtin_amdgcn_readfirstlane((int)rp[k]);
+    u32 n_coeffs = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        if (rp[4 * j] | rp[4 * j + 1] | rp[4 * j + 2] | rp[4 * j + 3]) n_coeffs = j + 1;
+
+    // mix_felts(rp.coeffs[:n_coeffs]) (channel/blake2.ts:113-118): Blake2s over digest || 16 n_coeffs bytes.  The words of the
+    // trimmed coefficients are zero, which is the padding of the last block.
+    {
+        u32 h[8] = {IV0 ^ 0x01010020u, IV1, IV2, IV3, IV4, IV5, IV6, IV7};
+        u32 m[16];
+#pragma unroll
+        for (int k = 0; k < 8; k++) { m[k] = d[k]; m[8 + k] = rp[k]; }
+        const u32 len = 32u + 16u * n_coeffs;
+        if (n_coeffs <= 2) {
+            b2s_compress(h, m, len, true);
+        } else {
+            b2s_compress(h, m, 64u, false);
+#pragma unroll
+            for (int k = 0; k < 8; k++) { m[k] = rp[8 + k]; m[8 + k] = 0u; }
+            b2s_compress(h, m, len, true);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) d[k] = h[k];
+        n_chal += 1;
+        n_sent = 0;
+    }
+    u32 felt[4] = {0u, 0u, 0u, 0u};
+    chan_mix_draw(d, n_chal, n_sent, nullptr, false, true, felt);
+    const qm31 ch = {felt[0], felt[1], felt[2], felt[3]};
+
+    // claim_i <- p_i(ch); corr_i <- corr_i eq(ch, y) for the active instances
+    if (in) {
+        qm31 v = c0;
+        if (act) {
+            v = qm31_add(qm31_mul(qm31_add(qm31_mul(qm31_add(qm31_mul(c3, ch), c2), ch), c1), ch), c0);
+            const qm31 e = qm31_add(qm31_mul(ch, y), qm31_mul(qm31_sub(one, ch), one_y));
+            gstore4(f.state, 8 * lane + 4, u4_of(qm31_mul(corr, e)));
+        }
+        gstore4(f.state, 8 * lane, u4_of(v));
+    }
+    if (lane == 0) {
+        gstore4(f.poly_out, 0, make_uint4(n_coeffs, 0u, 0u, 0u));
+#pragma unroll
+        for (int j = 0; j < 4; j++) gstore4(f.poly_out, 4 + 4 * j, make_uint4(rp[4 * j], rp[4 * j + 1], rp[4 * j + 2], rp[4 * j + 3]));
+        gstore4(f.ch_out, 0, u4_of(ch));
+#pragma unroll
+        for (int k = 0; k < 8; k++) gstore1(f.chan, k, d[k]);
+        gstore1(f.chan, 8, n_chal);
+        gstore1(f.chan, 9, n_sent);
+    }
+}
+
+bool q_is(const u32 v[4], u32 a) { return v[0] == a && v[1] == 0 && v[2] == 0 && v[3] == 0; }
+
 }  // namespace
 
 extern "C" {
+
+int tstwo_gkr_round_finish(u32 *chan, const u32 *sums, u32 *state, u32 n_instances, uint64_t active_mask, const u32 y_k[4],
+                           const u32 inv_eq0[4], const u32 alpha[4], u32 *round_poly_out, u32 *challenge_out) {
+    TSTWO_REQUIRE_READY();
+    TSTWO_REQUIRE_PTRS(chan, sums, state, round_poly_out, challenge_out);
+    if (!y_k || !inv_eq0 || !alpha) return set_error(TSTWO_ERR_BAD_ARG, "null host argument");
+    if (n_instances == 0 || n_instances > 64) return set_error(TSTWO_ERR_BAD_ARG, "sum-check: 1 to 64 instances per round");
+    if (((uintptr_t)chan & 3) || !aligned16(sums) || !aligned16(state) || !aligned16(round_poly_out) || !aligned16(challenge_out))
+        return set_error(TSTWO_ERR_BAD_ARG, "sum-check: misaligned device pointer");
+    // y_k = 1/2: b is undefined; y_k = 1, 0, 1/3: b = 0, 1, 2 collides with an interpolation point
+    if (q_is(y_k, 0u) || q_is(y_k, 1u) || q_is(y_k, 1u << 30) || q_is(y_k, 0x55555555u))
+        return set_error(TSTWO_ERR_BAD_ARG, "sum-check: degenerate eq point");
+    FinishArgs f{};
+    f.chan = chan; f.sums = sums; f.state = state; f.n = n_instances;
+    f.mask = n_instances == 64 ? active_mask : active_mask & ((1ull << n_instances) - 1);
+    f.y = qarg(y_k); f.a = qarg(inv_eq0); f.alpha = qarg(alpha);
+    f.poly_out = round_poly_out; f.ch_out = challenge_out;
+    hipLaunchKernelGGL(k_gkr_round_finish, dim3(1), dim3(64), 0, ctx().stream, f);
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
+}
+
 
 int tstwo_gkr_gen_eq_evals(const u32 *y, u32 n_y, const u32 v[4], u32 *const out[4]) {
     TSTWO_REQUIRE_READY();
@@ -397,7 +601,7 @@ int tstwo_gkr_sum_poly(u32 kind, const u32 *const eq[4], const u32 *const num[4]
         if (int rc = ensure_scratch(kTabOff)) return rc;
         dst = (u32 *)((uint8_t *)ctx().scratch + kResultOff);
     }
-    if (int rc = gkr_sum(kind, eq, num, den, nullptr, nullptr, n_vars, nullptr, lambda, dst, false)) return rc;
+    if (int rc = gkr_sum(kind, eq, num, den, nullptr, nullptr, n_vars, nullptr, nullptr, lambda, dst, false)) return rc;
     if (page) {
         const void *view = nullptr;
         if (int rc = result_wait(&view)) return rc;
@@ -411,47 +615,43 @@ int tstwo_gkr_sum_poly_async(u32 kind, const u32 *const eq[4], const u32 *const 
                              const u32 lambda[4], u32 *out_dev) {
     TSTWO_REQUIRE_READY();
     TSTWO_REQUIRE_PTRS(out_dev);
-    return gkr_sum(kind, eq, num, den, nullptr, nullptr, n_vars, nullptr, lambda, out_dev, false);
+    return gkr_sum(kind, eq, num, den, nullptr, nullptr, n_vars, nullptr, nullptr, lambda, out_dev, false);
 }
 
 int tstwo_gkr_round(u32 kind, const u32 *const eq[4], const u32 *const num[4], const u32 *const den[4], u32 *const out_num[4],
                     u32 *const out_den[4], u32 n_vars, const u32 r[4], const u32 lambda[4], u32 *out_dev) {
     TSTWO_REQUIRE_READY();
     TSTWO_REQUIRE_PTRS(out_dev);
-    return gkr_sum(kind, eq, num, den, out_num, out_den, n_vars, r, lambda, out_dev, true);
+    return gkr_sum(kind, eq, num, den, out_num, out_den, n_vars, r, nullptr, lambda, out_dev, true);
 }
 
 int tstwo_mle_fix_first_variable_base(const u32 *in, u32 log_n, const u32 r[4], u32 *const out[4]) {
     TSTWO_REQUIRE_READY();
-    if (log_n == 0) return TSTWO_OK;                 // a constant: midpoint 0, nothing to write (mle.ts:68-80)
-    if (log_n > kMaxLog) return set_error(TSTWO_ERR_BAD_ARG, "MLE too large");
-    if (!r) return set_error(TSTWO_ERR_BAD_ARG, "null assignment");
-    TSTWO_REQUIRE_PTRS(in); TSTWO_REQUIRE_TABLE(out, 4);
-    const u32 half = 1u << (log_n - 1);
-    const Soa4 o = soa(out);
-    if (half % 4 == 0 && aligned16(in) && all_aligned16(o))
-        hipLaunchKernelGGL((k_fold<true, 4>), dim3(grid_for(half / 4, 32)), dim3(kThreads), 0, ctx().stream, csoa1(in), qarg(r), o, half);
-    else
-        hipLaunchKernelGGL((k_fold<true, 1>), dim3(grid_for(half, 32)), dim3(kThreads), 0, ctx().stream, csoa1(in), qarg(r), o, half);
-    TSTWO_LAUNCH_CHECK();
-    return TSTWO_OK;
+    const u32 *const in4[4] = {in, in, in, in};
+    return mle_fold(true, in4, log_n, r, nullptr, out);
 }
 
 int tstwo_mle_fix_first_variable_secure(const u32 *const in[4], u32 log_n, const u32 r[4], u32 *const out[4]) {
     TSTWO_REQUIRE_READY();
-    if (log_n == 0) return TSTWO_OK;
-    if (log_n > kMaxLog) return set_error(TSTWO_ERR_BAD_ARG, "MLE too large");
-    if (!r) return set_error(TSTWO_ERR_BAD_ARG, "null assignment");
-    TSTWO_REQUIRE_TABLE(in, 4); TSTWO_REQUIRE_TABLE(out, 4);
-    const u32 half = 1u << (log_n - 1);
-    const CSoa4 i4 = csoa(in);
-    const Soa4 o = soa(out);
-    if (half % 4 == 0 && all_aligned16(i4) && all_aligned16(o))
-        hipLaunchKernelGGL((k_fold<false, 4>), dim3(grid_for(half / 4, 32)), dim3(kThreads), 0, ctx().stream, i4, qarg(r), o, half);
-    else
-        hipLaunchKernelGGL((k_fold<false, 1>), dim3(grid_for(half, 32)), dim3(kThreads), 0, ctx().stream, i4, qarg(r), o, half);
-    TSTWO_LAUNCH_CHECK();
-    return TSTWO_OK;
+    return mle_fold(false, in, log_n, r, nullptr, out);
+}
+
+int tstwo_gkr_round_dev(u32 kind, const u32 *const eq[4], const u32 *const num[4], const u32 *const den[4], u32 *const out_num[4],
+                        u32 *const out_den[4], u32 n_vars, const u32 *r_dev, const u32 lambda[4], u32 *out_dev) {
+    TSTWO_REQUIRE_READY();
+    TSTWO_REQUIRE_PTRS(out_dev, r_dev);
+    return gkr_sum(kind, eq, num, den, out_num, out_den, n_vars, nullptr, r_dev, lambda, out_dev, true);
+}
+
+int tstwo_mle_fix_first_variable_base_dev(const u32 *in, u32 log_n, const u32 *r_dev, u32 *const out[4]) {
+    TSTWO_REQUIRE_READY();
+    const u32 *const in4[4] = {in, in, in, in};
+    return mle_fold(true, in4, log_n, nullptr, r_dev, out);
+}
+
+int tstwo_mle_fix_first_variable_secure_dev(const u32 *const in[4], u32 log_n, const u32 *r_dev, u32 *const out[4]) {
+    TSTWO_REQUIRE_READY();
+    return mle_fold(false, in, log_n, nullptr, r_dev, out);
 }
 
 }  // extern "C"

@@ -3,11 +3,15 @@ GkrMultivariatePolyOracle (lookups/gkr_prover.ts) and prove_batch (gkr_prover.ts
 
 MLEs live in HBM: an Mle<SecureField> is a SecureColumnByCoords (4 SoA columns), an Mle<BaseField> one HipColumn; the first
 variable is the most significant bit of the index.  Every pass over 2^n values is a kernel of csrc/gkr.hip; the host keeps the
-O(rounds) protocol (sumcheck.py) and the channel.
+O(layers) protocol (sumcheck.py) and the channel between the layers.
 
-prove_batch reads back at most one small buffer per sum-check round (the (f(0), f(2)) slots of every active instance, written
-by one fused fold + sum launch each) and one per layer (the 2-point masks); the first read-back also takes every instance's
-output values and first mask.
+prove_batch enqueues a whole layer without reading anything back where it can (a Blake2s channel with the Rust draw semantics, at
+most 64 instances): per round one fused fold + sum launch per active instance, then one tstwo_gkr_round_finish launch that does
+what the host would do between two rounds (round polynomials, their combination, the channel, the new claims and corrections) and
+leaves the challenge in device memory for the next round's fold; per layer one upload and one read-back (channel, round
+polynomials, assignment, masks).  Elsewhere, and with device_rounds=False, the protocol of a round runs on the host: one read-back
+per round (the (f(0), f(2)) slots of every active instance) and one per layer (the 2-point masks).  The first read-back also takes
+every instance's output values and first mask.
 """
 from __future__ import annotations
 
@@ -305,9 +309,15 @@ class HipMleOps:
         return out
 
     @staticmethod
-    def fix_first_variable_into(mle: Mle, assignment: QM31, out: Mle) -> None:
-        """The same into `out` (may be `mle` itself for a secure MLE: in place, the first half of its columns)."""
-        if mle.is_base:
+    def fix_first_variable_into(mle: Mle, assignment, out: Mle) -> None:
+        """The same into `out` (may be `mle` itself for a secure MLE: in place, the first half of its columns).  `assignment`: a
+        QM31, or the device address (int) of 4 words written earlier on the stream."""
+        if isinstance(assignment, int):
+            if mle.is_base:
+                L.call("tstwo_mle_fix_first_variable_base_dev", C.c_void_p(mle.col.ptr), mle.n_variables(), C.c_void_p(assignment), out.ptrs())
+            else:
+                L.call("tstwo_mle_fix_first_variable_secure_dev", mle.ptrs(), mle.n_variables(), C.c_void_p(assignment), out.ptrs())
+        elif mle.is_base:
             L.call("tstwo_mle_fix_first_variable_base", C.c_void_p(mle.col.ptr), mle.n_variables(), _q(assignment), out.ptrs())
         else:
             L.call("tstwo_mle_fix_first_variable_secure", mle.ptrs(), mle.n_variables(), _q(assignment), out.ptrs())
@@ -375,7 +385,7 @@ class _Instance:
     def __init__(self, idx: int, layer: Layer, owned: bool, lam: QM31, slot: int):
         self.idx, self.layer, self.owned, self.lam, self.slot = idx, layer, owned, lam, slot
         self.correction = QM31.one()
-        self.pending = None              # challenge not yet applied to the device layer
+        self.pending = None              # challenge not yet applied to the device layer: a QM31, or the device address of its 4 words
 
     def n_vars(self) -> int:             # the oracle's variables still to fix
         return self.layer.n_variables() - 1 - (1 if self.pending is not None else 0)
@@ -410,8 +420,12 @@ class _Instance:
             return
         k = self.n_vars()
         num, den = self._fold_target()
-        L.call("tstwo_gkr_round", lay.kind, eq_evals.evals.ptrs(), num_p, lay.den.ptrs(), num.ptrs() if num else _null4(), den.ptrs(),
-               k, _q(self.pending), _q(self.lam), out_ptr)
+        if isinstance(self.pending, int):
+            L.call("tstwo_gkr_round_dev", lay.kind, eq_evals.evals.ptrs(), num_p, lay.den.ptrs(), num.ptrs() if num else _null4(),
+                   den.ptrs(), k, C.c_void_p(self.pending), _q(self.lam), out_ptr)
+        else:
+            L.call("tstwo_gkr_round", lay.kind, eq_evals.evals.ptrs(), num_p, lay.den.ptrs(), num.ptrs() if num else _null4(), den.ptrs(),
+                   k, _q(self.pending), _q(self.lam), out_ptr)
         self._replace(num, den)
         self.pending = None
 
@@ -447,13 +461,153 @@ def _gen_layers(layer: Layer):
     return out
 
 
-def prove_batch(channel, input_layer_by_instance):
+def _host_rounds(channel, insts, claims, eq_evals, alpha: QM31, n_rounds: int, slots):
+    """The layer's batched sum-check (sumcheck.ts proveBatch) with the protocol on the host: one read-back per round (the sums of
+    the active instances).  Returns (round polynomials, assignment); `claims` is updated in place."""
+    half = QM31.from_u32_unchecked(2, 0, 0, 0).inverse()
+    round_polys, assignment = [], []
+    for rnd in range(n_rounds):
+        rem = n_rounds - rnd
+        active = [sc for _, sc, _ in insts if sc is not None and sc.n_vars() == rem]
+        for sc in active:
+            sc.launch_round(eq_evals, slots)
+        words = L.download_many([(slots.ptr, 8 * len(insts))])[0] if active else None
+        polys = []
+        for i, sc, _ in insts:
+            if sc is not None and sc in active:
+                f = words[8 * sc.slot:8 * sc.slot + 8]
+                f0, f2 = _qs(f[:4]).mul(sc.correction), _qs(f[4:]).mul(sc.correction)
+                polys.append(correct_sum_as_poly_in_first_variable(f0, f2, claims[i], eq_evals.y, rem))
+            else:
+                polys.append(UnivariatePoly.from_(claims[i].mul(half)))
+        rp = combine(polys, alpha)
+        channel.mix_felts(rp.coeffs)
+        ch = channel.draw_felt()
+        for (i, _, _), p in zip(insts, polys):
+            claims[i] = p.eval_at_point(ch)
+        for sc in active:
+            sc.fix(ch, eq_evals.y)
+        round_polys.append(rp)
+        assignment.append(ch)
+    return round_polys, assignment
+
+
+MAX_DEVICE_INSTANCES = 64           # one lane of tstwo_gkr_round_finish's wave per instance
+_HALF, _THIRD = (1 << 30, 0, 0, 0), (0x55555555, 0, 0, 0)
+DEGENERATE_EQ_POINTS = (_Z, (1, 0, 0, 0), _HALF, _THIRD)      # y_k at which correct_sum_as_poly_in_first_variable divides by zero
+
+
+def inv_eq0_table(y):
+    """a of correct_sum_as_poly_in_first_variable for every round of a layer: entry r = 1 / eq({0}^(r+1), y[:r+1]), from prefix
+    products and ONE inversion (Montgomery's trick).  4-tuples in, 4-tuples out; a zero eq raises like the inversion it replaces."""
+    one = (1, 0, 0, 0)
+    pre, acc = [], one                   # pre[r] = prod_{j <= r} (1 - y_j)
+    for yj in y:
+        acc = _qmul(acc, _qsub(one, yj))
+        pre.append(acc)
+    prods, acc = [], one                 # prods[r] = pre[0] ... pre[r]
+    for e in pre:
+        if e == _Z:
+            raise ZeroDivisionError("0 has no inverse")
+        acc = _qmul(acc, e)
+        prods.append(acc)
+    inv = _qinv(acc) if pre else one
+    out = [None] * len(pre)
+    for r in range(len(pre) - 1, -1, -1):
+        out[r] = _qmul(inv, prods[r - 1]) if r else inv
+        inv = _qmul(inv, pre[r])
+    return out
+
+
+def round_finish(chan_ptr: int, sums_ptr: int, state_ptr: int, n_instances: int, active_mask: int, y_k, inv_eq0, alpha,
+                 round_poly_ptr: int, challenge_ptr: int) -> None:
+    """tstwo_gkr_round_finish: the end of one sum-check round on the device (asynchronous).  Scalars are 4-tuples.  Raises the host
+    path's ZeroDivisionError for an eq point at which it divides by zero, before anything is launched."""
+    if tuple(y_k) in DEGENERATE_EQ_POINTS:
+        raise ZeroDivisionError("0 has no inverse")
+    v = C.c_void_p
+    L.call("tstwo_gkr_round_finish", v(chan_ptr), v(sums_ptr), v(state_ptr), n_instances, C.c_uint64(active_mask), L.u32x(y_k),
+           L.u32x(inv_eq0), L.u32x(alpha), v(round_poly_ptr), v(challenge_ptr))
+
+
+class _DeviceRounds:
+    """The buffers of prove_batch's device path, allocated once: one block holding the channel (16 words), every instance's
+    (claim, correction) (8 words each), the round polynomials (20 words a round) and the assignment (4 words a round), so that a
+    layer costs one upload (channel + claims) and one read-back (the whole block + the masks)."""
+
+    def __init__(self, channel, n_inst: int, max_rounds: int):
+        from .channel import DeviceChannel
+        self.n_inst, self.max_rounds = n_inst, max_rounds
+        self.state_off, self.poly_off = 16, 16 + 8 * n_inst
+        self.assign_off = self.poly_off + 20 * max_rounds
+        self.words = self.assign_off + 4 * max_rounds
+        self.buf = L.DeviceBuffer(4 * self.words)
+        self.chan = DeviceChannel(channel, self.buf)
+
+    def ptr(self, word: int) -> int:
+        return self.buf.ptr + 4 * word
+
+    def free(self) -> None:
+        self.buf.free()
+
+    def run_layer(self, channel, insts, claims, n_v_of, eq_evals: EqEvals, alpha: QM31, n_rounds: int, slots):
+        """Enqueues the layer's rounds and the last fold.  Returns the pieces to read back (the block first)."""
+        y = [v.tup() for v in eq_evals.y]
+        inv_eq0 = inv_eq0_table(y)
+        if any(v in DEGENERATE_EQ_POINTS for v in y):
+            raise ZeroDivisionError("0 has no inverse")
+        state = np.zeros(8 * len(insts), dtype=np.uint32)
+        for j, (i, _, _) in enumerate(insts):
+            state[8 * j:8 * j + 4] = claims[i].tup()
+            state[8 * j + 4] = 1
+        self.chan.load(channel, tail=state)
+        alpha_t = alpha.tup()
+        for rnd in range(n_rounds):
+            rem = n_rounds - rnd
+            mask = 0
+            for j, (i, sc, _) in enumerate(insts):
+                if sc is None or n_v_of[i] < rem:
+                    continue
+                mask |= 1 << j
+                sc.launch_round(eq_evals, slots)
+                sc.pending = self.ptr(self.assign_off + 4 * rnd)        # the challenge this round is about to draw
+            round_finish(self.ptr(0), slots.ptr, self.ptr(self.state_off), len(insts), mask, y[rnd], inv_eq0[rnd], alpha_t,
+                         self.ptr(self.poly_off + 20 * rnd), self.ptr(self.assign_off + 4 * rnd))
+        return [(self.buf.ptr, self.words)]
+
+    def unpack(self, words, n_rounds: int):
+        """The block as read back: continues the host channel from the device state; returns (round polynomials, assignment)."""
+        self.chan.sync_to_host(words[:10])
+        round_polys, assignment = [], []
+        for rnd in range(n_rounds):
+            p = words[self.poly_off + 20 * rnd:self.poly_off + 20 * rnd + 20]
+            round_polys.append(UnivariatePoly([_qs(p[4 + 4 * k:8 + 4 * k]) for k in range(int(p[0]))]))
+            assignment.append(_qs(words[self.assign_off + 4 * rnd:self.assign_off + 4 * rnd + 4]))
+        return round_polys, assignment
+
+
+def device_rounds_supported(channel, n_instances: int) -> bool:
+    """Whether prove_batch can run its sum-check rounds on the device: a Blake2s channel with the Rust draw semantics and at most
+    64 instances."""
+    from .channel import Blake2sChannel
+    return isinstance(channel, Blake2sChannel) and not channel.ts_compat and n_instances <= MAX_DEVICE_INSTANCES
+
+
+def prove_batch(channel, input_layer_by_instance, device_rounds=None):
     """Batch-proves the instances' circuits (gkr_prover.ts proveBatch).  The input layers are left untouched; every layer the
-    prover generates is freed once consumed.  Returns (GkrBatchProof, GkrArtifact)."""
+    prover generates is freed once consumed.  Returns (GkrBatchProof, GkrArtifact).
+
+    device_rounds: True = the sum-check rounds run on the device (tstwo_gkr_round_finish: nothing is read back inside a layer;
+    ValueError where that path cannot be taken); False = the host loop, one read-back per round; None = the device path where it
+    can be taken (device_rounds_supported), else the host loop.  Both give the same proof, artifact and channel state."""
     layers_in = list(input_layer_by_instance)
     n_inst = len(layers_in)
     if n_inst == 0:
         raise ValueError("no instances")
+    if device_rounds is None:
+        device_rounds = device_rounds_supported(channel, n_inst)
+    elif device_rounds and not device_rounds_supported(channel, n_inst):
+        raise ValueError("device_rounds needs a Blake2sChannel with the Rust draw semantics and at most 64 instances")
     n_layers_by = [lay.n_variables() for lay in layers_in]
     n_layers = max(n_layers_by)
     if min(n_layers_by) == 0:
@@ -480,12 +634,12 @@ def prove_batch(channel, input_layer_by_instance):
         del st[:2]
 
     slots = L.DeviceBuffer(32 * n_inst)
+    dev = None                                # the device path's buffers, allocated at the first layer with rounds
     output_claims = [None] * n_inst
     masks = [[] for _ in range(n_inst)]
     sumcheck_proofs = []
     ood = []
     claims_to_verify = [None] * n_inst
-    half = QM31.from_u32_unchecked(2, 0, 0, 0).inverse()
     for layer in range(n_layers):
         rem_layers = n_layers - layer
         for i in range(n_inst):
@@ -511,51 +665,39 @@ def prove_batch(channel, input_layer_by_instance):
             insts.append((i, sc, random_linear_combination(c, lam)))
         # batched sum-check (sumcheck.ts proveBatch) over the layer's oracles
         n_rounds = layer
-        claims = {}
+        claims, n_v_of = {}, {}
         for i, sc, claim in insts:
-            n_v = layer - (n_layers - n_layers_by[i])
-            claims[i] = claim.mulM31(M31(1 << (n_rounds - n_v)))
-        round_polys, assignment = [], []
-        for rnd in range(n_rounds):
-            rem = n_rounds - rnd
-            active = [sc for _, sc, _ in insts if sc is not None and sc.n_vars() == rem]
-            for sc in active:
-                sc.launch_round(eq_evals, slots)
-            words = L.download_many([(slots.ptr, 8 * len(insts))])[0] if active else None
-            polys = []
-            for i, sc, _ in insts:
-                if sc is not None and sc in active:
-                    f = words[8 * sc.slot:8 * sc.slot + 8]
-                    f0, f2 = _qs(f[:4]).mul(sc.correction), _qs(f[4:]).mul(sc.correction)
-                    polys.append(correct_sum_as_poly_in_first_variable(f0, f2, claims[i], eq_evals.y, rem))
-                else:
-                    polys.append(UnivariatePoly.from_(claims[i].mul(half)))
-            rp = combine(polys, alpha)
-            channel.mix_felts(rp.coeffs)
-            ch = channel.draw_felt()
-            for (i, _, _), p in zip(insts, polys):
-                claims[i] = p.eval_at_point(ch)
-            for sc in active:
-                sc.fix(ch, eq_evals.y)
-            round_polys.append(rp)
-            assignment.append(ch)
-        sumcheck_proofs.append(SumcheckProof(round_polys))
-        # masks of the reduced layers: one read-back for all of them
+            n_v_of[i] = layer - (n_layers - n_layers_by[i])
+            claims[i] = claim.mulM31(M31(1 << (n_rounds - n_v_of[i])))
         reduced = [sc for _, sc, _ in insts if sc is not None]
-        for sc in reduced:
-            sc.apply_pending()
-        if reduced:
-            pieces = []
+        if device_rounds and n_rounds:
+            # every round enqueued without a read-back; the layer's one read-back brings the channel, the round polynomials, the
+            # assignment and the masks
+            if dev is None:
+                dev = _DeviceRounds(channel, n_inst, n_layers - 1)
+            pieces = dev.run_layer(channel, insts, claims, n_v_of, eq_evals, alpha, n_rounds, slots)
             for sc in reduced:
+                sc.apply_pending()
                 pieces += _read_pairs(sc.layer, 2)
             words = L.download_many(pieces)
-            k = 0
+            round_polys, assignment = dev.unpack(words[0], n_rounds)
+            words = words[1:]
+        else:
+            round_polys, assignment = _host_rounds(channel, insts, claims, eq_evals, alpha, n_rounds, slots)
+            # masks of the reduced layers: one read-back for all of them
+            pieces = []
             for sc in reduced:
-                n_p = len(_read_pairs(sc.layer, 2))
-                new_masks[sc.idx] = _mask_of(sc.layer, [tuple(c) for c in _unpack(sc.layer, words[k:k + n_p], 2)])
-                k += n_p
-                if sc.owned:
-                    sc.layer.free()
+                sc.apply_pending()
+                pieces += _read_pairs(sc.layer, 2)
+            words = L.download_many(pieces) if pieces else []
+        sumcheck_proofs.append(SumcheckProof(round_polys))
+        k = 0
+        for sc in reduced:
+            n_p = len(_read_pairs(sc.layer, 2))
+            new_masks[sc.idx] = _mask_of(sc.layer, [tuple(c) for c in _unpack(sc.layer, words[k:k + n_p], 2)])
+            k += n_p
+            if sc.owned:
+                sc.layer.free()
         if eq_evals is not None:
             eq_evals.free()
         for i, _, _ in insts:
@@ -566,10 +708,12 @@ def prove_batch(channel, input_layer_by_instance):
         for i, _, _ in insts:
             claims_to_verify[i] = new_masks[i].reduce_at_point(ch)
     slots.free()
+    if dev is not None:
+        dev.free()
     proof = GkrBatchProof(sumcheck_proofs, masks, output_claims)
     return proof, GkrArtifact(ood, claims_to_verify, n_layers_by)
 
 
 __all__ = ["GRAND_PRODUCT", "LOGUP_GENERIC", "LOGUP_MULTIPLICITIES", "LOGUP_SINGLES", "EqEvals", "GkrArtifact", "GkrBatchProof",
            "GkrMask", "GkrMultivariatePolyOracle", "HipGkrOps", "HipMleOps", "Layer", "Mle", "correct_sum_as_poly_in_first_variable",
-           "fold_mle_evals", "prove_batch"]
+           "device_rounds_supported", "fold_mle_evals", "inv_eq0_table", "prove_batch", "round_finish"]
