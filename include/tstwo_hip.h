@@ -490,6 +490,25 @@ int tstwo_gkr_round_dev(uint32_t kind, const uint32_t *const eq[4], const uint32
                         const uint32_t lambda[4], uint32_t *out_dev);
 int tstwo_mle_fix_first_variable_base_dev(const uint32_t *in, uint32_t log_n, const uint32_t *r_dev, uint32_t *const out[4]);
 int tstwo_mle_fix_first_variable_secure_dev(const uint32_t *const in[4], uint32_t log_n, const uint32_t *r_dev, uint32_t *const out[4]);
+/* Mle.evalAtPoint (lookups/mle.ts:81-114) of n_mles base MLEs of 2^log_n values at one point:
+ * out[4k .. 4k+4) = sum_i mles[k][i] prod_j (bit_{n-1-j}(i) ? p_j : 1 - p_j), p_j = point[4j .. 4j+4) (host, 4 log_n words);
+ * log_n = 0 gives mles[k][0] (mle.ts:83-88).  One pass over the input (4 bytes per value) and one read-back for the whole batch;
+ * synchronous, `out` is host memory (4 n_mles words).  Columns may have any 4-byte alignment; one column may be named twice.
+ * Refused with TSTWO_ERR_BAD_ARG before anything is enqueued ("mle eval_at_point: ..."): n_mles = 0 ("no MLE given") or above
+ * 32768, log_n > 28 ("more than 28 variables"), a null pointer, a point word >= 2^31 - 1 ("point word out of range"), a call
+ * during graph capture. */
+int tstwo_mle_eval_at_point_base(const uint32_t *const *mles, size_t n_mles, uint32_t log_n, const uint32_t *point, uint32_t *out);
+/* Mle.evalAtPoint (lookups/mle.ts:81-114) of n_mles secure MLEs: cols = 4 n_mles device pointers, MLE k = cols[4k .. 4k+4)
+ * (SecureColumnByCoords); 16 bytes per value.  Everything else as the base form. */
+int tstwo_mle_eval_at_point_secure(const uint32_t *const *cols, size_t n_mles, uint32_t log_n, const uint32_t *point, uint32_t *out);
+/* The denominators of a LogUp-GKR input layer (gkr_prover.ts Layer, LogUp kinds) from trace columns; the reference does not
+ * define this step, it follows Rust stwo's LookupElements::combine over whole columns:
+ * out[r] = sum_t coeffs[4t .. 4t+4) * cols[t][r] + constant for r < 2^log_n,
+ * the denominator of a tstwo_logup_frac written out as a secure MLE.  Elementwise: the row order of the inputs is the order of
+ * the MLE.  1 <= n_terms <= TSTWO_LOGUP_MAX_TERMS ("1 to 16 terms"), log_n <= 28, host words < 2^31 - 1 ("... out of range"), an
+ * output column that overlaps an input is refused ("an output column is also an input").  Asynchronous. */
+int tstwo_gkr_logup_denominators(const uint32_t *const *cols, const uint32_t *coeffs, size_t n_terms, const uint32_t constant[4],
+                                 uint32_t log_n, uint32_t *const out[4]);
 /* The end of one round of the batched sum-check of prove_batch (sumcheck.ts:99-227 with the oracles of gkr_prover.ts:290-420), in
  * one single-wave launch and without a read-back: everything the host does between the sums of a round and the launches of the
  * next.  Asynchronous.

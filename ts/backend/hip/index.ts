@@ -153,6 +153,34 @@ export class HipBackend implements Backend {
     else check(hip.tstwo_mle_fix_first_variable_secure(ptr(mle.ptrs()), logN, ptr(q4(assignment)), ptr(out.ptrs())));
     return out;
   }
+  /** Mle.evalAtPoint (lookups/mle.ts:81-114) of MLEs of one kind and size at one point: one pass over the values, one read-back
+   *  for the batch.  point.length must be log2 of the MLEs' length. */
+  evalAtPoint(mles: readonly (HipSecureColumn | HipColumn)[], point: readonly QM31[]): QM31[] {
+    if (mles.length === 0) return [];
+    const logN = Math.log2(mles[0]!.len());
+    if (point.length !== logN) throw new Error(`a point of ${point.length} coordinates for an MLE of ${logN} variables`);
+    const words = new Uint32Array(Math.max(4 * logN, 4));
+    point.forEach((p, k) => words.set(q4(p), 4 * k));
+    const out = new Uint32Array(4 * mles.length);
+    if (mles[0] instanceof HipColumn) {
+      check(hip.tstwo_mle_eval_at_point_base(ptr(ptrs(mles.map((m) => (m as HipColumn).dev))), BigInt(mles.length), logN, ptr(words), ptr(out)));
+    } else {
+      const cols = new BigUint64Array(4 * mles.length);
+      mles.forEach((m, k) => cols.set((m as HipSecureColumn).ptrs(), 4 * k));
+      check(hip.tstwo_mle_eval_at_point_secure(ptr(cols), BigInt(mles.length), logN, ptr(words), ptr(out)));
+    }
+    return mles.map((_, k) => QM31.from_u32_unchecked(out[4 * k]!, out[4 * k + 1]!, out[4 * k + 2]!, out[4 * k + 3]!));
+  }
+  /** The denominators of a LogUp-GKR input layer from trace columns: out[r] = sum_t coeffs[t] * cols[t][r] + constant
+   *  (LookupElements.combine over whole columns), as a secure MLE in the row order of the columns.  Asynchronous. */
+  logupDenominators(cols: readonly HipColumn[], coeffs: readonly QM31[], constant: QM31): HipSecureColumn {
+    const out = HipSecureColumn.uninitialized(cols[0]!.len());
+    const words = new Uint32Array(4 * coeffs.length);
+    coeffs.forEach((c, t) => words.set(q4(c), 4 * t));
+    check(hip.tstwo_gkr_logup_denominators(ptr(ptrs(cols.map((c) => c.dev))), ptr(words), BigInt(cols.length), ptr(q4(constant)),
+      Math.log2(cols[0]!.len()), ptr(out.ptrs())));
+    return out;
+  }
   // AIR (constraint_framework/index.ts, examples/fibonacci.ts; the prover around them: tstwo_amd/air.py and tstwo_amd/prover.py)
   /** generateTrace of wide Fibonacci on the device: x_0 = a, x_1 = b, x_k = x_{k-2}^2 + x_{k-1}^2, nColumns columns of a.len(). */
   generateWideFibTrace(a: HipColumn, b: HipColumn, nColumns: number): HipColumn[] {

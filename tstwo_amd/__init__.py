@@ -14,8 +14,10 @@ from .fri_prover import (FriCommitPlan, FriConfig, FriLayerProof, FriProof, FriP
                          compute_decommitment_positions_and_witness_evals)
 from .fri_verifier import (CirclePolyDegreeBound, FriVerificationError, FriVerifier, LinePolyDegreeBound,  # noqa: F401
                            SparseEvaluation, accumulate_line, compute_decommitment_positions_and_rebuild_evals)
-from .gkr import (EqEvals, GkrMultivariatePolyOracle, HipGkrOps, HipMleOps, Layer, Mle,  # noqa: F401
+from .gkr import (EqEvals, GkrInputClaimMismatch, GkrMultivariatePolyOracle, HipGkrOps, HipMleOps, Layer, Mle,  # noqa: F401
+                  check_logup_sum, eval_mles_at_point, logup_denominators, logup_input_layer, verify_input_claims,
                   prove_batch as gkr_prove_batch)
+from .gkr_lookup import gkr_range_check_layers, gkr_range_check_prove, gkr_range_check_verify  # noqa: F401
 from .gkr_verifier import (Gate, GkrArtifact, GkrBatchProof, GkrError, GkrErrorType, GkrMask,  # noqa: F401
                            partially_verify_batch)
 from .sumcheck import SumcheckError, SumcheckProof, UnivariatePoly  # noqa: F401

@@ -165,6 +165,9 @@ _SIGS = {
     "tstwo_mle_fix_first_variable_base_dev": [vp, C.c_uint32, vp, P4],
     "tstwo_mle_fix_first_variable_secure_dev": [P4, C.c_uint32, vp, P4],
     "tstwo_gkr_round_finish": [vp, vp, vp, C.c_uint32, C.c_uint64, u32p, u32p, u32p, vp, vp],
+    "tstwo_mle_eval_at_point_base": [C.POINTER(vp), C.c_size_t, C.c_uint32, u32p, u32p],
+    "tstwo_mle_eval_at_point_secure": [C.POINTER(vp), C.c_size_t, C.c_uint32, u32p, u32p],
+    "tstwo_gkr_logup_denominators": [C.POINTER(vp), u32p, C.c_size_t, u32p, C.c_uint32, P4],
     "tstwo_poseidon252_hash_many": [vp, C.c_size_t, C.c_uint32, vp],
     "tstwo_poseidon252_merkle_commit_layer": [C.c_uint32, vp, C.POINTER(vp), C.c_size_t, vp],
     "tstwo_poseidon252_merkle_commit": [C.POINTER(vp), u32p, C.c_size_t, vp, u8p],

@@ -173,8 +173,57 @@ __global__ void __launch_bounds__(kThreads) k_logup_column(ColArgs a) {
     }
 }
 
+// ---------------------------------------------------------------- denominators of a LogUp-GKR input layer
+// tstwo_gkr_logup_denominators: out[r] = sum_t coeff_t cols_t[r] + constant, the linear form above written out as a secure MLE
+// instead of being inverted.  W rows per lane as in k_logup_column; the column pointers and the coefficients are kernel arguments
+// read at a wave-uniform index (scalar loads).  64-bit sums of canonical M31 x M31 products, folded after every fourth term: a
+// folded sum is below 2^33 and four more products add less than 4 (P - 1)^2, so 16 terms of (P - 1) (P - 1) stay below 2^64.
+struct DenCoef { qm31 c[kMaxTerms]; };
+
+template <int W>
+__global__ void __launch_bounds__(kThreads) k_gkr_logup_den(ColPtrs cols, DenCoef coef, qm31 constant, u32 n_terms, Soa4 out, u32 n_rows) {
+    const u32 t = blockIdx.x * kThreads + threadIdx.x;
+    if (t >= n_rows / W) return;
+    const u32 row = t * W;
+    u64 acc[W][4];
+#pragma unroll
+    for (int e = 0; e < W; e++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc[e][j] = 0;
+#pragma unroll 1
+    for (u32 k = 0; k < n_terms; k++) {
+        const qm31 q = coef.c[uni(k)];
+        u32 x[W];
+        load_w<W>(colp_u(cols, k), row, x);
+#pragma unroll
+        for (int e = 0; e < W; e++) {
+            acc[e][0] += (u64)q.a * x[e];
+            acc[e][1] += (u64)q.b * x[e];
+            acc[e][2] += (u64)q.c * x[e];
+            acc[e][3] += (u64)q.d * x[e];
+        }
+        if ((k & 3) == 3) {
+#pragma unroll
+            for (int e = 0; e < W; e++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[e][j] = fold64(acc[e][j]);
+        }
+    }
+    u32 r[4][W];
+#pragma unroll
+    for (int e = 0; e < W; e++) {
+        r[0][e] = m31_add(m31_reduce_u64(acc[e][0]), constant.a); r[1][e] = m31_add(m31_reduce_u64(acc[e][1]), constant.b);
+        r[2][e] = m31_add(m31_reduce_u64(acc[e][2]), constant.c); r[3][e] = m31_add(m31_reduce_u64(acc[e][3]), constant.d);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if constexpr (W == 4) gstore4(out.p[j], row, make_uint4(r[j][0], r[j][1], r[j][2], r[j][3]));
+        else gstore1(out.p[j], row, r[j][0]);
+    }
+}
+
 // ---------------------------------------------------------------- coset-order prefix sum
-constexpr u32 kR = 7, kG = 16;                           // blocks of 2^7 j (256 coset rows), 16 blocks per tile
+constexpr u32 kR = 7, kG = 16;                          // blocks of 2^7 j (256 coset rows), 16 blocks per tile
 constexpr u32 kRuns = 1u << kR, kRunWords = 2 * kG;      // a tile: 128 runs of 32 words
 constexpr u32 kRunStride = kRunWords + 1;                // LDS row pitch (odd: the lanes of a block walk down a column)
 constexpr u32 kTileWords = kRuns * kRunStride;
@@ -416,6 +465,37 @@ int tstwo_logup_column(const tstwo_logup_frac *fracs, size_t n_fracs, const u32 
     a.flag = ctx().flag;
     if (vec) hipLaunchKernelGGL(k_logup_column<4>, dim3(ceil_div(n / 4, kThreads)), dim3(kThreads), 0, ctx().stream, a);
     else hipLaunchKernelGGL(k_logup_column<1>, dim3(ceil_div(n, kThreads)), dim3(kThreads), 0, ctx().stream, a);
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
+}
+
+int tstwo_gkr_logup_denominators(const u32 *const *cols, const u32 *coeffs, size_t n_terms, const u32 constant[4], u32 log_n,
+                                 u32 *const out[4]) {
+    TSTWO_REQUIRE_READY();
+    if (n_terms == 0 || n_terms > kMaxTerms) return bad("logup denominators: 1 to 16 terms");
+    if (log_n > kMaxLog) return bad("logup denominators: log_n above 28");
+    if (!cols || !coeffs || !constant) return bad("logup denominators: null host argument");
+    TSTWO_REQUIRE_TABLE(cols, n_terms); TSTWO_REQUIRE_TABLE(out, 4);
+    const u32 n = 1u << log_n;
+    bool vec = n % 4 == 0;
+    DenCoef coef = {};
+    for (size_t k = 0; k < n_terms; k++) {
+        for (int j = 0; j < 4; j++)
+            if (coeffs[4 * k + j] >= M31_P) return bad("logup denominators: coefficient word out of range");
+        coef.c[k] = to_q(coeffs + 4 * k);
+        for (int j = 0; j < 4; j++)
+            if (out[j] < cols[k] + n && cols[k] < out[j] + n) return bad("logup denominators: an output column is also an input");
+        vec = vec && aligned16(cols[k]);
+    }
+    for (int j = 0; j < 4; j++) {
+        if (constant[j] >= M31_P) return bad("logup denominators: constant out of range");
+        vec = vec && aligned16(out[j]);
+    }
+    ColPtrs cp;
+    if (int rc = fill_col_table(cp, cols, n_terms, 0)) return rc;
+    const Soa4 o = {{out[0], out[1], out[2], out[3]}};
+    if (vec) hipLaunchKernelGGL(k_gkr_logup_den<4>, dim3(ceil_div(n / 4, kThreads)), dim3(kThreads), 0, ctx().stream, cp, coef, to_q(constant), (u32)n_terms, o, n);
+    else hipLaunchKernelGGL(k_gkr_logup_den<1>, dim3(ceil_div(n, kThreads)), dim3(kThreads), 0, ctx().stream, cp, coef, to_q(constant), (u32)n_terms, o, n);
     TSTWO_LAUNCH_CHECK();
     return TSTWO_OK;
 }

@@ -2,6 +2,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "eval_sum.cuh"
 
 using namespace tstwo;
 
@@ -24,10 +25,6 @@ namespace {
 struct EvalW { qm31 w[16]; };        // products over the 4 "uniform" bits of a level (entry 0 = 1)
 struct EvalF { qm31 f[8]; };         // factors of the 8 lane bits of a level (A: f[0..3], B: f[4..7])
 
-__device__ __forceinline__ u32 red64(u64 x) {          // x < 2^64: canonical x mod P
-    u64 f = (x & M31_P) + (x >> 31);                     // < 2^31 + 2^33
-    return m31_reduce64(f);
-}
 // lane factor tables: entry e < 16 = prod_{i<4, bit i of e} f[i]; entry 16 + e = the same over f[4..7]
 __device__ __forceinline__ void eval_build_tables(qm31 *tab, const EvalF &ff) {
     const u32 t = threadIdx.x;
@@ -43,19 +40,6 @@ __device__ __forceinline__ void eval_build_tables(qm31 *tab, const EvalF &ff) {
         }
         tab[t] = v;
     }
-}
-// sum of one QM31 per lane over the workgroup (256 lanes); the result is valid in lane 0
-__device__ __forceinline__ qm31 eval_wg_sum(qm31 v, qm31 *scratch /* >= 4 entries */) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        qm31 o = {(u32)__shfl_down((int)v.a, off, 64), (u32)__shfl_down((int)v.b, off, 64), (u32)__shfl_down((int)v.c, off, 64),
-                  (u32)__shfl_down((int)v.d, off, 64)};
-        v = qm31_add(v, o);
-    }
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) v = qm31_add(qm31_add(scratch[0], scratch[1]), qm31_add(scratch[2], scratch[3]));
-    return v;
 }
 
 // Fold of up to 4096 QM31 partials by one workgroup (R = 16 per lane; fewer when `left` < 4096): entry i lives at

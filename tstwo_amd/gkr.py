@@ -12,6 +12,12 @@ leaves the challenge in device memory for the next round's fold; per layer one u
 polynomials, assignment, masks).  Elsewhere, and with device_rounds=False, the protocol of a round runs on the host: one read-back
 per round (the (f(0), f(2)) slots of every active instance) and one per layer (the 2-point masks).  The first read-back also takes
 every instance's output values and first mask.
+
+The two ends: logup_input_layer builds a LogUp input layer from M31 trace columns (denominators sum_i alpha^i col_i - z by
+tstwo_gkr_logup_denominators; numerators none, a base column or a secure MLE), and verify_input_claims checks what
+partially_verify_batch leaves open — each input layer evaluated at the artifact's point by Mle.eval_at_point, one pass over the
+values on the device (csrc/mle_eval.hip) — with check_logup_sum for the fractions the LogUp instances output.  gkr_lookup.py runs
+a range check through all of it.
 """
 from __future__ import annotations
 
@@ -93,9 +99,36 @@ class Mle:
 
     fixFirstVariable = fix_first_variable
 
+    def eval_at_point(self, point) -> QM31:
+        """Mle.evalAtPoint (lookups/mle.ts:81-114): one pass over the values on the device, one read-back."""
+        return eval_mles_at_point([self], point)[0]
+
+    evalAtPoint = eval_at_point
+
     def free(self) -> None:
         for c in ([self.col] if self.is_base else self.col.columns):
             c.buf.free()
+
+
+def eval_mles_at_point(mles, point):
+    """Mle.evalAtPoint of several MLEs at one point (tstwo_mle_eval_at_point_base / _secure): one call, and one read-back, per
+    kind and size; the values come back in input order.  A point whose length is not an MLE's n_variables() raises ValueError (Rust
+    asserts it; the reference misbehaves silently)."""
+    mles, point = list(mles), list(point)
+    groups = {}
+    for i, m in enumerate(mles):
+        if m.n_variables() != len(point):
+            raise ValueError(f"a point of {len(point)} coordinates for an MLE of {m.n_variables()} variables")
+        groups.setdefault((m.is_base, m.n_variables()), []).append(i)
+    words = L.u32x([w for p in point for w in p.tup()])
+    out = [None] * len(mles)
+    for (is_base, n), idx in groups.items():
+        res = (C.c_uint32 * (4 * len(idx)))()
+        L.call("tstwo_mle_eval_at_point_base" if is_base else "tstwo_mle_eval_at_point_secure",
+               L.ptr_array([p for i in idx for p in mles[i].ptr_list()]), len(idx), n, words, res)
+        for k, i in enumerate(idx):
+            out[i] = _qs(res[4 * k:4 * k + 4])
+    return out
 
 
 class Layer:
@@ -152,6 +185,14 @@ class Layer:
         kind = LOGUP_GENERIC if self.kind == LOGUP_MULTIPLICITIES else self.kind
         num = self.num.fix_first_variable(x0) if self.num is not None else None
         return Layer(kind, num, self.den.fix_first_variable(x0))
+
+    def eval_at_point(self, point):
+        """The layer's columns at `point`, in mask order: [den] for a grand product, [num, den] for LogUp, [1, den] for
+        LogUpSingles — what partially_verify_batch leaves in claims_to_verify_by_instance."""
+        vals = eval_mles_at_point(self.columns(), point)
+        return [QM31.one()] + vals if self.kind == LOGUP_SINGLES else vals
+
+    evalAtPoint = eval_at_point
 
     def into_multivariate_poly(self, lam: QM31, eq_evals: "EqEvals") -> "GkrMultivariatePolyOracle":
         return GkrMultivariatePolyOracle(eq_evals, self, QM31.one(), lam)
@@ -321,6 +362,93 @@ class HipMleOps:
             L.call("tstwo_mle_fix_first_variable_base", C.c_void_p(mle.col.ptr), mle.n_variables(), _q(assignment), out.ptrs())
         else:
             L.call("tstwo_mle_fix_first_variable_secure", mle.ptrs(), mle.n_variables(), _q(assignment), out.ptrs())
+
+
+    @staticmethod
+    def evalAtPoint(mle: Mle, point) -> QM31:
+        """Mle.evalAtPoint (lookups/mle.ts:81-114) on the device."""
+        return mle.eval_at_point(point)
+
+
+# ---------------------------------------------------------------- input layers from trace columns, and the claims on them
+class GkrInputClaimMismatch(Exception):
+    """An input layer does not take the value the GKR artifact claims for it at the out-of-domain point."""
+
+    def __init__(self, instance: int, column: int):
+        super().__init__(f"input layer of instance {instance}: column {column} does not evaluate to its claim")
+        self.instance, self.column = instance, column
+
+
+def logup_denominators(form) -> Mle:
+    """tstwo_gkr_logup_denominators: the LinearForm sum_t coeff_t cols_t[r] + constant written out as a secure MLE (asynchronous;
+    the row order of the columns is the order of the MLE)."""
+    from .logup import MAX_TERMS
+    if not 1 <= len(form.terms) <= MAX_TERMS:
+        raise ValueError(f"a denominator needs 1 to {MAX_TERMS} column terms")
+    n = form.terms[0][1].len()
+    if any(col.len() != n for _, col in form.terms):
+        raise ValueError("the columns of a denominator must have one length")
+    out = Mle.uninitialized_secure(n)
+    L.call("tstwo_gkr_logup_denominators", L.ptr_array([col.ptr for _, col in form.terms]),
+           L.u32x([w for p, _ in form.terms for w in p.tup()]), len(form.terms), _q(form.constant), _log2(n), out.ptrs())
+    return out
+
+
+def logup_input_layer(form_or_relation, values=None, numerators=None) -> Layer:
+    """A LogUp input layer over trace columns.  The denominators are a logup.LinearForm, or relation.combine_columns(values) of a
+    logup.LookupElements (sum_i alpha^i values_i - z).  numerators: None = LogUpSingles; a HipColumn or a base Mle =
+    LogUpMultiplicities; a secure Mle = LogUpGeneric."""
+    from .logup import LinearForm
+    if isinstance(form_or_relation, LinearForm):
+        if values is not None:
+            raise ValueError("values go with a relation, not with a LinearForm")
+        form = form_or_relation
+    else:
+        if values is None:
+            raise ValueError("a relation needs the values it combines")
+        form = form_or_relation.combine_columns(values)
+    den = logup_denominators(form)
+    if numerators is None:
+        return Layer.logup_singles(den)
+    num = numerators if isinstance(numerators, Mle) else Mle.base(numerators)
+    return Layer.logup_multiplicities(num, den) if num.is_base else Layer.logup_generic(num, den)
+
+
+def verify_input_claims(artifact: GkrArtifact, layers) -> None:
+    """The check partially_verify_batch leaves open: input layer i, evaluated on the device at the last n_i coordinates of
+    artifact.ood_point, gives claims_to_verify_by_instance[i].  Raises GkrInputClaimMismatch(instance, column)."""
+    layers = list(layers)
+    if len(layers) != len(artifact.n_variables_by_instance):
+        raise ValueError(f"{len(layers)} input layers for {len(artifact.n_variables_by_instance)} instances")
+    n = max(artifact.n_variables_by_instance)
+    for i, (lay, nv, claims) in enumerate(zip(layers, artifact.n_variables_by_instance, artifact.claims_to_verify_by_instance)):
+        if lay.n_variables() != nv:
+            raise ValueError(f"input layer {i} has {lay.n_variables()} variables, the artifact says {nv}")
+        got = lay.eval_at_point(artifact.ood_point[n - nv:])
+        if len(got) != len(claims):
+            raise ValueError(f"input layer {i} has {len(got)} columns, the artifact claims {len(claims)}")
+        for col, (g, want) in enumerate(zip(got, claims)):
+            if g.tup() != want.tup():
+                raise GkrInputClaimMismatch(i, col)
+
+
+def check_logup_sum(output_claims_by_instance, gates, claimed: QM31 | None = None) -> None:
+    """The fractions (numerator, denominator) the LogUp instances output add up to `claimed` (zero by default).  Host only, by
+    cross-multiplication: N / D = sum n_i / d_i is kept as (N, D) and nothing is inverted.  Raises InvalidLogupSum, also for a
+    zero denominator (prover.InvalidLogupSum: the error of the STARK's own LogUp sum check)."""
+    from .gkr_verifier import Gate
+    from .prover import InvalidLogupSum
+    claimed = QM31.zero() if claimed is None else claimed
+    num, den = QM31.zero(), QM31.one()
+    for out, gate in zip(output_claims_by_instance, gates):
+        if gate is not Gate.LogUp:
+            continue
+        n_i, d_i = out
+        if d_i.tup() == _Z:
+            raise InvalidLogupSum("a LogUp instance outputs the denominator zero")
+        num, den = num.mul(d_i).add(n_i.mul(den)), den.mul(d_i)
+    if num.tup() != claimed.mul(den).tup():
+        raise InvalidLogupSum("the LogUp fractions do not add up to the claimed sum")
 
 
 _NULL4 = None
@@ -715,5 +843,6 @@ def prove_batch(channel, input_layer_by_instance, device_rounds=None):
 
 
 __all__ = ["GRAND_PRODUCT", "LOGUP_GENERIC", "LOGUP_MULTIPLICITIES", "LOGUP_SINGLES", "EqEvals", "GkrArtifact", "GkrBatchProof",
-           "GkrMask", "GkrMultivariatePolyOracle", "HipGkrOps", "HipMleOps", "Layer", "Mle", "correct_sum_as_poly_in_first_variable",
-           "device_rounds_supported", "fold_mle_evals", "inv_eq0_table", "prove_batch", "round_finish"]
+           "GkrInputClaimMismatch", "GkrMask", "GkrMultivariatePolyOracle", "HipGkrOps", "HipMleOps", "Layer", "Mle", "check_logup_sum",
+           "correct_sum_as_poly_in_first_variable", "device_rounds_supported", "eval_mles_at_point", "fold_mle_evals", "inv_eq0_table",
+           "logup_denominators", "logup_input_layer", "prove_batch", "round_finish", "verify_input_claims"]
