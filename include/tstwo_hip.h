@@ -625,6 +625,23 @@ int tstwo_air_program_destroy(uint64_t kernel_id);
 #define TSTWO_AIR_COLUMNS_MAX_OUT 64
 int tstwo_air_eval_columns(const uint32_t *const *cols, size_t n_cols, uint32_t log_size, const uint32_t *program,
                            size_t program_len, uint32_t *const *out, size_t n_out);
+/* The column programs compiled to native kernels at run time, opt-in: tstwo_air_eval_columns_compiled writes bit for bit what
+ * tstwo_air_eval_columns writes for the program the kernel was compiled from.
+ * tstwo_air_columns_compile: validates the program (the checks and texts of tstwo_air_eval_columns; TSTWO_AIR_OP_ACC is a bad
+ *   opcode, as TSTWO_AIR_OP_STORE is for tstwo_air_program_compile), writes it as HIP source (every STORE is one 16-byte store per
+ *   lane, or one word for unaligned columns), compiles it with hipRTC and loads it, as tstwo_air_program_compile does.
+ *   *kernel_id comes from the same table and the same counter; log_size is not part of a kernel.  Synchronous; refused during
+ *   graph capture; TSTWO_ERR_HIP "hipRTC is not available" without hipRTC.
+ * tstwo_air_eval_columns_compiled: the arguments, limits and error texts of tstwo_air_eval_columns without the program; n_cols
+ *   and n_out must be those the kernel was compiled for.  An id that is unknown, destroyed or from before tstwo_shutdown is
+ *   TSTWO_ERR_BAD_ARG "unknown air kernel"; the id of a constraint kernel is TSTWO_ERR_BAD_ARG "air columns: the kernel was
+ *   compiled from a constraint program" (and the id of a columns kernel given to tstwo_air_eval_compiled "air program: the
+ *   kernel was compiled from a columns program").  Nothing is uploaded: with at most 64 input columns the call may be recorded
+ *   during graph capture (more than 64 go through a table in device memory, which is refused there).  Asynchronous.
+ * tstwo_air_kernel_info and tstwo_air_program_destroy serve kernels of both kinds. */
+int tstwo_air_columns_compile(const uint32_t *program, size_t program_len, size_t n_cols, size_t n_out, uint64_t *kernel_id);
+int tstwo_air_eval_columns_compiled(uint64_t kernel_id, const uint32_t *const *cols, size_t n_cols, uint32_t log_size,
+                                    uint32_t *const *out, size_t n_out);
 
 /* ---------------------------------------------------------------- LogUp interaction trace
  * Rust stwo constraint_framework/logup.rs (LogupTraceGenerator, LogupColGenerator); tstwo_amd/logup.py drives it.

@@ -10,9 +10,14 @@
     range_check_table_interaction_trace (downloads the multiplicities, negates them in numpy, uploads them and the table column
     again).  Host wall time ended by a device synchronisation, the two alternating, median of --reps; `ratio` is hand-written
     over derived.
+(c) --native: part (a) for the interpreter (tstwo_air_eval_columns) and for the native kernel of the same program
+    (tstwo_air_columns_compile / tstwo_air_eval_columns_compiled) in the same process, the two alternating inside every
+    repetition, with the outputs of both compared at every size; the compile wall time and the kernel's resources
+    (tstwo_air_kernel_info) are reported per program, apart from the run times.  Part (b) is timed with native=False and True.
 Prints one JSON line and writes it to --out.
 
     python tools/bench_air_columns.py [--logs 16,20,22] [--reps 10] [--out profiles/r14_bench_air_columns.json]
+    python tools/bench_air_columns.py --native [--out profiles/bench_air_columns_native.json]
 """
 from __future__ import annotations
 
@@ -71,6 +76,22 @@ def event_ms(fn, reps):
     return statistics.median(ts)
 
 
+def event_ms_alternating(fns, reps):
+    """event_ms for several functions at once: each warmed up, then one call of each per repetition, in turn."""
+    for fn in fns:
+        fn()
+    L.sync()
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for k, fn in enumerate(fns):
+            e0, e1 = L.Event(), L.Event()
+            e0.record()
+            fn()
+            e1.record()
+            ts[k].append(e0.elapsed_ms(e1))
+    return [statistics.median(t) for t in ts]
+
+
 def entry(ms, b):
     return {"ms": ms, "bytes": b, "hbm_bound_ms": b / HBM_COPY * 1e3, "achieved_tb_s": b / ms / 1e9, "frac_hbm": b / HBM_COPY * 1e3 / ms}
 
@@ -79,7 +100,7 @@ def felt(rng):
     return QM31.from_u32_unchecked(*[int(v) for v in rng.integers(0, P, size=4)])
 
 
-def kernel(log, reps, rng):
+def kernel(log, reps, rng, native=False):
     n = 1 << log
     le = LG.LookupElements(felt(rng), felt(rng), 3)
     cols = [HipColumn(rng.integers(0, P, size=n, dtype=np.uint32)) for _ in range(5)]
@@ -88,9 +109,20 @@ def kernel(log, reps, rng):
         plan = LG.plan_interaction_trace(eval_)
         program = F.compile_columns(plan.exprs, n_main, n_pre)
         loads = {(program.words[2 * i] >> 16, program.words[2 * i + 1]) for i in range(program.n_instr) if program.words[2 * i] & 0xff == F.OP_LOAD}
-        ms = event_ms(lambda: F.evaluate_columns(cols[:n_main + n_pre], log, program, program.n_out), reps)
-        res[name] = dict(entry(ms, (len(loads) + program.n_out) * 4 * n), n_instr=program.n_instr, n_regs=program.n_regs,
-                         distinct_loads=len(loads), stores=program.n_out)
+        ins, nbytes = cols[:n_main + n_pre], (len(loads) + program.n_out) * 4 * n
+        shape = dict(n_instr=program.n_instr, n_regs=program.n_regs, distinct_loads=len(loads), stores=program.n_out)
+        if not native:
+            ms = event_ms(lambda: F.evaluate_columns(ins, log, program, program.n_out), reps)
+            res[name] = dict(entry(ms, nbytes), **shape)
+            continue
+        kernel_ = F.compile_columns_native(program, len(ins))          # compiled here, outside every timed window
+        same = all(np.array_equal(a.to_numpy(), b.to_numpy()) for a, b in zip(F.evaluate_columns(ins, log, program, program.n_out),
+                                                                             F.evaluate_columns(ins, log, program, program.n_out, native=True)))
+        ms_i, ms_n = event_ms_alternating([lambda: F.evaluate_columns(ins, log, program, program.n_out),
+                                           lambda: F.evaluate_columns(ins, log, program, program.n_out, native=True)], reps)
+        res[name] = dict(shape, bytes=nbytes, hbm_bound_ms=nbytes / HBM_COPY * 1e3, interpreter=entry(ms_i, nbytes), native=entry(ms_n, nbytes),
+                         speedup=ms_i / ms_n, same_outputs=bool(same), compile_seconds=kernel_.compile_seconds,
+                         kernel_info={k: v for k, v in kernel_.info().items() if k != "compile_seconds"})
     return res
 
 
@@ -102,7 +134,7 @@ def wall_ms(fn):
     return (time.perf_counter() - t0) * 1e3
 
 
-def range_check_table(log, reps, rng):
+def range_check_table(log, reps, rng, native=False):
     le = LG.LookupElements(felt(rng), felt(rng), 1)
     mult = HipColumn(F.range_check_multiplicities(log, rng.integers(0, 1 << log, size=1 << log)))
     table = HipColumn(F.range_check_table_column(log))
@@ -117,22 +149,41 @@ def range_check_table(log, reps, rng):
         td.append(wall_ms(derived))
         th.append(wall_ms(hand))
     d, h = statistics.median(td), statistics.median(th)
-    return {"log": log, "derived_ms": d, "hand_written_ms": h, "ratio": h / d, "same_trace": bool(same)}
+    res = {"log": log, "derived_ms": d, "hand_written_ms": h, "ratio": h / d, "same_trace": bool(same)}
+    if native:
+        derived_native = lambda: LG.derive_interaction_trace(eval_, [mult], [table], native=True)     # noqa: E731
+        n_ev, n_sum = derived_native()
+        (d_ev, d_sum) = derived()
+        res["same_trace_native"] = bool(n_sum == d_sum and all(np.array_equal(a.values.to_numpy(), b.values.to_numpy()) for a, b in zip(n_ev, d_ev)))
+        del n_ev, d_ev
+        td, tn = [], []
+        for _ in range(reps):
+            td.append(wall_ms(derived))
+            tn.append(wall_ms(derived_native))
+        res.update(derived_ms=statistics.median(td), derived_native_ms=statistics.median(tn))
+        res["ratio"] = h / res["derived_ms"]
+    return res
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--logs", default="16,20,22")
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r14_bench_air_columns.json"))
+    ap.add_argument("--native", action="store_true", help="time the interpreter and the native kernels side by side")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "bench_air_columns_native.json" if a.native else "r14_bench_air_columns.json")
     if a.reps < 10:
         raise SystemExit("--reps: at least 10")
     logs = [int(x) for x in a.logs.split(",") if x]
     L.init(0)
     rng = np.random.default_rng(0)
     out = {"device": L.device_name(), "reps": a.reps, "hbm_tb_s": HBM_COPY / 1e12,
-           "kernel": [kernel(lg, a.reps, rng) for lg in logs], "range_check_table": [range_check_table(lg, a.reps, rng) for lg in logs]}
+           "kernel": [kernel(lg, a.reps, rng, a.native) for lg in logs],
+           "range_check_table": [range_check_table(lg, a.reps, rng, a.native) for lg in logs]}
+    if a.native:
+        out["native"] = True
     line = json.dumps(out)
     if a.out:
         os.makedirs(os.path.dirname(a.out), exist_ok=True)

@@ -10,7 +10,8 @@ A component is a FrameworkComponent of an eval, an object with `log_size()`, `ma
   PointEvaluator    the constraints over QM31 at the out-of-domain point (the verifier, and the prover's sanity check).
 A fourth, RelationEvaluator, keeps the relation entries of `evaluate` as they were added (relation, multiplicity, values) and
 their batching: logup.derive_interaction_trace builds the interaction trace from them, with compile_columns / evaluate_columns
-(tstwo_air_eval_columns) for every multiplicity or value that is an expression of columns.
+(tstwo_air_eval_columns; with native=True a kernel compiled from the columns program, compile_columns_native /
+tstwo_air_eval_columns_compiled) for every multiplicity or value that is an expression of columns.
 The prover evaluates a component's constraints on the whole evaluation domain with one launch: WideFibonacciEval and MulAddEval
 (exactly these types, not subclasses) run on the hand-written kernel of tstwo_air_constraint_quotients, every other eval on the
 program interpreter or, for a FrameworkComponent made with native=True, on a kernel compiled from the program at construction
@@ -759,11 +760,16 @@ def evaluate_program(cols, trace_log_size: int, log_expand: int, program: Progra
 
 
 class NativeKernel:
-    """A program compiled to a native kernel (tstwo_air_program_compile): `id` names it in the library's table, n_cols and
-    n_constraints are what it was compiled for, compile_seconds the wall time of the compilation."""
+    """A program compiled to a native kernel (tstwo_air_program_compile, or tstwo_air_columns_compile for a columns program):
+    `id` names it in the library's table, n_cols and n_constraints (the outputs of a columns program: n_out) are what it was
+    compiled for, compile_seconds the wall time of the compilation."""
 
     def __init__(self, id_: int, n_cols: int, n_constraints: int, compile_seconds: float):
         self.id, self.n_cols, self.n_constraints, self.compile_seconds = id_, n_cols, n_constraints, compile_seconds
+
+    @property
+    def n_out(self) -> int:
+        return self.n_constraints
 
     def info(self) -> dict:
         """tstwo_air_kernel_info: VGPRs, SGPRs and private-segment bytes of both widths, the code-object size, the compile time."""
@@ -780,6 +786,16 @@ def compile_native(program: Program, n_cols: int) -> NativeKernel:
     """The native kernel of a constraint program over n_cols columns, compiled once per process: programs with the same words
     (the same eval at any size) share it.  A cached kernel the library no longer knows (tstwo_shutdown unloads every kernel,
     and so does tstwo_init on another device) is compiled again."""
+    return _compile_native("tstwo_air_program_compile", program, n_cols)
+
+
+def compile_columns_native(program: Program, n_cols: int) -> NativeKernel:
+    """The native kernel of a compile_columns program over n_cols input columns (tstwo_air_columns_compile), cached and
+    recompiled as compile_native's: the words of a columns program (its STOREs) never equal those of a constraint program."""
+    return _compile_native("tstwo_air_columns_compile", program, n_cols)
+
+
+def _compile_native(entry: str, program: Program, n_cols: int) -> NativeKernel:
     key = (tuple(program.words), n_cols)
     kernel = _native_kernels.get(key)
     if kernel is not None:
@@ -791,7 +807,7 @@ def compile_native(program: Program, n_cols: int) -> NativeKernel:
     L.ensure_init()
     kid = C.c_uint64(0)
     t0 = time.perf_counter()
-    L.call("tstwo_air_program_compile", L.u32x(program.words), program.n_instr, n_cols, program.n_constraints, C.byref(kid))
+    L.call(entry, L.u32x(program.words), program.n_instr, n_cols, program.n_constraints, C.byref(kid))
     kernel = _native_kernels[key] = NativeKernel(kid.value, n_cols, program.n_constraints, time.perf_counter() - t0)
     return kernel
 
@@ -805,9 +821,11 @@ def evaluate_program_native(cols, trace_log_size: int, log_expand: int, kernel: 
            cw, len(coeffs), dinv, accum.ptrs())
 
 
-def evaluate_columns(cols, log_size: int, program: Program, n_out: int) -> list:
+def evaluate_columns(cols, log_size: int, program: Program, n_out: int, *, native: bool = False) -> list:
     """tstwo_air_eval_columns: the n_out output columns (new HipColumns of 2^log_size values) of a compile_columns program over
-    `cols`, HipColumns on CanonicCoset(log_size).circle_domain() in storage order (main, then preprocessed).  Asynchronous."""
+    `cols`, HipColumns on CanonicCoset(log_size).circle_domain() in storage order (main, then preprocessed).  Asynchronous.
+    native=True (opt-in): the program is compiled once per process (compile_columns_native) and
+    tstwo_air_eval_columns_compiled runs that kernel instead of the interpreter, with identical results."""
     from .backend import HipColumn
     if n_out != program.n_out:
         raise ValueError(f"the program stores {program.n_out} outputs, {n_out} were asked for")
@@ -815,6 +833,11 @@ def evaluate_columns(cols, log_size: int, program: Program, n_out: int) -> list:
     if any(c.len() != n for c in cols):
         raise ValueError("every column must hold 2^log_size values")
     out = [HipColumn.uninitialized(n) for _ in range(n_out)]
+    if native:
+        kernel = compile_columns_native(program, len(cols))
+        L.call("tstwo_air_eval_columns_compiled", kernel.id, L.ptr_array([c.ptr for c in cols]), len(cols), log_size,
+               L.ptr_array([c.ptr for c in out]), n_out)
+        return out
     L.call("tstwo_air_eval_columns", L.ptr_array([c.ptr for c in cols]), len(cols), log_size, L.u32x(program.words), program.n_instr,
            L.ptr_array([c.ptr for c in out]), n_out)
     return out
@@ -882,6 +905,12 @@ class FrameworkComponent:
     def native_info(self) -> dict | None:
         """NativeKernel.info() of the component's kernel; None for a component that does not run one."""
         return self.native.info() if self.native is not None else None
+
+    def derive_interaction_trace(self, main, preprocessed=()):
+        """logup.derive_interaction_trace of the component's eval, through native column kernels when the component runs a
+        native constraint kernel (native=True)."""
+        from .logup import derive_interaction_trace
+        return derive_interaction_trace(self.eval, main, preprocessed, native=self.native is not None)
 
     # --- Component
     def max_constraint_log_degree_bound(self) -> int:

@@ -14,6 +14,8 @@
 //     (fetch, exec_op, the LDS register file) and has no accumulators, coefficients or denominators.
 //   tstwo_air_eval_compiled  the contract and argument checks of k_air_program's entry, run by a kernel that air_native.hip
 //     compiled from the program (air_codegen.h writes its source; the program validator of all three entries lives there).
+//   tstwo_air_eval_columns_compiled  the same for k_air_columns: the entry's argument checks, a kernel compiled from the STORE
+//     program (tstwo_air_columns_compile), and no upload at all, so it can be recorded into a graph.
 // Row r (bit-reversed order on CanonicCoset(trace_log + log_expand).circle_domain()):
 //   row_res = sum_i coeff_i c_i(r),   accum[r] += row_res * denom_inv[r >> trace_log]
 //
@@ -487,6 +489,27 @@ int check_eval_args(const u32 *const *cols, size_t n_cols, u32 trace_log_size, u
     return TSTWO_OK;
 }
 
+// What tstwo_air_eval_columns and tstwo_air_eval_columns_compiled ask of everything but the program itself: the log range and
+// the counts, then the two tables.
+int check_columns_shape(size_t n_cols, u32 log_size, size_t n_out) {
+    if (log_size < 1 || log_size > kMaxLog) return bad("air columns: log_size out of range");
+    if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return bad("air columns: number of columns out of range");
+    if (n_out == 0 || n_out > TSTWO_AIR_COLUMNS_MAX_OUT) return bad("air columns: number of outputs out of range");
+    return TSTWO_OK;
+}
+int check_columns_tables(const u32 *const *cols, size_t n_cols, u32 *const *out, size_t n_out) {
+    TSTWO_REQUIRE_TABLE(cols, n_cols);
+    TSTWO_REQUIRE_TABLE(out, n_out);
+    // a load at an offset reads rows that other lanes store: no output may be an input (or another output)
+    for (size_t k = 0; k < n_out; k++) {
+        for (size_t i = 0; i < n_cols; i++)
+            if (out[k] == cols[i]) return bad("air columns: an output column is also an input column");
+        for (size_t i = 0; i < k; i++)
+            if (out[k] == out[i]) return bad("air columns: two outputs are the same column");
+    }
+    return TSTWO_OK;
+}
+
 template <int KIND>
 int launch_quotients(const ColPtrs &cp, const AirArgs &a, bool vec) {
     if (vec) hipLaunchKernelGGL((k_constraint_quotients<KIND, 4>), dim3(grid_for(a.n_rows / 4)), dim3(kThreads), 0, ctx().stream, cp, a);
@@ -581,8 +604,10 @@ int tstwo_air_eval_program(const u32 *const *cols, size_t n_cols, u32 trace_log_
 int tstwo_air_eval_compiled(uint64_t kernel_id, const u32 *const *cols, size_t n_cols, u32 trace_log_size, u32 log_expand,
                             const u32 *coeffs, size_t n_constraints, const u32 *denom_inv, u32 *const accum[4]) {
     TSTWO_REQUIRE_READY();
+    AirKernelKind kind;
     u32 for_cols = 0, for_constraints = 0;
-    if (int rc = air_native_shape(kernel_id, for_cols, for_constraints)) return rc;
+    if (int rc = air_native_shape(kernel_id, kind, for_cols, for_constraints)) return rc;
+    if (kind != kAirKernelConstraints) return bad("air program: the kernel was compiled from a columns program");
     if (int rc = check_eval_args(cols, n_cols, trace_log_size, log_expand, coeffs, n_constraints, denom_inv, accum)) return rc;
     if (n_cols != for_cols) return bad("air kernel: compiled for another number of columns");
     if (n_constraints != for_constraints) return bad("air kernel: compiled for another number of constraints");
@@ -610,34 +635,14 @@ int tstwo_air_eval_compiled(uint64_t kernel_id, const u32 *const *cols, size_t n
 int tstwo_air_eval_columns(const u32 *const *cols, size_t n_cols, u32 log_size, const u32 *program, size_t program_len,
                            u32 *const *out, size_t n_out) {
     TSTWO_REQUIRE_READY();
-    if (log_size < 1 || log_size > kMaxLog) return bad("air columns: log_size out of range");
-    if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return bad("air columns: number of columns out of range");
-    if (n_out == 0 || n_out > TSTWO_AIR_COLUMNS_MAX_OUT) return bad("air columns: number of outputs out of range");
+    if (int rc = check_columns_shape(n_cols, log_size, n_out)) return rc;
     if (program_len == 0 || program_len > TSTWO_AIR_PROGRAM_MAX_INSTR) return bad("air columns: program length out of range");
     if (!program) return bad("null host argument");
-    TSTWO_REQUIRE_TABLE(cols, n_cols);
-    TSTWO_REQUIRE_TABLE(out, n_out);
-    // a load at an offset reads rows that other lanes store: no output may be an input (or another output)
-    for (size_t k = 0; k < n_out; k++) {
-        for (size_t i = 0; i < n_cols; i++)
-            if (out[k] == cols[i]) return bad("air columns: an output column is also an input column");
-        for (size_t i = 0; i < k; i++)
-            if (out[k] == out[i]) return bad("air columns: two outputs are the same column");
-    }
+    if (int rc = check_columns_tables(cols, n_cols, out, n_out)) return rc;
     // the program words travel through the small-upload ring, which a captured graph cannot replay
     if (stream_is_capturing()) return bad("host-array upload during graph capture (the air columns program cannot be recorded)");
-    bool stored[TSTWO_AIR_COLUMNS_MAX_OUT] = {};
-    size_t n_stored = 0;
     u32 n_regs = 0;
-    auto on_store = [&](u32 k) -> const char * {
-        if (k >= n_out) return "output index out of range";
-        if (stored[k]) return "output stored twice";
-        stored[k] = true;
-        n_stored++;
-        return (const char *)nullptr;
-    };
-    if (const char *why = check_program(program, program_len, n_cols, TSTWO_AIR_OP_STORE, n_regs, on_store)) return bad(std::string("air columns: ") + why);
-    if (n_stored != n_out) return bad("air columns: an output is never stored");
+    if (const char *why = check_store_program(program, program_len, n_cols, n_out, n_regs)) return bad(std::string("air columns: ") + why);
     const size_t bytes = 2 * program_len * sizeof(u32);
     static_assert(2 * TSTWO_AIR_PROGRAM_MAX_INSTR * 4 <= kUpSlotBytes, "program upload exceeds one ring slot");
     if (int rc = ensure_scratch(bytes)) return rc;
@@ -657,6 +662,29 @@ int tstwo_air_eval_columns(const u32 *const *cols, size_t n_cols, u32 log_size, 
     else hipLaunchKernelGGL(k_air_columns<1>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, op, a);
     TSTWO_LAUNCH_CHECK();
     return TSTWO_OK;
+}
+
+int tstwo_air_eval_columns_compiled(uint64_t kernel_id, const u32 *const *cols, size_t n_cols, u32 log_size, u32 *const *out, size_t n_out) {
+    TSTWO_REQUIRE_READY();
+    AirKernelKind kind;
+    u32 for_cols = 0, for_out = 0;
+    if (int rc = air_native_shape(kernel_id, kind, for_cols, for_out)) return rc;
+    if (kind != kAirKernelColumns) return bad("air columns: the kernel was compiled from a constraint program");
+    if (int rc = check_columns_shape(n_cols, log_size, n_out)) return rc;
+    if (int rc = check_columns_tables(cols, n_cols, out, n_out)) return rc;
+    if (n_cols != for_cols) return bad("air kernel: compiled for another number of columns");
+    if (n_out != for_out) return bad("air kernel: compiled for another number of outputs");
+    // nothing is uploaded: with at most 64 input columns both tables travel by value and the launch can be captured
+    ColPtrs cp, op;
+    if (int rc = fill_col_table(cp, cols, n_cols, 0)) return rc;
+    if (int rc = fill_col_table(op, (const u32 *const *)out, n_out, 1)) return rc;      // at most 64: by value
+    ColumnsArgs a = {};
+    a.log = log_size;
+    a.n_rows = 1u << log_size;
+    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, out, n_out);
+    const unsigned grid = grid_for(a.n_rows / (vec ? 4 : 1));
+    a.stride = grid * kThreads;
+    return air_native_launch_columns(kernel_id, vec, grid, cp, op, a);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // air_codegen.h — a constraint program (the words of tstwo_air_eval_program) as HIP source text (host only: no HIP, no context).
-// check_program validates the programs of all three entries (tstwo_air_eval_program, tstwo_air_eval_columns,
-// tstwo_air_program_compile); air_codegen writes, for one program, two extern "C" kernels with the contract of k_air_program
+// check_program validates the programs of every entry (tstwo_air_eval_program, tstwo_air_eval_columns,
+// tstwo_air_program_compile, tstwo_air_columns_compile); air_codegen writes, for one program, two extern "C" kernels with the contract of k_air_program
 // (air.hip): for every row r, accum[r] += (sum_k coeff_k e_k(r)) * denom_inv[r >> trace_log].  tests/test_cpu_air_codegen.py
 // builds tests/air_codegen_main.cpp around this header alone.
 //
@@ -11,6 +11,11 @@
 // per distinct offset; column and coefficient indices are constants of the text.  The accumulators fold after every fourth ACC
 // and reduce once per row, as the interpreter's.  trace_log, log_expand and n_rows are kernel arguments: one text serves every
 // domain size.  The same words give the same text.
+//
+// air_columns_codegen is the twin for the STORE programs of tstwo_air_eval_columns (check_store_program validates them for the
+// interpreter entry and for the generator): the same statements, neighbours on the TRACE domain, `STORE k` as one store_rows
+// to output column k, kernels air_columns_w4 / air_columns_w1 with the contract of k_air_columns.  Its device helpers
+// (csrc/air_native_columns_prelude.inc) follow the prelude in column texts only: the text of an ACC program does not change.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -76,6 +81,25 @@ inline const char *check_acc_program(const uint32_t *program, size_t program_len
     return nullptr;
 }
 
+// What tstwo_air_eval_columns and tstwo_air_columns_compile accept: the limits, every instruction, every output stored once.
+inline const char *check_store_program(const uint32_t *program, size_t program_len, size_t n_cols, size_t n_out, uint32_t &n_regs) {
+    if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return "number of columns out of range";
+    if (n_out == 0 || n_out > TSTWO_AIR_COLUMNS_MAX_OUT) return "number of outputs out of range";
+    if (program_len == 0 || program_len > TSTWO_AIR_PROGRAM_MAX_INSTR) return "program length out of range";
+    bool stored[TSTWO_AIR_COLUMNS_MAX_OUT] = {};
+    size_t n_stored = 0;
+    auto on_store = [&](uint32_t k) -> const char * {
+        if (k >= n_out) return "output index out of range";
+        if (stored[k]) return "output stored twice";
+        stored[k] = true;
+        n_stored++;
+        return (const char *)nullptr;
+    };
+    if (const char *why = check_program(program, program_len, n_cols, TSTWO_AIR_OP_STORE, n_regs, on_store)) return why;
+    if (n_stored != n_out) return "an output is never stored";
+    return nullptr;
+}
+
 inline const char *air_native_prelude() {
     static const char text[] =
 #include "air_native_prelude.inc"
@@ -83,9 +107,19 @@ inline const char *air_native_prelude() {
     return text;
 }
 
+// The helpers of column texts alone, behind air_native_prelude().
+inline const char *air_native_columns_prelude() {
+    static const char text[] =
+#include "air_native_columns_prelude.inc"
+        ;
+    return text;
+}
+
 // The kernels of a compiled program, and what hipRTC is given besides --offload-arch=<the device's architecture>.
 constexpr const char *kAirNativeKernelW4 = "air_native_w4";
 constexpr const char *kAirNativeKernelW1 = "air_native_w1";
+constexpr const char *kAirColumnsKernelW4 = "air_columns_w4";
+constexpr const char *kAirColumnsKernelW1 = "air_columns_w1";
 constexpr int kAirNativeThreads = 256;
 constexpr const char *kAirNativeOptions[] = {"-O3", "-std=c++17"};
 
@@ -107,34 +141,28 @@ inline bool code_object_uint(const char *code, size_t size, const char *kernel, 
     return true;
 }
 
-// The source text of a program's two kernels into `out`.  Returns the reason (the texts of tstwo_air_eval_program, without
-// its prefix) and leaves `out` empty for a program the interpreter would refuse.
-inline const char *air_codegen(const uint32_t *program, size_t program_len, size_t n_cols, size_t n_constraints, std::string &out) {
-    out.clear();
-    uint32_t n_regs = 0;
-    if (const char *why = check_acc_program(program, program_len, n_cols, n_constraints, n_regs)) return why;
+// The statements of a validated program, for the loop body of either generator: one `const V n_p<k> / n_m<k> = <neighbour(off)>;`
+// per distinct non-zero offset (ordered: the text does not depend on where an offset first occurs), then one statement per
+// instruction; terminal(reg name, w1) writes the statement(s) of the entry's own ACC or STORE.
+template <class N, class T>
+std::string program_statements(const uint32_t *program, size_t program_len, N neighbour, T terminal) {
     auto num = [](uint64_t v) { return std::to_string(v); };
     auto nb_name = [&](int off) { return std::string(off < 0 ? "n_m" : "n_p") + num((uint64_t)(off < 0 ? -off : off)); };
-    std::set<int> offsets;                   // ordered: the text does not depend on where an offset first occurs
+    std::set<int> offsets;
     for (size_t pc = 0; pc < program_len; pc++)
         if ((program[2 * pc] & 0xffu) == TSTWO_AIR_OP_LOAD && program[2 * pc + 1] != 0) offsets.insert((int)program[2 * pc + 1]);
     std::string body;
-    for (int off : offsets)
-        body += "        const V " + nb_name(off) + " = neighbour_rows<W>(row, a.eval_log, a.log_expand, " + std::to_string(off) + ");\n";
+    for (int off : offsets) body += "        const V " + nb_name(off) + " = " + neighbour(std::to_string(off)) + ";\n";
     size_t name_of[TSTWO_AIR_PROGRAM_MAX_REGS] = {};     // the instruction whose result the register holds
-    size_t n_acc = 0;
     for (size_t pc = 0; pc < program_len; pc++) {
         const uint32_t w0 = program[2 * pc], w1 = program[2 * pc + 1];
         const uint32_t op = w0 & 0xffu, dst = (w0 >> 8) & 0xffu, x = w0 >> 16;
         auto reg = [&](uint32_t r) { return "t" + num(name_of[r]); };
-        if (op == TSTWO_AIR_OP_ACC) {
-            const std::string k = num(4 * n_acc);
-            body += "        accumulate<W>(acc, " + reg(x) + ", coeff[" + k + "], coeff[" + k + " + 1], coeff[" + k + " + 2], coeff[" + k + " + 3]);\n";
-            if ((++n_acc & 3) == 0) body += "        fold_all<W>(acc);\n";
-            continue;
-        }
         std::string rhs;
         switch (op) {
+            case TSTWO_AIR_OP_ACC: case TSTWO_AIR_OP_STORE:
+                body += terminal(reg(x), w1);
+                continue;
             case TSTWO_AIR_OP_LOAD:
                 if (w1 == 0) rhs = "load_rows<W>(col_at(tab, " + num(x) + "), row)";
                 else rhs = "load_at<W>(col_at(tab, " + num(x) + "), " + nb_name((int)w1) + ")";
@@ -149,6 +177,25 @@ inline const char *air_codegen(const uint32_t *program, size_t program_len, size
         body += "        const V t" + num(pc) + " = " + rhs + ";\n";
         name_of[dst] = pc;
     }
+    return body;
+}
+
+// The source text of a program's two kernels into `out`.  Returns the reason (the texts of tstwo_air_eval_program, without
+// its prefix) and leaves `out` empty for a program the interpreter would refuse.
+inline const char *air_codegen(const uint32_t *program, size_t program_len, size_t n_cols, size_t n_constraints, std::string &out) {
+    out.clear();
+    uint32_t n_regs = 0;
+    if (const char *why = check_acc_program(program, program_len, n_cols, n_constraints, n_regs)) return why;
+    auto num = [](uint64_t v) { return std::to_string(v); };
+    size_t n_acc = 0;
+    const std::string body = program_statements(
+        program, program_len, [](const std::string &off) { return "neighbour_rows<W>(row, a.eval_log, a.log_expand, " + off + ")"; },
+        [&](const std::string &reg, uint32_t) {
+            const std::string k = num(4 * n_acc);
+            std::string st = "        accumulate<W>(acc, " + reg + ", coeff[" + k + "], coeff[" + k + " + 1], coeff[" + k + " + 2], coeff[" + k + " + 3]);\n";
+            if ((++n_acc & 3) == 0) st += "        fold_all<W>(acc);\n";
+            return st;
+        });
     const std::string threads = num(kAirNativeThreads);
     out = air_native_prelude();
     out += "\n// " + num(program_len) + " instructions, " + num(n_cols) + " columns, " + num(n_constraints) + " constraints\n"
@@ -168,6 +215,38 @@ inline const char *air_codegen(const uint32_t *program, size_t program_len, size
     for (int w : {4, 1})
         out += "extern \"C\" __global__ void __attribute__((amdgpu_flat_work_group_size(1, " + threads + "))) " + (w == 4 ? kAirNativeKernelW4 : kAirNativeKernelW1) +
                "(airn::ColPtrs cols, airn::NativeArgs a) { air_native_rows<" + num((uint64_t)w) + ">(cols, a); }\n";
+    return nullptr;
+}
+
+// The same for a STORE program: the text of air_columns_w4 / air_columns_w1, which write n_out output columns on the trace domain
+// (k_air_columns).  Returns the reason (the texts of tstwo_air_eval_columns, without its prefix) and leaves `out` empty for a
+// program the interpreter would refuse.
+inline const char *air_columns_codegen(const uint32_t *program, size_t program_len, size_t n_cols, size_t n_out, std::string &out) {
+    out.clear();
+    uint32_t n_regs = 0;
+    if (const char *why = check_store_program(program, program_len, n_cols, n_out, n_regs)) return why;
+    auto num = [](uint64_t v) { return std::to_string(v); };
+    const std::string body = program_statements(
+        program, program_len, [](const std::string &off) { return "trace_neighbour_rows<W>(row, a.log, " + off + ")"; },
+        [&](const std::string &reg, uint32_t k) { return "        store_rows<W>(out_at(otab, " + num(k) + "), row, " + reg + ");\n"; });
+    const std::string threads = num(kAirNativeThreads);
+    out = air_native_prelude();
+    out += air_native_columns_prelude();
+    out += "\n// " + num(program_len) + " instructions, " + num(n_cols) + " columns, " + num(n_out) + " outputs\n"
+           "template <int W>\n"
+           "AIRN_DEV void air_columns_rows(const airn::ColPtrs &cols, const airn::ColPtrs &out, const airn::ColumnsArgs &a) {\n"
+           "    using namespace airn;\n"
+           "    typedef Rows<W> V;\n"
+           "    const k64 tab = col_table(cols);\n"
+           "    const k64 otab = out_table(out);\n"
+           "    for (u32 t = __builtin_amdgcn_workgroup_id_x() * " + threads + "u + __builtin_amdgcn_workitem_id_x(); t < a.n_rows / W; t += a.stride) {\n"
+           "        const u32 row = t * W;\n";
+    out += body;
+    out += "    }\n"
+           "}\n";
+    for (int w : {4, 1})
+        out += "extern \"C\" __global__ void __attribute__((amdgpu_flat_work_group_size(1, " + threads + "))) " + (w == 4 ? kAirColumnsKernelW4 : kAirColumnsKernelW1) +
+               "(airn::ColPtrs cols, airn::ColPtrs out, airn::ColumnsArgs a) { air_columns_rows<" + num((uint64_t)w) + ">(cols, out, a); }\n";
     return nullptr;
 }
 

@@ -1,5 +1,7 @@
 // air_native.h — between air.hip (argument checks, launch shape) and air_native.hip (hipRTC, the table of compiled kernels).
 #pragma once
+#include <cstddef>
+
 #include "common.h"
 
 namespace tstwo {
@@ -14,10 +16,23 @@ struct NativeArgs {
 };
 static_assert(sizeof(NativeArgs) == 128 && sizeof(ColPtrs) == 520, "the layouts the prelude text states");
 
-// What kernel `id` was compiled for; TSTWO_ERR_BAD_ARG "unknown air kernel" for an id that is not in the table.
-__attribute__((visibility("hidden"))) int air_native_shape(uint64_t id, u32 &n_cols, u32 &n_constraints);
+// The third argument of a generated columns kernel, behind the input and the output ColPtrs tables: field for field the
+// ColumnsArgs of csrc/air_native_columns_prelude.inc.
+struct ColumnsArgs { u32 n_rows, log, stride; };
+static_assert(sizeof(ColumnsArgs) == 12 && offsetof(ColumnsArgs, log) == 4 && offsetof(ColumnsArgs, stride) == 8,
+              "the layout the columns prelude text states");
+
+// What a table entry was compiled from: a constraint (ACC) program or a columns (STORE) program.
+enum AirKernelKind : u32 { kAirKernelConstraints = 0, kAirKernelColumns = 1 };
+
+// What kernel `id` was compiled for (n_terminal: its constraints, or its outputs); TSTWO_ERR_BAD_ARG "unknown air kernel" for an
+// id that is not in the table.
+__attribute__((visibility("hidden"))) int air_native_shape(uint64_t id, AirKernelKind &kind, u32 &n_cols, u32 &n_terminal);
 // Launches kernel `id` (W = 4 rows per lane when vec, else W = 1) with `grid` workgroups of kAirNativeThreads lanes on the
 // library's stream.
 __attribute__((visibility("hidden"))) int air_native_launch(uint64_t id, bool vec, unsigned grid, ColPtrs &cols, NativeArgs &args);
+
+// The same for a columns kernel: (cols, out, args).
+__attribute__((visibility("hidden"))) int air_native_launch_columns(uint64_t id, bool vec, unsigned grid, ColPtrs &cols, ColPtrs &out, ColumnsArgs &args);
 
 }  // namespace tstwo

@@ -3,7 +3,9 @@
 // register file, so the compiler keeps many column loads in flight), compiles it with hipRTC for the architecture of the current
 // device and loads the code object; tstwo_air_eval_compiled (air.hip) checks its arguments as tstwo_air_eval_program does and
 // launches it here.  A kernel is named by an id into the table below, never by a pointer: ids are handed out once and are not
-// reused, so a destroyed id, or one from before tstwo_shutdown, is simply not found.
+// reused, so a destroyed id, or one from before tstwo_shutdown, is simply not found.  tstwo_air_columns_compile does the same for
+// the STORE programs of tstwo_air_eval_columns (air_columns_codegen; tstwo_air_eval_columns_compiled launches them): one table, one
+// id counter, and every entry knows which of the two kinds it is.
 //
 // hipRTC is bound at first use (dlopen / dlsym, as comm.hip binds RCCL), not at link time: it brings the whole compiler
 // (libamd_comgr) into the process, which a prover that never compiles should not pay for at load, and a process that already
@@ -73,7 +75,8 @@ int load_hiprtc() {
 struct Kernel {
     hipModule_t module = nullptr;
     hipFunction_t fn[2] = {nullptr, nullptr};        // W = 4, W = 1
-    u32 n_cols = 0, n_constraints = 0;
+    AirKernelKind kind = kAirKernelConstraints;
+    u32 n_cols = 0, n_terminal = 0;                  // n_terminal: the constraints (ACC) or the outputs (STORE) it was compiled for
     u32 sgprs[2] = {0, 0};                           // from the code object's metadata (the runtime does not report them)
     size_t code_bytes = 0;
 };
@@ -117,22 +120,60 @@ int compile(const std::string &src, const std::string &arch, std::vector<char> &
     return rc;
 }
 
+const char *kernel_name(AirKernelKind kind, int w) {
+    return kind == kAirKernelColumns ? (w == 0 ? kAirColumnsKernelW4 : kAirColumnsKernelW1) : (w == 0 ? kAirNativeKernelW4 : kAirNativeKernelW1);
+}
+
+// compiles `src` for the current device, loads it and enters its two kernels into the table under a fresh id
+int compile_and_register(const std::string &src, AirKernelKind kind, size_t n_cols, size_t n_terminal, uint64_t *kernel_id) {
+    hipDeviceProp_t prop;
+    TSTWO_HIP(hipGetDeviceProperties(&prop, ctx().device));
+    std::vector<char> code;
+    if (int rc = compile(src, prop.gcnArchName, code)) return rc;
+    Kernel k;
+    k.kind = kind;
+    k.n_cols = (u32)n_cols;
+    k.n_terminal = (u32)n_terminal;
+    k.code_bytes = code.size();
+    TSTWO_HIP(hipModuleLoadData(&k.module, code.data()));
+    for (int w = 0; w < 2; w++) {
+        const hipError_t e = hipModuleGetFunction(&k.fn[w], k.module, kernel_name(kind, w));
+        if (e != hipSuccess) {
+            (void)hipModuleUnload(k.module);
+            return hip_fail(e, "hipModuleGetFunction");
+        }
+        (void)code_object_uint(code.data(), code.size(), kernel_name(kind, w), ".sgpr_count", k.sgprs[w]);
+    }
+    *kernel_id = g_next_id++;
+    g_kernels[*kernel_id] = k;
+    return TSTWO_OK;
+}
+
 }  // namespace
 
 namespace tstwo {
 
-int air_native_shape(uint64_t id, u32 &n_cols, u32 &n_constraints) {
+int air_native_shape(uint64_t id, AirKernelKind &kind, u32 &n_cols, u32 &n_terminal) {
     const Kernel *k = find(id);
     if (!k) return bad("unknown air kernel");
+    kind = k->kind;
     n_cols = k->n_cols;
-    n_constraints = k->n_constraints;
+    n_terminal = k->n_terminal;
     return TSTWO_OK;
 }
 
 int air_native_launch(uint64_t id, bool vec, unsigned grid, ColPtrs &cols, NativeArgs &args) {
     const Kernel *k = find(id);
-    if (!k) return bad("unknown air kernel");
+    if (!k || k->kind != kAirKernelConstraints) return bad("unknown air kernel");
     void *params[] = {&cols, &args};
+    TSTWO_HIP(hipModuleLaunchKernel(k->fn[vec ? 0 : 1], grid, 1, 1, kAirNativeThreads, 1, 1, 0, ctx().stream, params, nullptr));
+    return TSTWO_OK;
+}
+
+int air_native_launch_columns(uint64_t id, bool vec, unsigned grid, ColPtrs &cols, ColPtrs &out, ColumnsArgs &args) {
+    const Kernel *k = find(id);
+    if (!k || k->kind != kAirKernelColumns) return bad("unknown air kernel");
+    void *params[] = {&cols, &out, &args};
     TSTWO_HIP(hipModuleLaunchKernel(k->fn[vec ? 0 : 1], grid, 1, 1, kAirNativeThreads, 1, 1, 0, ctx().stream, params, nullptr));
     return TSTWO_OK;
 }
@@ -152,27 +193,16 @@ int tstwo_air_program_compile(const u32 *program, size_t program_len, size_t n_c
     if (stream_is_capturing()) return bad("air program compile: refused during graph capture (it loads a module, synchronously)");
     std::string src;
     if (const char *why = air_codegen(program, program_len, n_cols, n_constraints, src)) return bad(std::string("air program: ") + why);
-    hipDeviceProp_t prop;
-    TSTWO_HIP(hipGetDeviceProperties(&prop, ctx().device));
-    std::vector<char> code;
-    if (int rc = compile(src, prop.gcnArchName, code)) return rc;
-    Kernel k;
-    k.n_cols = (u32)n_cols;
-    k.n_constraints = (u32)n_constraints;
-    k.code_bytes = code.size();
-    TSTWO_HIP(hipModuleLoadData(&k.module, code.data()));
-    const char *const names[2] = {kAirNativeKernelW4, kAirNativeKernelW1};
-    for (int w = 0; w < 2; w++) {
-        const hipError_t e = hipModuleGetFunction(&k.fn[w], k.module, names[w]);
-        if (e != hipSuccess) {
-            (void)hipModuleUnload(k.module);
-            return hip_fail(e, "hipModuleGetFunction");
-        }
-        (void)code_object_uint(code.data(), code.size(), names[w], ".sgpr_count", k.sgprs[w]);
-    }
-    *kernel_id = g_next_id++;
-    g_kernels[*kernel_id] = k;
-    return TSTWO_OK;
+    return compile_and_register(src, kAirKernelConstraints, n_cols, n_constraints, kernel_id);
+}
+
+int tstwo_air_columns_compile(const u32 *program, size_t program_len, size_t n_cols, size_t n_out, uint64_t *kernel_id) {
+    TSTWO_REQUIRE_READY();
+    if (!program || !kernel_id) return bad("null host argument");
+    if (stream_is_capturing()) return bad("air columns compile: refused during graph capture (it loads a module, synchronously)");
+    std::string src;
+    if (const char *why = air_columns_codegen(program, program_len, n_cols, n_out, src)) return bad(std::string("air columns: ") + why);
+    return compile_and_register(src, kAirKernelColumns, n_cols, n_out, kernel_id);
 }
 
 int tstwo_air_kernel_info(uint64_t kernel_id, u32 info[TSTWO_AIR_KERNEL_INFO_WORDS]) {

@@ -307,7 +307,7 @@ def _m31(v) -> M31:
     raise TypeError(f"a multiplicity or relation value is an int, M31, QM31 or an expression here, not {type(v).__name__}")
 
 
-def derive_interaction_trace(eval_, main, preprocessed=()):
+def derive_interaction_trace(eval_, main, preprocessed=(), *, native: bool = False):
     """The interaction trace of a LogUp component from its `evaluate` alone: (HipCircleEvaluations, 4 per batch, claimed sum), the
     return of LogupTraceGenerator.finalize_last().  main, preprocessed: the component's columns (HipColumns, or arrays in storage
     order) in the order `evaluate` consumes them (next_trace_mask / next_interaction_mask, get_preprocessed_column(i)).
@@ -315,6 +315,7 @@ def derive_interaction_trace(eval_, main, preprocessed=()):
       every other expression of columns (x + 1, a * b - c, a value at another row, -multiplicity), as a multiplicity or as a value,
       is one output of a tstwo_air_eval_columns program (equal expressions share one; more than 64 take several calls);
       constant values fold into the denominator's constant as LookupElements.combine_columns folds them.
+    native=True (opt-in): every columns program runs as a native kernel (evaluate_columns(..., native=True)); same columns, same sum.
     Nothing is read back before finalize_last.  Raises ValueError for an `evaluate` without relation entries, an entry without a
     column among its values, a secure (QM31) multiplicity, more than 8 fractions in a batch or more than 16 column values."""
     from .constraint_framework import MAX_OUT, compile_columns, evaluate_columns
@@ -330,7 +331,7 @@ def derive_interaction_trace(eval_, main, preprocessed=()):
     outs = []
     for i in range(0, len(plan.exprs), MAX_OUT):
         chunk = plan.exprs[i:i + MAX_OUT]
-        outs += evaluate_columns(main + pre, log_size, compile_columns(chunk, len(main), len(pre)), len(chunk))
+        outs += evaluate_columns(main + pre, log_size, compile_columns(chunk, len(main), len(pre)), len(chunk), native=native)
 
     def resolve(r):
         kind, x = r
