@@ -66,6 +66,7 @@ struct Knobs {
     bool cfft_trace = false, cfft_sync = false;             // TSTWO_CFFT_TRACE / TSTWO_CFFT_SYNC
     // merkle.hip
     int merkle_cap = 32;               // TSTWO_MERKLE_CAP: workgroups per CU before lanes grid-stride
+    int merkle_pair_log = 19;          // TSTWO_MERKLE_PAIR_LOG: smallest leaf layer hashed together with the layer above it (k_merkle_leaf_pair)
     // fri.hip
     int fold_cap = 64;                 // TSTWO_FOLD_CAP: workgroups per CU of the fold kernels
 };

@@ -31,6 +31,7 @@ static Knobs read_knobs() {
     k.cfft_logta = num("TSTWO_CFFT_LOGTA", 0); if (k.cfft_logta < 12 || k.cfft_logta > 15) k.cfft_logta = 0;
     k.cfft_trace = on("TSTWO_CFFT_TRACE"); k.cfft_sync = on("TSTWO_CFFT_SYNC");
     k.merkle_cap = num("TSTWO_MERKLE_CAP", 32);
+    k.merkle_pair_log = num("TSTWO_MERKLE_PAIR_LOG", 19); if (k.merkle_pair_log < 1) k.merkle_pair_log = 1;
     k.fold_cap = num("TSTWO_FOLD_CAP", 64);
     return k;
 }

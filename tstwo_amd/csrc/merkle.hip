@@ -5,7 +5,7 @@
 // per wave.  Algorithmic bytes for a layer of n nodes: 4*C*n (+ 64*n children) read, 32*n written; the compression is VALU-bound
 // (~1.2k lane-ops per 64-byte block) — DESIGN.md §4.2 prices it against the integer-issue ceiling as well as the HBM roofline.
 //
-// Holds the layer kernels (k_merkle_layer, k_merkle_leaf_static, k_merkle_leaf4, k_merkle_inner[_set],
+// Holds the layer kernels (k_merkle_layer, k_merkle_leaf_static, k_merkle_leaf_pair, k_merkle_leaf4, k_merkle_inner[_set],
 // k_merkle_subtree2c); the latency path below 2^kUpLog nodes, a quad of lanes per node (k_merkle_upq, k_merkle_leaf4_upq) with
 // the channel step that can ride on a root (ChanHook, k_channel_mix_draw); the FRI commit tail (k_fri_tail) and the grind
 // (k_grind); then the host side — the ONE launch plan (launch_leaf_static, commit_column_free, commit_upper_levels under
@@ -13,6 +13,7 @@
 // launch_fri_tail, tstwo_channel_mix_root_draw_felt, tstwo_grind_blake2s.  Reading trees back is decommit.hip's.
 #include <string.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "blake2s.cuh"
@@ -174,6 +175,98 @@ __global__ void __launch_bounds__(256) k_merkle_leaf_static(HashColPtrs cols, Tr
     if (pnode < n_nodes) {
         out[2 * pnode] = make_uint4(hp[0], hp[1], hp[2], hp[3]);
         out[2 * pnode + 1] = make_uint4(hp[4], hp[5], hp[6], hp[7]);
+    }
+}
+
+// (1a) the same leaf layer AND the layer above it, when that layer has no columns: a lane owns the sibling rows 2i and 2i + 1, so
+// the parent's message (left digest || right digest) is in its registers when the second leaf is done — layer log - 1 costs
+// no load, no LDS and no launch of its own, and the column-free launches that follow read half as much.  One 8-byte load per
+// column fetches word 2i (row A) and word 2i + 1 (row B): 512 contiguous bytes per wave instruction, from the column's scalar
+// base plus one 32-bit byte offset (8 * pair < 2^32: the host takes this kernel for log_size <= 30 only).
+// Order of a pair: A.b0, B.b0, A.b1, B.b1, ..., parent — two live states.  The next block (the lane's next pair's first block behind
+// the last one) is requested in two halves: columns 0-7 before A's compression, columns 8-15 before B's, when A's 16 words are
+// dead — 32 message registers less at the widest point than a whole block ahead, and every load still has at least one
+// compression (the last half: B's and the parent's) to arrive.  Stores as in k_merkle_leaf_static, behind a compression's worth
+// of time before anything waits for them: the two leaf digests (64 contiguous bytes per lane) go out in front of the parent's
+// compression, whose message they are anyway; the parent (32 bytes) waits in hp for the next pair's first loads.  Default cache
+// policy for the digests (non-temporal digest stores measured 16-24 % slower); NT is the policy of the COLUMN loads, words that
+// are read exactly once.  Measured, non-temporal column loads lie inside the default policy's range (8 trees of 32 x 2^22, five
+// rounds alternating: merkle_ms 2.138-2.149 against 2.140-2.156, profiles/merkle_pair_parent_vs_branch.txt): no gain, so the
+// DEFAULT policy ships (TSTWO_MERKLE_PAIR_NT = 0 below); the parameter stays for the next measurement.
+// The 8-byte loads need every column 8-byte aligned: the host takes this kernel only then (leaf_takes_pair), the static leaf otherwise.
+// outs.t[tree] is layer log (2 * n_pairs digests); layer log - 1 lies 32 * n_pairs bytes below it in the same layers buffer.
+#ifndef TSTWO_MERKLE_PAIR_NT
+#define TSTWO_MERKLE_PAIR_NT 0
+#endif
+constexpr bool kPairNT = TSTWO_MERKLE_PAIR_NT != 0;
+template <int NBLK, bool NT>
+__global__ void __launch_bounds__(256) k_merkle_leaf_pair(HashColPtrs cols, TreeSet outs, size_t n_pairs) {
+    uint4 *__restrict__ leaf = outs.t[blockIdx.y];
+    uint4 *__restrict__ up = outs.t[blockIdx.y] - 2 * n_pairs;
+    const u32 col0 = blockIdx.y * (16 * NBLK);
+    // pair numbers fit 32 bits (n_pairs <= 2^29, the grid at most 2^21 lanes per tree): one register each, not two
+    const u32 np = (u32)n_pairs, stride = gridDim.x * blockDim.x, pair0 = blockIdx.x * blockDim.x + threadIdx.x;
+    const u32 rows = (np + stride - 1) / stride;
+    const u32 last_pair = np - 1;
+    u32 ca[16], cb[16], na[16], nb[16];                            // rows A / B: the block being compressed, the block in flight
+    auto words = [&](int k, u32 byte_off, u32 &a, u32 &b) {
+        const u32x2_t v = gload_as<NT>((const TSTWO_GLOBAL u32x2_t *)((const TSTWO_GLOBAL char *)cols.p[col0 + k] + byte_off));
+        a = v.x; b = v.y;
+    };
+    {
+        const u32 oc = min(pair0, last_pair) * 8u;
+#pragma unroll
+        for (int k = 0; k < 16; k++) words(k, oc, ca[k], cb[k]);
+    }
+    u32 hp[8] = {0, 0, 0, 0, 0, 0, 0, 0};                          // the parent digest waiting for its store
+    u32 ppair = np;                                                // its node of layer log - 1 (none yet)
+    for (u32 j = 0; j < rows; j++) {
+        const u32 pair = pair0 + j * stride;
+        const u32 pn = min(pair + stride, last_pair);                 // next pair of this lane (clamped: loads are never branched around)
+        const u32 pc = min(pair, last_pair);
+        Digest A = {{IV0 ^ 0x01010020u, IV1, IV2, IV3, IV4, IV5, IV6, IV7}}, B = A;
+        // one block of both rows; written out per block below, not as `#pragma unroll` over b: four blocks of two compressions are
+        // past the size up to which the compiler honours the pragma, and a rolled loop indexes the pointer table at run time
+        auto block = [&](auto bc) __attribute__((always_inline)) {
+            constexpr int b = decltype(bc)::value;
+            constexpr int bn = (b + 1) % NBLK;
+            // (the offset is made opaque in front of each half so that its zero-extension is selected in the block of the loads:
+            // extended in an earlier block it becomes a 64-bit VGPR offset, and every load gets a v_lshl_add_u64 and an address
+            // pair of its own)
+            u32 src = ((b + 1 < NBLK) ? pc : pn) * 8u;
+            asm volatile("" : "+v"(src));
+#pragma unroll
+            for (int k = 0; k < 8; k++) words(16 * bn + k, src, na[k], nb[k]);
+            if (b == 0 && ppair < np) {
+                up[2 * (size_t)ppair] = make_uint4(hp[0], hp[1], hp[2], hp[3]);
+                up[2 * (size_t)ppair + 1] = make_uint4(hp[4], hp[5], hp[6], hp[7]);
+            }
+            b2s_compress(A.w, ca, 64u * (b + 1), b == NBLK - 1);
+            asm volatile("" : "+v"(src));
+#pragma unroll
+            for (int k = 8; k < 16; k++) words(16 * bn + k, src, na[k], nb[k]);
+            b2s_compress(B.w, cb, 64u * (b + 1), b == NBLK - 1);
+#pragma unroll
+            for (int k = 0; k < 16; k++) { ca[k] = na[k]; cb[k] = nb[k]; }
+        };
+        block(std::integral_constant<int, 0>{});
+        if constexpr (NBLK > 1) block(std::integral_constant<int, 1>{});
+        if constexpr (NBLK > 2) block(std::integral_constant<int, 2>{});
+        if constexpr (NBLK > 3) block(std::integral_constant<int, 3>{});
+        if (pair < np) {
+            leaf[4 * (size_t)pair] = make_uint4(A.w[0], A.w[1], A.w[2], A.w[3]);
+            leaf[4 * (size_t)pair + 1] = make_uint4(A.w[4], A.w[5], A.w[6], A.w[7]);
+            leaf[4 * (size_t)pair + 2] = make_uint4(B.w[0], B.w[1], B.w[2], B.w[3]);
+            leaf[4 * (size_t)pair + 3] = make_uint4(B.w[4], B.w[5], B.w[6], B.w[7]);
+        }
+        const Digest top = hash_pair(A, B);
+#pragma unroll
+        for (int k = 0; k < 8; k++) hp[k] = top.w[k];
+        ppair = pair;
+    }
+    if (ppair < np) {
+        up[2 * (size_t)ppair] = make_uint4(hp[0], hp[1], hp[2], hp[3]);
+        up[2 * (size_t)ppair + 1] = make_uint4(hp[4], hp[5], hp[6], hp[7]);
     }
 }
 
@@ -662,6 +755,31 @@ int launch_leaf_static(const HashColPtrs &hp, size_t cols_per_tree, const TreeSe
     return TSTWO_OK;
 }
 
+// Whether the leaf layer of such trees is hashed together with the layer above it (k_merkle_leaf_pair): from 2^merkle_pair_log
+// leaves up (below that a tree is a handful of latency-bound launches and the static leaf keeps its lane per row), when layer
+// log_size - 1 has no columns of its own and every column is 8-byte aligned (the kernel's loads fetch two words; a column at an odd
+// word offset keeps the static leaf, which needs 4-byte alignment only).
+bool leaf_takes_pair(u32 log_size, bool columns_below, const u32 *const *cols, size_t n_cols) {
+    if (!(log_size >= 1 && log_size <= 30 && (int)log_size >= knobs().merkle_pair_log && !columns_below)) return false;
+    for (size_t i = 0; i < n_cols; i++)
+        if ((uintptr_t)cols[i] & 7) return false;
+    return true;
+}
+// Layers log_size (at leaf.t[tree]) and log_size - 1 of n_trees trees: one lane per pair of sibling leaves.
+int launch_leaf_pair(const HashColPtrs &hp, size_t cols_per_tree, const TreeSet &leaf, unsigned n_trees, u32 log_size) {
+    const size_t n_pairs = (size_t)1 << (log_size - 1);
+    const dim3 grid(layer_blocks(n_pairs, n_trees), n_trees);
+    hipStream_t stream = ctx().stream;
+    switch (cols_per_tree / 16) {
+        case 1: hipLaunchKernelGGL((k_merkle_leaf_pair<1, kPairNT>), grid, dim3(256), 0, stream, hp, leaf, n_pairs); break;
+        case 2: hipLaunchKernelGGL((k_merkle_leaf_pair<2, kPairNT>), grid, dim3(256), 0, stream, hp, leaf, n_pairs); break;
+        case 3: hipLaunchKernelGGL((k_merkle_leaf_pair<3, kPairNT>), grid, dim3(256), 0, stream, hp, leaf, n_pairs); break;
+        default: hipLaunchKernelGGL((k_merkle_leaf_pair<4, kPairNT>), grid, dim3(256), 0, stream, hp, leaf, n_pairs); break;
+    }
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
+}
+
 // Column-free layers log_child-1 .. log_stop of every tree of a set, the launch plan of every tree above its columns: layers of
 // at least 2^kUpLog nodes two per launch (k_merkle_subtree2c; measured for 32 x 2^22: 0.308 ms, against 0.313 for one launch per
 // layer and 0.326 / 0.332 for runs of 3 / 4 layers), a single leftover one on its own, the smaller ones by commit_upper_levels
@@ -808,6 +926,17 @@ int commit_tree(const u32 *const *cols, const u32 *log_sizes, size_t n_cols, uin
             lg = stop - 1;
             continue;
         }
+        if (!prev && !fold && (k == 16 || k == 32 || k == 48 || k == 64) && aligned16(dst) && leaf_takes_pair((u32)lg, has_cols((u32)lg - 1), lc, k)) {
+            // the static leaf's shapes, with the column-free layer above the leaves riding on the leaf launch
+            HashColPtrs hp;
+            for (size_t i = 0; i < k; i++) hp.p[i] = lc[i];
+            TreeSet leaf = {};
+            leaf.t[0] = (uint4 *)dst;
+            rc = launch_leaf_pair(hp, k, leaf, 1, (u32)lg);
+            prev = layers + 32 * (((size_t)1 << (lg - 1)) - 1);
+            lg -= 2;
+            continue;
+        }
         rc = commit_layer((u32)lg, prev, lc, k, dst, prev ? nullptr : fold);      // the leaf layer carries the fold
         prev = dst;
         lg--;
@@ -950,8 +1079,9 @@ int tstwo_merkle_commit_many(const tstwo_commit_request *reqs, size_t n_trees, u
             ts.t[r] = (uint4 *)reqs[r].layers;
             leaf.t[r] = (uint4 *)(reqs[r].layers + 32 * (((size_t)1 << lg) - 1));
         }
-        int rc = launch_leaf_static(hp, n_cols, leaf, (unsigned)n_trees, lg);
-        if (rc == TSTWO_OK) rc = commit_column_free(ts, (unsigned)n_trees, lg, 0, nullptr);
+        const bool pair = leaf_takes_pair(lg, false, hp.p, n_cols * n_trees);      // one log size: no columns below the leaves
+        int rc = pair ? launch_leaf_pair(hp, n_cols, leaf, (unsigned)n_trees, lg) : launch_leaf_static(hp, n_cols, leaf, (unsigned)n_trees, lg);
+        if (rc == TSTWO_OK) rc = commit_column_free(ts, (unsigned)n_trees, pair ? lg - 1 : lg, 0, nullptr);
         if (rc) return rc;
     }
     if (!roots) return TSTWO_OK;
