@@ -693,6 +693,45 @@ int tstwo_logup_finalize_last(uint32_t *const col[4], uint32_t log_size, uint32_
  * small-upload ring: refused during graph capture.  Asynchronous. */
 int tstwo_lookup_multiplicities(const uint32_t *const *cols, const size_t *lens, size_t n_cols, uint32_t log_range, uint32_t order,
                                 uint32_t *out, uint32_t *n_rejected);
+/* The same column for keys joined from several columns and rows that carry a weight (tstwo_amd/logup.py
+ * lookup_multiplicities_keyed): a table of tuples (a, b) -> bin a + 2^bits_a b, looked up by a component whose padded rows are
+ * switched off by an `enabler` column.  One group is one set of rows: n_limbs limb columns and, optionally, a weight column. */
+#define TSTWO_LOOKUP_MAX_LIMBS 4
+#define TSTWO_LOOKUP_MAX_GROUPS 64
+typedef struct {
+    const uint32_t *limbs[TSTWO_LOOKUP_MAX_LIMBS]; /* device columns of len words; limbs[0] = least significant; unused entries NULL */
+    uint32_t bits[TSTWO_LOOKUP_MAX_LIMBS];         /* limb j of a row must be < 2^bits[j]; 1 <= bits[j]; sum over the n_limbs used = log_range */
+    uint32_t n_limbs;                              /* 1 .. TSTWO_LOOKUP_MAX_LIMBS */
+    const uint32_t *weight;                        /* device column of len words, or NULL: every row weighs 1 */
+    size_t len;                                    /* rows: any length, 0 included; any 4-byte alignment of every column */
+} tstwo_lookup_group;
+/* groups: a host array of n_groups descriptors.  out: 2^log_range device words, overwritten completely.
+ * Key.  The key of row r of group g is sum_j limbs[j][r] << (bits[0] + ... + bits[j-1]).
+ * Result.  out[place(k)] = (sum of weight[r] over all groups and rows with key k) mod P, canonical in [0, P); place is
+ *   TSTWO_LOOKUP_ORDER_* as above.
+ * Weights.  Weight words are added as the unsigned integers they are (M31 values, so P - 1 is -1).  A word >= P is not rejected:
+ *   it is reduced with the sum.
+ * Accumulators are exact: sum(len) <= 2^31 - 2 rows of weight < 2^32 stay below 2^63, and a call with any weight column
+ *   accumulates in 64-bit integers (8 bytes per bin from the library's allocator for the duration of the call, reduced mod P by a
+ *   second kernel; a table too large for that block fails with TSTWO_ERR_HIP and the allocator's text, before anything is zeroed
+ *   or launched).  A call whose groups all have weight NULL counts in 32-bit words, which the row limit keeps canonical.
+ * Zero weight.  A row whose weight is 0 is skipped before anything else: its limbs are not range-checked and it is counted
+ *   nowhere, n_rejected included.  This is what gating means: padding may hold anything.
+ * Rejection.  A row with non-zero weight is rejected when any limb is >= 2^bits[j]: it is counted in no bin and never forms an
+ *   index.  Rejected rows add 1 each, per row and not per limb, to *n_rejected (a device word, or NULL).
+ * Limits (TSTWO_ERR_BAD_ARG, text "lookup: ..." in tstwo_last_error, before anything is launched or zeroed):
+ *   1 <= n_groups <= TSTWO_LOOKUP_MAX_GROUPS ("1 to 64 groups"), 1 <= n_limbs <= TSTWO_LOOKUP_MAX_LIMBS ("1 to 4 limbs per
+ *   group"), every bits[j] >= 1 ("every limb needs at least 1 bit"), every group's sum of bits = log_range ("the bits of every
+ *   group must add up to log_range"), 1 <= log_range <= TSTWO_LOOKUP_MAX_LOG ("log_range must be 1 to 28"), sum(len) <= 2^31 - 2
+ *   ("more than 2^31 - 2 rows"), order 0 or 1 ("order must be 0 (natural) or 1 (coset)"), no null pointer except weight and
+ *   n_rejected ("null ..."), out overlaps no limb or weight column ("out overlaps a limb or weight column") and does not
+ *   contain n_rejected ("n_rejected lies inside out").
+ * Integer atomics only: the result is the same bit for bit on every run.  The descriptor table is uploaded through the
+ * small-upload ring: refused during graph capture.  Asynchronous, with one exception: a call with a weight column returns its
+ * accumulator block through tstwo_free, which in TSTWO_ALLOC_DIRECT mode synchronises the stream before hipFree (pool and async
+ * modes release in stream order and do not wait). */
+int tstwo_lookup_multiplicities_keyed(const tstwo_lookup_group *groups, size_t n_groups, uint32_t log_range, uint32_t order,
+                                      uint32_t *out, uint32_t *n_rejected);
 /* out[coset_pos(k)] = k for k < 2^log_size: the preprocessed column of a range-check table (range_check_table_column).
  * 1 <= log_size <= TSTWO_LOOKUP_MAX_LOG ("lookup: log_size must be 1 to 28").  Asynchronous; refused during graph capture. */
 int tstwo_coset_iota(uint32_t *out, uint32_t log_size);

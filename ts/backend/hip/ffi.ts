@@ -133,6 +133,7 @@ const lib = dlopen(process.env.TSTWO_HIP_LIB ?? "libtstwo_hip.so", {
   tstwo_logup_column: { args: [P, u64, P, u32, P], returns: i32 },
   tstwo_logup_finalize_last: { args: [P, u32, P], returns: i32 },
   tstwo_lookup_multiplicities: { args: [P, P, u64, u32, u32, u64, u64], returns: i32 },
+  tstwo_lookup_multiplicities_keyed: { args: [P, u64, u32, u32, u64, u64], returns: i32 },
   tstwo_coset_iota: { args: [u64, u32], returns: i32 },
 });
 

@@ -41,10 +41,11 @@ from .air import (ColumnAccumulator, ComponentProvers, Components, DomainEvaluat
                   PointEvaluationAccumulator, Trace, TraceLocationAllocator, coset_vanishing, generate_wide_fib_trace)
 from .constraint_framework import (FrameworkComponent, MulAddComponent, MulAddEval, PermutationEval,  # noqa: F401
                                    RangeCheckTableEval, RangeCheckValuesEval, RelationEvaluator, StateMachineEval,
-                                   WideFibonacciComponent, WideFibonacciEval, compile_columns, evaluate_columns,
-                                   state_machine_trace)
-from .logup import (INTERACTION_TRACE_IDX, LogupColGenerator, LogupTraceGenerator, LookupElements,  # noqa: F401
-                    RelationEntry, coset_iota, derive_interaction_trace, deriveInteractionTrace, lookup_multiplicities)
+                                   WideFibonacciComponent, WideFibonacciEval, XorTableEval, XorValuesEval, compile_columns,
+                                   evaluate_columns, state_machine_trace, xor_multiplicities_device, xor_table_columns)
+from .logup import (INTERACTION_TRACE_IDX, LogupColGenerator, LogupTraceGenerator, LookupElements, LookupGroup,  # noqa: F401
+                    RelationEntry, coset_iota, derive_interaction_trace, deriveInteractionTrace, lookup_multiplicities,
+                    lookup_multiplicities_keyed)
 from .prover import (ConstraintsNotSatisfied, InvalidLogupSum, InvalidStructure, OodsNotMatching, StarkProof, prove,  # noqa: F401
                      verify)
 

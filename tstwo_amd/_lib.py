@@ -61,6 +61,11 @@ class LogupFrac(C.Structure):
                 ("constant", C.c_uint32 * 4)]
 
 
+class LookupGroup(C.Structure):
+    """tstwo_lookup_group (include/tstwo_hip.h)."""
+    _fields_ = [("limbs", vp * 4), ("bits", C.c_uint32 * 4), ("n_limbs", C.c_uint32), ("weight", vp), ("len", C.c_size_t)]
+
+
 _SIGS = {
     "tstwo_init": [C.c_int],
     "tstwo_shutdown": [],
@@ -185,6 +190,7 @@ _SIGS = {
     "tstwo_logup_column": [C.POINTER(LogupFrac), C.c_size_t, C.POINTER(vp), C.c_uint32, P4],
     "tstwo_logup_finalize_last": [P4, C.c_uint32, u32p],
     "tstwo_lookup_multiplicities": [C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp],
+    "tstwo_lookup_multiplicities_keyed": [C.POINTER(LookupGroup), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp],
     "tstwo_coset_iota": [vp, C.c_uint32],
 }
 ALLOC_POOL, ALLOC_DIRECT, ALLOC_ASYNC, ALLOC_POISON = 0, 1, 2, 0x10

@@ -1326,3 +1326,75 @@ def range_check_values_interaction_trace(log_n_rows: int, v0, v1, lookup_element
     col.write_frac(1, lookup_elements.combine_columns([_col(v1)]))
     col.finalize_col()
     return gen.finalize_last()
+
+
+class XorTableEval:
+    """The table side of a lookup with a tuple key: XOR of two log_bits-bit words.  Preprocessed columns 0..2 hold (a, b, a ^ b)
+    of k = a + 2^log_bits b at coset row k (xor_table_columns), the main column `multiplicity` says how often the values
+    components use the row; entry (-multiplicity, [a, b, c]), finalize_logup().  Degree 2."""
+
+    def __init__(self, log_bits: int, lookup_elements: LookupElements):
+        self.log_bits, self.lookup_elements = log_bits, lookup_elements
+
+    def log_size(self) -> int:
+        return 2 * self.log_bits
+
+    def max_constraint_log_degree_bound(self) -> int:
+        return 2 * self.log_bits + 1
+
+    def evaluate(self, eval):
+        a, b, c = (eval.get_preprocessed_column(i) for i in range(3))
+        multiplicity = eval.next_trace_mask()
+        eval.add_to_relation(RelationEntry(self.lookup_elements, -multiplicity, [a, b, c]))
+        eval.finalize_logup()
+        return eval
+
+    logSize = log_size
+    maxConstraintLogDegreeBound = max_constraint_log_degree_bound
+
+
+class XorValuesEval:
+    """The values side: main columns a, b, c, enabler.  A component whose row count is no power of two pads its trace and
+    switches the padded rows off: enabler is 0 or 1 (constraint enabler (1 - enabler) = 0), the entry is (enabler, [a, b, c]),
+    finalize_logup(), so a padded row may hold anything.  Degree 2."""
+
+    def __init__(self, log_n_rows: int, lookup_elements: LookupElements):
+        self.log_n_rows, self.lookup_elements = log_n_rows, lookup_elements
+
+    def log_size(self) -> int:
+        return self.log_n_rows
+
+    def max_constraint_log_degree_bound(self) -> int:
+        return self.log_n_rows + 1
+
+    def evaluate(self, eval):
+        a, b, c, enabler = (eval.next_trace_mask() for _ in range(4))
+        eval.add_constraint(enabler * (1 - enabler))
+        eval.add_to_relation(RelationEntry(self.lookup_elements, enabler, [a, b, c]))
+        eval.finalize_logup()
+        return eval
+
+    logSize = log_size
+    maxConstraintLogDegreeBound = max_constraint_log_degree_bound
+
+
+def xor_table_columns(log_bits: int):
+    """The preprocessed columns of XorTableEval: (a, b, a ^ b) of k = a + 2^log_bits b at coset row k (numpy uint32, storage order)."""
+    import numpy as np
+    k = np.arange(1 << (2 * log_bits), dtype=np.uint32)
+    a, b = k & ((1 << log_bits) - 1), k >> log_bits
+    pos = _coset_positions(2 * log_bits)
+    cols = []
+    for v in (a, b, a ^ b):
+        c = np.empty(k.size, dtype=np.uint32)
+        c[pos] = v
+        cols.append(c)
+    return cols
+
+
+def xor_multiplicities_device(log_bits: int, a, b, enabler, check: bool = True):
+    """The multiplicity column of XorTableEval counted on the device (logup.lookup_multiplicities_keyed, coset order): row
+    a + 2^log_bits b receives the sum of `enabler` over the rows that hold (a, b); each limb is checked against log_bits on the
+    enabled rows only.  c is not part of the key: a wrong c is the proof's business.  HipColumns stay where they are."""
+    from .logup import LookupGroup, lookup_multiplicities_keyed
+    return lookup_multiplicities_keyed([LookupGroup([(a, log_bits), (b, log_bits)], weight=enabler)], order="coset", check=check)

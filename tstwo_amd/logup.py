@@ -179,6 +179,61 @@ def lookup_multiplicities(log_range: int, *value_columns, order: str = "coset", 
     return out
 
 
+MAX_LIMBS, MAX_GROUPS = 4, 64           # include/tstwo_hip.h TSTWO_LOOKUP_MAX_LIMBS / _GROUPS
+
+
+class LookupGroup:
+    """One tstwo_lookup_group: rows whose key is joined from limb columns, limbs = [(column, bits), ...] with the least
+    significant limb first (limb j of a row must be < 2^bits_j), and an optional weight column (None: every row weighs 1; a row
+    of weight 0 is skipped unchecked).  Columns are HipColumns, which stay where they are, or arrays, which are uploaded; all of
+    one length."""
+
+    def __init__(self, limbs, weight=None):
+        limbs = list(limbs)
+        if not 1 <= len(limbs) <= MAX_LIMBS:
+            raise ValueError(f"1 to {MAX_LIMBS} limbs per group")
+        self.limbs = [c if isinstance(c, HipColumn) else HipColumn(c) for c, _ in limbs]
+        self.bits = [int(b) for _, b in limbs]
+        if any(b < 1 for b in self.bits):
+            raise ValueError("every limb needs at least 1 bit")
+        self.weight = weight if weight is None or isinstance(weight, HipColumn) else HipColumn(weight)
+        self.len = self.limbs[0].len()
+        if any(c.len() != self.len for c in self.limbs + ([self.weight] if self.weight is not None else [])):
+            raise ValueError("the columns of a group must have one length")
+
+    @property
+    def log_range(self) -> int:
+        return sum(self.bits)
+
+
+def lookup_multiplicities_keyed(groups, order: str = "coset", check: bool = True) -> HipColumn:
+    """tstwo_lookup_multiplicities_keyed: the column of 2^log_range sums, log_range = the groups' common bit sum; the sum of
+    k = a_0 + 2^bits_0 a_1 + ... is the sum of the weights of the rows with limbs (a_0, a_1, ...) over `groups` (LookupGroups),
+    mod P.  order as for lookup_multiplicities.  check=True reads one word back and raises ValueError when a row of non-zero
+    weight has a limb outside its width; check=False reads nothing back and skips such rows."""
+    if order not in ORDERS:
+        raise ValueError(f"order is 'natural' or 'coset', not {order!r}")
+    groups = list(groups)
+    if not 1 <= len(groups) <= MAX_GROUPS:
+        raise ValueError(f"1 to {MAX_GROUPS} groups")
+    log_range = groups[0].log_range
+    if any(g.log_range != log_range for g in groups):
+        raise ValueError("the bits of every group must add up to the same log_range")
+    if not 1 <= log_range <= MAX_LOG:
+        raise ValueError(f"log_range must be 1 to {MAX_LOG}")
+    descs = (L.LookupGroup * len(groups))()
+    for d, g in zip(descs, groups):
+        for j, (c, b) in enumerate(zip(g.limbs, g.bits)):
+            d.limbs[j], d.bits[j] = c.ptr, b
+        d.n_limbs, d.weight, d.len = len(g.limbs), g.weight.ptr if g.weight is not None else None, g.len
+    out = HipColumn.uninitialized(1 << log_range)
+    rejected = HipColumn.uninitialized(1) if check else None
+    L.call("tstwo_lookup_multiplicities_keyed", descs, len(groups), log_range, ORDERS[order], out.ptr, rejected.ptr if check else None)
+    if check and int(rejected.to_numpy()[0]):
+        raise ValueError("a checked value lies outside the range")
+    return out
+
+
 def coset_iota(log_size: int) -> HipColumn:
     """tstwo_coset_iota: value k at the storage position of coset row k (the preprocessed column of a range-check table)."""
     out = HipColumn.uninitialized(1 << log_size)
