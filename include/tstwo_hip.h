@@ -386,6 +386,29 @@ int tstwo_poseidon252_merkle_commit(const uint32_t *const *cols, const uint32_t 
  * pow_bits trailing zeros as channel/poseidon.ts:209-229 counts them: the first 16 bytes of the big-endian encoding read as a
  * little-endian u128, so counting starts at bit 248 of the element.  digest: host, 8 limbs, canonical.  Synchronises. */
 int tstwo_grind_poseidon252(const uint32_t digest[8], uint32_t pow_bits, uint64_t start_nonce, uint64_t *nonce_out);
+/* The same hashes with 8 lanes per hash instead of one (csrc/felt252_coop.cuh): a lone permutation, or a layer too small to fill
+ * the device, waits for one lane's instruction stream in the entries above and for a fraction of it here.
+ * tstwo_poseidon252_hash_many_coop: poseidonHashMany (@scure/starknet) with exactly the contract of tstwo_poseidon252_hash_many. */
+int tstwo_poseidon252_hash_many_coop(const uint32_t *in, size_t n_msgs, uint32_t felts_per_msg, uint32_t *out);
+/* CpuPoseidon252MerkleOps.commitOnLayer (backend/cpu/poseidon252.ts:44-78) with exactly the contract of
+ * tstwo_poseidon252_merkle_commit_layer: any n_cols, prev may be NULL, one block per 8 columns. */
+int tstwo_poseidon252_merkle_commit_layer_coop(uint32_t log_size, const uint8_t *prev, const uint32_t *const *cols,
+                                               size_t n_cols, uint8_t *out);
+/* Poseidon252Channel on the device (channel/poseidon.ts:122-360; mix_root: vcs/poseidon252_merkle.ts:146-178).  chan = 10 words
+ * of device memory: the digest's 8 limbs (canonical), n_challenges, n_sent — the shape of the Blake2s device channel.
+ * root != NULL: digest = hash_many([digest, root]) of the element at `root` (device memory, e.g. byte 0 of a Poseidon tree's
+ * layers buffer), n_challenges += 1, n_sent = 0.  felt != NULL: draw_felt into the 4 words at `felt` (device memory): the first
+ * four of the eight 31-bit slices of poseidonHash(digest, n_sent), least significant first, each reduced as M31.reduce does;
+ * n_sent += 1.  One wave.  Asynchronous: later calls on the stream see the results; nothing reaches the host. */
+int tstwo_poseidon252_channel_mix_root_draw_felt(uint32_t *chan, const uint8_t *root, uint32_t *felt);
+/* FriProver.commit's whole layer loop (commitInnerLayers, fri.ts:676-716) over Poseidon252 trees and the Poseidon252 device
+ * channel: the arguments, outputs, ownership, error texts and failure behaviour of tstwo_fri_commit_layers (every check before
+ * the first allocation; on failure nothing is returned, nothing leaks, the channel and the alphas are as they were).  chan: the
+ * 10 words of tstwo_poseidon252_channel_mix_root_draw_felt.  Trees have the tstwo_merkle_commit layout. */
+int tstwo_fri_commit_layers_poseidon252(const uint32_t *const *circle_cols, const uint32_t *col_logs, size_t n_columns,
+                                        const uint32_t *itw, uint32_t tw_log, uint32_t log_last_layer_size, uint32_t *chan,
+                                        uint32_t *alphas, size_t alphas_cap, uint8_t **first_tree, tstwo_fri_layer_out *out,
+                                        size_t out_cap, size_t *n_out);
 
 /* ---------------------------------------------------------------- QuotientOps
  * accumulateQuotients row loop (backend/cpu/quotients.ts:52-116,160-178) with the per-batch constants

@@ -120,6 +120,10 @@ const lib = dlopen(process.env.TSTWO_HIP_LIB ?? "libtstwo_hip.so", {
   tstwo_poseidon252_merkle_commit_layer: { args: [u32, u64, P, u64, u64], returns: i32 },
   tstwo_poseidon252_merkle_commit: { args: [P, P, u64, u64, P], returns: i32 },
   tstwo_grind_poseidon252: { args: [P, u32, u64, P], returns: i32 },
+  tstwo_poseidon252_hash_many_coop: { args: [u64, u64, u32, u64], returns: i32 },
+  tstwo_poseidon252_merkle_commit_layer_coop: { args: [u32, u64, P, u64, u64], returns: i32 },
+  tstwo_poseidon252_channel_mix_root_draw_felt: { args: [u64, u64, u64], returns: i32 },
+  tstwo_fri_commit_layers_poseidon252: { args: [P, P, u64, u64, u32, u32, u64, u64, u64, P, P, u64, P], returns: i32 },
   tstwo_air_wide_fib_trace: { args: [u64, u64, u32, P, u64], returns: i32 },
   tstwo_air_constraint_quotients: { args: [u32, P, u64, u32, u32, P, u64, P, P], returns: i32 },
   tstwo_air_eval_program: { args: [P, u64, u32, u32, P, u64, P, u64, P, P], returns: i32 },

@@ -534,6 +534,25 @@ export class HipPoseidon252MerkleProver {
   }
 }
 
+/** Poseidon252Channel on the device (channel/poseidon.ts:122-360): `chan` = 10 words (8 digest limbs, n_challenges, n_sent).
+ *  rootDev != 0n: mix_root of the element there (byte 0 of a Poseidon tree); feltDev != 0n: draw_felt into the 4 words there.
+ *  Nothing reaches the host. */
+export function poseidon252ChannelMixRootDrawFelt(chan: DeviceBuffer, rootDev: bigint, feltDev: bigint): void {
+  check(hip.tstwo_poseidon252_channel_mix_root_draw_felt(chan.dev, rootDev, feltDev));
+}
+
+/** poseidonHashMany of nMsgs messages of feltsPerMsg elements each (8 limbs per element, device memory) with 8 lanes per message:
+ *  the contract of tstwo_poseidon252_hash_many, for batches too small to fill the device. */
+export function poseidon252HashManyCoop(input: DeviceBuffer, nMsgs: number, feltsPerMsg: number, out: DeviceBuffer): void {
+  check(hip.tstwo_poseidon252_hash_many_coop(input.dev, BigInt(nMsgs), feltsPerMsg, out.dev));
+}
+
+/** commitOnLayer over device buffers with 8 lanes per node (tstwo_poseidon252_merkle_commit_layer_coop): `prev` = the 2^(logSize+1)
+ *  child hashes or undefined, `out` = 2^logSize * 32 bytes. */
+export function poseidon252CommitLayerCoop(logSize: number, prev: DeviceBuffer | undefined, columns: readonly HipColumn[], out: DeviceBuffer): void {
+  check(hip.tstwo_poseidon252_merkle_commit_layer_coop(logSize, prev ? prev.dev : 0n, ptr(ptrs(columns.map((c) => c.dev))), BigInt(columns.length), out.dev));
+}
+
 /** GrindOps.grind (backend/cpu/grind.ts:31-42) on the device, dispatched on the channel: the first nonce the sequential loop finds. */
 export function grind(channel: Blake2sChannel | Poseidon252Channel, powBits: number): number {
   ensureInit();
@@ -611,7 +630,8 @@ export interface HipFriCommittedLayer { logSize: number; columns: HipSecureColum
  *  `alphas` receives the drawn challenges (16 bytes each).  Every buffer returned was allocated by the library (tstwo_malloc)
  *  and is owned by the returned objects. */
 export function friCommitLayers(circleEvals: readonly HipSecureColumn[], itwiddles: HipColumn, twLog: number, logLastLayerSize: number,
-                                chan: DeviceBuffer, alphas: DeviceBuffer): { firstTree: HipMerkleProver; layers: HipFriCommittedLayer[] } {
+                                chan: DeviceBuffer, alphas: DeviceBuffer,
+                                poseidon252 = false): { firstTree: HipMerkleProver; layers: HipFriCommittedLayer[] } {
   const logs = circleEvals.map((e) => Math.log2(e.len()));
   const firstLog = logs[0]! - 1;
   if (firstLog < logLastLayerSize) throw new Error("last layer domain size mismatch");
@@ -619,7 +639,9 @@ export function friCommitLayers(circleEvals: readonly HipSecureColumn[], itwiddl
   const outs = new BigUint64Array(6 * cap);        // packed tstwo_fri_layer_out: { u32 log_size (+ pad); u32 *cols[4]; u8 *layers }
   const first = new BigUint64Array(1), nOut = new BigUint64Array(1);
   const cols = ptrs(circleEvals.flatMap((e) => e.columns.map((c) => c.dev))), lg = u32s(logs);
-  check(hip.tstwo_fri_commit_layers(ptr(cols), ptr(lg), BigInt(circleEvals.length), itwiddles.dev, twLog, logLastLayerSize, chan.dev,
+  // poseidon252: Poseidon252 trees and `chan` in the layout of poseidon252ChannelMixRootDrawFelt; same arguments, same outputs
+  const entry = poseidon252 ? hip.tstwo_fri_commit_layers_poseidon252 : hip.tstwo_fri_commit_layers;
+  check(entry(ptr(cols), ptr(lg), BigInt(circleEvals.length), itwiddles.dev, twLog, logLastLayerSize, chan.dev,
     alphas.dev, BigInt(Math.floor(alphas.nbytes / 16)), ptr(first), ptr(outs), BigInt(cap), ptr(nOut)));
   const layers: HipFriCommittedLayer[] = [];
   for (let i = 0; i < Number(nOut[0]); i++) {

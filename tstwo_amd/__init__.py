@@ -35,7 +35,7 @@ from .quotients import (ColumnSampleBatch, accumulate, accumulateQuotients, gene
                         quotientConstants)
 from .vcs import (Blake2sMerkleChannel, Blake2sMerkleHasher, DeviceHashLayer, HipMerkleOps, MerkleDecommitment,  # noqa: F401
                   MerkleProver, MerkleVerifier)
-from .poseidon import (DeviceFeltLayer, FieldElement252, HipPoseidon252MerkleOps, Poseidon252Channel,  # noqa: F401
+from .poseidon import (DeviceFeltLayer, DevicePoseidon252Channel, FieldElement252, HipPoseidon252MerkleOps, Poseidon252Channel,  # noqa: F401
                        Poseidon252MerkleChannel, Poseidon252MerkleHasher, Poseidon252MerkleProver)
 from .air import (ColumnAccumulator, ComponentProvers, Components, DomainEvaluationAccumulator,  # noqa: F401
                   PointEvaluationAccumulator, Trace, TraceLocationAllocator, coset_vanishing, generate_wide_fib_trace)

@@ -177,6 +177,11 @@ _SIGS = {
     "tstwo_poseidon252_merkle_commit_layer": [C.c_uint32, vp, C.POINTER(vp), C.c_size_t, vp],
     "tstwo_poseidon252_merkle_commit": [C.POINTER(vp), u32p, C.c_size_t, vp, u8p],
     "tstwo_grind_poseidon252": [u32p, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)],
+    "tstwo_poseidon252_hash_many_coop": [vp, C.c_size_t, C.c_uint32, vp],
+    "tstwo_poseidon252_merkle_commit_layer_coop": [C.c_uint32, vp, C.POINTER(vp), C.c_size_t, vp],
+    "tstwo_poseidon252_channel_mix_root_draw_felt": [vp, vp, vp],
+    "tstwo_fri_commit_layers_poseidon252": [C.POINTER(vp), u32p, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, C.POINTER(vp),
+                                            C.POINTER(FriLayerOut), C.c_size_t, C.POINTER(C.c_size_t)],
     "tstwo_air_wide_fib_trace": [vp, vp, C.c_uint32, C.POINTER(vp), C.c_size_t],
     "tstwo_air_constraint_quotients": [C.c_uint32, C.POINTER(vp), C.c_size_t, C.c_uint32, C.c_uint32, u32p, C.c_size_t, u32p, P4],
     "tstwo_air_eval_program": [C.POINTER(vp), C.c_size_t, C.c_uint32, C.c_uint32, u32p, C.c_size_t, u32p, C.c_size_t, u32p, P4],

@@ -235,6 +235,9 @@ int merkle_commit_then_channel(const u32 *const *cols, const u32 *log_sizes, siz
 // merkle.hip: the FRI commit's last layers (2^log0 <= 2^9 rows and below) in one single-workgroup launch
 int launch_fri_tail(u32 *const (*eval)[4], uint8_t *const *trees, u32 n_layers, u32 log0, const u32 *itw, u32 tw_log, u32 *chan, u32 *alphas,
                     const u32 *const *pre, const u32 *pre_alpha);
+// fri.hip: fold_circle_into_line with tree twiddles and the alpha in device memory; accum = false writes dst instead of updating it
+__attribute__((visibility("hidden"))) int fri_fold_circle_dev(u32 *const dst[4], size_t dst_len, const u32 *const src[4], u32 log_n, const u32 *itw,
+                                                              u32 tw_log, const u32 *alpha_dev, bool accum);
 // decommit.hip: the roots (digest 0 of each of the n_trees layers buffers, device memory) into host memory: one gather launch, one
 // read-back.  Hidden, unlike the older internal entries above, which are exported only because nothing ever hid them: the
 // library's dynamic symbol list is part of what callers see and does not grow for a function no caller may use.

@@ -288,6 +288,13 @@ int fold_circle(u32 *const dst[4], size_t dst_len, const u32 *const src[4], u32 
 
 }  // namespace
 
+// fold_circle with the alpha in device memory, written (accum = false) or accumulated: what a commit loop in another file needs
+// (poseidon_coop.hip) and the C ABI does not say — tstwo_fri_fold_circle_into_line_dev always accumulates
+int tstwo::fri_fold_circle_dev(u32 *const dst[4], size_t dst_len, const u32 *const src[4], u32 log_n, const u32 *itw, u32 tw_log,
+                               const u32 *alpha_dev, bool accum) {
+    return fold_circle(dst, dst_len, src, log_n, nullptr, {itw, true, tw_log}, {alpha_dev, true}, accum);
+}
+
 extern "C" {
 
 int tstwo_fri_fold_line_tw(const u32 *const in[4], u32 log_n, const u32 *inv_x, const u32 alpha[4], u32 *const out[4]) {

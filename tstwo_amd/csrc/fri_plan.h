@@ -28,7 +28,10 @@ struct FriStep {
 constexpr uint32_t kFriTailLog = 9;          // k_fri_tail holds layers of at most 2^9 rows
 
 // The steps of a commit, in launch order.  Returns the reason (a TSTWO_ERR_BAD_ARG) and no steps for an input that has no schedule.
-inline const char *fri_plan(const uint32_t *col_logs, size_t n_columns, uint32_t log_last_layer_size, std::vector<FriStep> &steps) {
+// fused = false is the schedule of tstwo_fri_commit_layers_poseidon252: FOLD_COMMIT and TAIL hash Blake2s leaves inside the fold, so
+// a commit over Poseidon trees takes the unfused kinds only — every layer above the last is a COMMIT, every fold a FOLD_LINE.
+inline const char *fri_plan(const uint32_t *col_logs, size_t n_columns, uint32_t log_last_layer_size, std::vector<FriStep> &steps,
+                            bool fused = true) {
     steps.clear();
     if (!n_columns) return "no columns";
     for (size_t i = 0; i < n_columns; i++) {
@@ -44,7 +47,7 @@ inline const char *fri_plan(const uint32_t *col_logs, size_t n_columns, uint32_t
     bool committed = false;                             // the fold that produced `layer` hashed it into its tree already
     while (log > last) {
         // every remaining layer fits one workgroup's LDS and no column is left: one launch does tree / mix / draw / fold for all of them
-        if (!committed && log <= kFriTailLog && nxt == n_columns) {
+        if (fused && !committed && log <= kFriTailLog && nxt == n_columns) {
             steps.push_back({FriStep::TAIL, layer, log, 0, 0, layer + 1, log - last, false});
             break;
         }
@@ -53,7 +56,7 @@ inline const char *fri_plan(const uint32_t *col_logs, size_t n_columns, uint32_t
         layer++, log--;
         const bool joins = nxt < n_columns && col_logs[nxt] - 1 == log;
         const bool tail_next = log <= kFriTailLog && nxt + (joins ? 1 : 0) == n_columns;
-        if (log == last || joins) {                     // never committed, or not complete before the column is in
+        if (log == last || joins || !fused) {          // never committed, or not complete before the column is in
             steps.push_back({FriStep::FOLD_LINE, layer, log, 0, layer, 0, 0, false});
         } else if (tail_next) {                         // the tail launch folds the layer on its way in
             steps.push_back({FriStep::TAIL, layer, log, 0, layer, layer + 1, log - last, true});

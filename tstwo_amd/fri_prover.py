@@ -280,6 +280,12 @@ class FriInnerLayerProver:
 FriLayer = FriInnerLayerProver
 
 
+# FriProver.commit over Poseidon252 with device_channel=None: the one-call commit (True) or the host transcript (False).  Decided by
+# measurement (profiles/poseidon_coop.jsonl): one column at circle log 16 and 20, the one-call commit against the host
+# transcript of the commit before it existed — faster beyond the spread at both, so it is the default.
+POSEIDON252_DEVICE_TRANSCRIPT = True
+
+
 class _HostTranscript:
     """mix_root / draw_felt on the host channel: one 32-byte root read-back per layer.  `prover` commits the layers' trees (the
     Merkle channel's: Blake2s by default, Poseidon252MerkleProver for a Poseidon252 channel)."""
@@ -319,11 +325,13 @@ class FriProver:
         self.config, self.first_layer, self.inner_layers, self.last_layer_poly = config, first_layer, inner_layers, last_layer_coeffs
 
     @staticmethod
-    def commit(channel, config: FriConfig, columns, twiddles: TwiddleTree, device_channel: bool = True, merkle_channel=None, *,
+    def commit(channel, config: FriConfig, columns, twiddles: TwiddleTree, device_channel: bool | None = None, merkle_channel=None, *,
                per_layer_calls: bool = False, host_last_layer: bool = False) -> "FriProver":
         """columns: SecureEvaluation list, canonic domains, strictly decreasing sizes (fri.ts:644-674).  merkle_channel: the
-        Merkle channel of the layer trees (default Blake2sMerkleChannel; Poseidon252MerkleChannel keeps the transcript on the
-        host: the device channel and tstwo_fri_commit_layers are Blake2s only).  With the device transcript, the references the
+        Merkle channel of the layer trees (default Blake2sMerkleChannel).  device_channel: None takes the channel's default — the
+        device transcript for Blake2s, POSEIDON252_DEVICE_TRANSCRIPT for Poseidon252MerkleChannel with a Poseidon252Channel, whose
+        one-call commit is tstwo_fri_commit_layers_poseidon252 (DevicePoseidon252Channel; per_layer_calls does not apply to it);
+        False keeps the transcript on the host.  With the device transcript, the references the
         one-call commit is tested and timed against: per_layer_calls runs the layer loop through round 2's per-layer calls
         (_commit_layers, what FriCommitPlan captures) instead of tstwo_fri_commit_layers; host_last_layer interpolates the last
         layer on the host (numpy) instead of by tstwo_line_interpolate."""
@@ -338,6 +346,19 @@ class FriProver:
         # commit loop is one launch sequence — roots are mixed and alphas drawn by the device channel, nothing is read back
         # until the last layer.  Otherwise: the host channel, one 32-byte read-back per layer.
         prover = (merkle_channel or Blake2sMerkleChannel).prover
+        from .poseidon import DevicePoseidon252Channel, Poseidon252Channel, Poseidon252MerkleProver
+        if device_channel is None:
+            device_channel = POSEIDON252_DEVICE_TRANSCRIPT if prover is Poseidon252MerkleProver else True
+        if (device_channel and prover is Poseidon252MerkleProver and isinstance(channel, Poseidon252Channel)
+                and FriProver._device_capable(columns, twiddles)):
+            # the whole layer loop in one call over Poseidon trees and the Poseidon device channel; the last layer as below
+            dch = DevicePoseidon252Channel(channel)
+            alphas = L.DeviceBuffer(16 * (columns[0].domain.logSize() + 2))
+            first_layer, inner, layer_eval = FriProver._commit_layers_in_library(
+                config, columns, twiddles, dch, alphas, entry="tstwo_fri_commit_layers_poseidon252", tree_cls=Poseidon252MerkleProver)
+            coeff_buf = None if host_last_layer else line_interpolate_device(layer_eval, twiddles)
+            prefetched = FriProver._fetch_end_of_commit(dch, layer_eval, twiddles, coeff_buf)
+            return FriProver(config, first_layer, inner, FriProver._commit_last_layer(channel, config, layer_eval, twiddles, prefetched))
         on_device = (device_channel and prover is MerkleProver and not getattr(channel, "ts_compat", False) and hasattr(channel, "_digest")
                      and FriProver._device_capable(columns, twiddles))
         if device_channel and getattr(channel, "ts_compat", False):
@@ -392,7 +413,8 @@ class FriProver:
                 and HipFriOps.can_fold_on_device(LineDomain(Coset.half_odds(first_log)), twiddles))
 
     @staticmethod
-    def _commit_layers_in_library(config: FriConfig, columns, twiddles: TwiddleTree, dch: DeviceChannel, alphas) -> tuple:
+    def _commit_layers_in_library(config: FriConfig, columns, twiddles: TwiddleTree, dch, alphas, entry: str = "tstwo_fri_commit_layers",
+                                  tree_cls=MerkleProver) -> tuple:
         """commitInnerLayers (fri.ts:676-716) through tstwo_fri_commit_layers: first-layer tree, then per layer mix root / draw
         alpha / fold / commit on the device, in one call; the buffers it returns are adopted by the host objects below."""
         import ctypes as C
@@ -404,7 +426,7 @@ class FriProver:
         cap = first_log - last_log + 1
         outs = (L.FriLayerOut * cap)()
         n_out, first = C.c_size_t(0), L.vp()
-        L.call("tstwo_fri_commit_layers", L.ptr_array([cc.ptr for c in columns for cc in c.values.columns]), L.u32x(logs), len(columns),
+        L.call(entry, L.ptr_array([cc.ptr for c in columns for cc in c.values.columns]), L.u32x(logs), len(columns),
                C.c_void_p(twiddles.itwiddles.ptr), twiddles.log_size, last_log, C.c_void_p(dch.buf.ptr), C.c_void_p(alphas.ptr),
                alphas.nbytes // 16, C.byref(first), outs, cap, C.byref(n_out))
         # every block the library handed out is adopted HERE, before any other object is built: an exception further down must not
@@ -419,7 +441,7 @@ class FriProver:
             adopted.append((o.log_size, cols, tree))
 
         def tree_of(buf, max_log):
-            return MerkleProver(TreeLayers(buf, max_log), buf, None)
+            return tree_cls(TreeLayers(buf, max_log), buf, None)
 
         def eval_of(entry, domain):
             n = 1 << entry[0]

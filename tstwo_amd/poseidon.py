@@ -2,7 +2,8 @@
 uses when it is to be verified on Starknet.
 
 Trees and the proof-of-work grind run on the GPU (csrc/poseidon.hip); the channel and the verifier's hashNode need a handful of
-hashes and stay on the host, in Python integers.  Poseidon here is Starknet's: Hades over F_p, p = 2^251 + 17 2^192 + 1, width 3,
+hashes and stay on the host, in Python integers — except inside a FRI commit, whose transcript can run on the device
+(DevicePoseidon252Channel, csrc/poseidon_coop.hip).  Poseidon here is Starknet's: Hades over F_p, p = 2^251 + 17 2^192 + 1, width 3,
 8 full and 83 partial rounds, S-box x^3; poseidonHashMany / poseidonHash as @scure/starknet computes them for the reference.
 
 A FieldElement252 crosses the C ABI and lives in device memory as 8 little-endian u32 limbs (32 bytes): a Poseidon tree has the
@@ -277,6 +278,41 @@ class Poseidon252MerkleChannel:
     mixRoot = mix_root
     # hasher / prover of this channel's trees: set below (Poseidon252MerkleProver is defined further down)
     hasher = Poseidon252MerkleHasher
+
+
+class DevicePoseidon252Channel:
+    """The Poseidon252Channel's state (digest limbs, n_challenges, n_sent) mirrored in 40 bytes of device memory — the surface of
+    channel.DeviceChannel — so that a launch sequence (FRI commit: tree -> mix_root -> draw_felt -> fold -> tree ...) never waits
+    for the host (csrc/poseidon_coop.hip: one wave, the permutation spread over 8 lanes)."""
+
+    def __init__(self, host: Poseidon252Channel, buf=None):
+        self.buf = buf if buf is not None else L.DeviceBuffer(64)
+        self.load(host)
+
+    def load(self, host: Poseidon252Channel, tail=None) -> None:
+        """(Re)start from the host channel's state (one 64-byte upload).  tail: words the owner of a larger buffer keeps behind the
+        16 state words, sent in the same upload."""
+        if not isinstance(host, Poseidon252Channel):
+            raise TypeError("Expected Poseidon252Channel")
+        self.host = host
+        st = np.zeros(16 + (0 if tail is None else len(tail)), dtype=np.uint32)
+        if tail is not None:
+            st[16:] = tail
+        st[:8] = host.digest().to_words()
+        st[8], st[9] = host.n_challenges, host.n_sent
+        self.buf.upload(st)
+
+    def mix_root_draw_felt(self, root_ptr: int | None, felt_ptr: int | None) -> None:
+        """mix_root of the element at device address root_ptr, then draw_felt into the 4 words at felt_ptr (either may be None)."""
+        L.call("tstwo_poseidon252_channel_mix_root_draw_felt", C.c_void_p(self.buf.ptr), C.c_void_p(root_ptr or 0), C.c_void_p(felt_ptr or 0))
+
+    def sync_to_host(self, st=None) -> Poseidon252Channel:
+        """The host channel continues from the device state (st: the 10 state words when the caller already fetched them)."""
+        if st is None:
+            st = self.buf.download(count=10)
+        self.host._felt = FieldElement252.from_words(st[:8])
+        self.host.n_challenges, self.host.n_sent = int(st[8]), int(st[9])
+        return self.host
 
 
 # ---- device trees
