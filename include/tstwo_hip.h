@@ -202,6 +202,22 @@ int tstwo_eval_at_point(const uint32_t *coeffs, uint32_t log_size, const uint32_
  * column (host). */
 int tstwo_eval_at_point_batch(const uint32_t *const *coeffs, size_t n_cols, uint32_t log_size, const uint32_t px[4],
                               const uint32_t py[4], uint32_t *out);
+/* PolyOps.eval_at_point (backend/cpu/circle.ts:52-69) for every (column, point) pair of an opening: the reference's caller loops
+ * per column over that column's points (packages/core/src/pcs/prover.ts:94-106).  Columns sampled at the same points form a
+ * group; one call takes any number of groups of mixed sizes, loads every coefficient once per sweep of up to 4 points and ends
+ * with one read-back.  Synchronous.
+ *   coeffs        host array of device pointers: the columns of group 0, then group 1, ...  Any 4-byte alignment (one column off a
+ *                 16-byte boundary puts its group on the word loads); a column may appear more than once.
+ *   group_cols    columns of group g (>= 1), each of 2^group_logs[g] coefficients (log <= 31)
+ *   group_points  points of group g: 1..TSTWO_EVAL_MAX_POINTS; a point may repeat
+ *   points        host, 8 words per point (x[4], y[4]), the groups' points one after the other
+ *   out           host, 4 words per (group, column, point), in that nesting order
+ * n_groups == 0 is a no-op.  Refused with TSTWO_ERR_BAD_ARG before anything is enqueued, `out` untouched ("eval_at_points: ..."):
+ * "null argument", "a group without columns", "1 to 16 points per group", "log size out of range", "point word out of range"
+ * (a word >= 2^31 - 1), and a call while the stream is capturing ("host read-back during graph capture ..."). */
+#define TSTWO_EVAL_MAX_POINTS 16
+int tstwo_eval_at_points(const uint32_t *const *coeffs, const uint32_t *group_cols, const uint32_t *group_logs,
+                         const uint32_t *group_points, size_t n_groups, const uint32_t *points, uint32_t *out);
 
 /* ---------------------------------------------------------------- FriOps (fri.ts:93-110)
  * Twiddles come from the inverse twiddle tree `itw` (root coset log tw_log) — a FRI fold is one

@@ -327,6 +327,34 @@ export class HipCirclePoly extends CirclePoly<HipBackend> {
     check(hip.tstwo_eval_at_point_batch(ptr(ptrs(polys.map((p) => p.dev.dev))), BigInt(polys.length), polys[0]!.logSize(), ptr(q4(point.x)), ptr(q4(point.y)), ptr(out)));
     return polys.map((_, i) => QM31.from_u32_unchecked(out[4 * i]!, out[4 * i + 1]!, out[4 * i + 2]!, out[4 * i + 3]!));
   }
+  /** polys[i] (any sizes) at every point of pointSets[i] (1..16 points each) in ONE call: polynomials with the same size and the
+   *  same ordered points form a group, every coefficient is read once per sweep of up to 4 points, one read-back
+   *  (tstwo_eval_at_points; the caller's loop of pcs/prover.ts:94-106). */
+  static evalAtPoints(polys: HipCirclePoly[], pointSets: CirclePoint<QM31>[][]): QM31[][] {
+    const groups = new Map<string, { pts: CirclePoint<QM31>[]; log: number; members: number[] }>();
+    polys.forEach((p, i) => {
+      const pts = pointSets[i]!;
+      if (pts.length === 0) return;
+      const key = `${p.logSize()}|${pts.map((pt) => [...q4(pt.x), ...q4(pt.y)].join(",")).join(";")}`;
+      const g = groups.get(key) ?? { pts, log: p.logSize(), members: [] };
+      g.members.push(i);
+      groups.set(key, g);
+    });
+    const gs = [...groups.values()];
+    const values: QM31[][] = polys.map(() => []);
+    if (gs.length === 0) return values;
+    const words = new Uint32Array(8 * gs.reduce((n, g) => n + g.pts.length, 0));
+    let w = 0;
+    for (const g of gs) for (const pt of g.pts) { words.set(q4(pt.x), w); words.set(q4(pt.y), w + 4); w += 8; }
+    const out = new Uint32Array(4 * gs.reduce((n, g) => n + g.members.length * g.pts.length, 0));
+    check(hip.tstwo_eval_at_points(ptr(ptrs(gs.flatMap((g) => g.members.map((i) => polys[i]!.dev.dev)))), ptr(Uint32Array.from(gs, (g) => g.members.length)),
+      ptr(Uint32Array.from(gs, (g) => g.log)), ptr(Uint32Array.from(gs, (g) => g.pts.length)), BigInt(gs.length), ptr(words), ptr(out)));
+    let o = 0;
+    for (const g of gs) for (const i of g.members) {
+      values[i] = g.pts.map(() => { o += 4; return QM31.from_u32_unchecked(out[o - 4]!, out[o - 3]!, out[o - 2]!, out[o - 1]!); });
+    }
+    return values;
+  }
   static eval_at_point(poly: HipCirclePoly, point: CirclePoint<QM31>): QM31 {
     const out = new Uint32Array(4);
     check(hip.tstwo_eval_at_point(poly.dev.dev, poly.logSize(), ptr(q4(point.x)), ptr(q4(point.y)), ptr(out)));

@@ -151,6 +151,13 @@ class TreeBuilder:
         self.scheme.commit(self.polys, channel)
 
 
+# prove_values samples through ONE tstwo_eval_at_points call up to this many coefficients in all.  Measured
+# (profiles/bench_eval_points.jsonl): at 2 to 4 points the one call is 1.1 to 2 times faster than a batched call per point up to
+# 2^25 coefficients (32 x 2^20), where launches and read-backs dominate, and 1.16 times slower at 2^30 (256 x 2^22), where both
+# run at the multiplier's rate and the one-point kernels are the tighter code.
+ONE_CALL_SAMPLING_MAX_COEFFS = 1 << 25
+
+
 class CommitmentSchemeProver:
     """pcs/prover.ts:26-80 (Rust comment): a list of commitment trees sharing one twiddle tree."""
 
@@ -188,19 +195,32 @@ class CommitmentSchemeProver:
         Out-of-domain evaluation, quotients, FRI commit, grinding and every decommitment read device-resident data;
         only sampled values, roots, witnesses and queried values reach the host."""
         # "Evaluate columns out of domain"
-        # (all polynomials of one size sampled at the same point share one batched launch sequence)
-        groups = {}
-        for ti, (tree, tree_pts) in enumerate(zip(self.trees, sampled_points)):
+        for tree, tree_pts in zip(self.trees, sampled_points):
             if len(tree_pts) != len(tree.polynomials):
                 raise ValueError("sampled_points does not match the committed columns")
-            for ci, (poly, pts) in enumerate(zip(tree.polynomials, tree_pts)):
-                for pi, pt in enumerate(pts):
-                    key = (poly.logSize(), pt.x.tup(), pt.y.tup())
-                    groups.setdefault(key, (pt, []))[1].append((ti, ci, pi, poly))
         values = {}
-        for pt, members in groups.values():
-            for (ti, ci, pi, _), v in zip(members, HipCirclePoly.eval_at_point_batch([m[3] for m in members], pt)):
-                values[(ti, ci, pi)] = v
+        several = any(len(pts) != 1 for tree_pts in sampled_points for pts in tree_pts)
+        coeffs = sum(1 << poly.logSize() for tree, tree_pts in zip(self.trees, sampled_points) for poly, pts in zip(tree.polynomials, tree_pts) if pts)
+        if not several or coeffs > ONE_CALL_SAMPLING_MAX_COEFFS:
+            # (all polynomials of one size sampled at the same point share one batched launch sequence)
+            groups = {}
+            for ti, (tree, tree_pts) in enumerate(zip(self.trees, sampled_points)):
+                for ci, (poly, pts) in enumerate(zip(tree.polynomials, tree_pts)):
+                    for pi, pt in enumerate(pts):
+                        key = (poly.logSize(), pt.x.tup(), pt.y.tup())
+                        groups.setdefault(key, (pt, []))[1].append((ti, ci, pi, poly))
+            for pt, members in groups.values():
+                for (ti, ci, pi, _), v in zip(members, HipCirclePoly.eval_at_point_batch([m[3] for m in members], pt)):
+                    values[(ti, ci, pi)] = v
+        else:
+            # some column is opened at several points (row offsets, LogUp) and the opening is small enough to be bound by launches
+            # and read-backs: one call samples every column of every tree, one read-back
+            where = [(ti, ci) for ti, tree_pts in enumerate(sampled_points) for ci in range(len(tree_pts))]
+            got = HipCirclePoly.eval_at_points([self.trees[ti].polynomials[ci] for ti, ci in where],
+                                               [sampled_points[ti][ci] for ti, ci in where])
+            for (ti, ci), vs in zip(where, got):
+                for pi, v in enumerate(vs):
+                    values[(ti, ci, pi)] = v
         samples = [[[PointSample(pt, values[(ti, ci, pi)]) for pi, pt in enumerate(pts)] for ci, pts in enumerate(tree_pts)]
                    for ti, tree_pts in enumerate(sampled_points)]
         sampled_values = [[[s.value for s in col] for col in tree] for tree in samples]

@@ -59,6 +59,9 @@ def _swap57(col: HipColumn) -> None:
     col.buf.upload(v)
 
 
+EVAL_MAX_POINTS = 16         # TSTWO_EVAL_MAX_POINTS (include/tstwo_hip.h)
+
+
 class HipCirclePoly:
     """CirclePoly<HipBackend> (poly/circle/poly.ts:9-73) + the PolyOps statics of backend/cpu/circle.ts:39-208."""
 
@@ -112,6 +115,40 @@ class HipCirclePoly:
         L.call("tstwo_eval_at_point_batch", L.ptr_array([p.coeffs.ptr for p in polys]), len(polys), lg,
                L.u32x(as_q4(point.x)), L.u32x(as_q4(point.y)), out)
         return [QM31.from_u32_unchecked(*out[4 * i:4 * i + 4]) for i in range(len(polys))]
+
+    @staticmethod
+    def eval_at_points(polys, point_sets) -> list:
+        """polys[i] (any sizes) at every point of point_sets[i]: [[value per point] per polynomial], the values of
+        [[p.evalAtPoint(pt) for pt in pts] for p, pts in zip(polys, point_sets)].  Polynomials with the same (log size, ordered
+        point tuple) form a group of ONE tstwo_eval_at_points call: every coefficient is read once per sweep of up to 4 points
+        and the call has one read-back."""
+        polys, point_sets = list(polys), [list(pts) for pts in point_sets]
+        if len(polys) != len(point_sets):
+            raise ValueError("eval_at_points: one point list per polynomial")
+        groups = {}                  # (log size, points) -> (points, [(polynomial, offset of these points in its list)])
+        for i, (p, pts) in enumerate(zip(polys, point_sets)):
+            for off in range(0, len(pts), EVAL_MAX_POINTS):        # a longer list: runs of 16 points, a group each
+                run = pts[off:off + EVAL_MAX_POINTS]
+                key = (p.logSize(), tuple((pt.x.tup(), pt.y.tup()) for pt in run))
+                groups.setdefault(key, (run, []))[1].append((i, off))
+        values = [[None] * len(pts) for pts in point_sets]
+        if not groups:
+            return values
+        ptrs, cols, logs, npts, words = [], [], [], [], []
+        for (lg, _), (run, members) in groups.items():
+            ptrs += [polys[i].coeffs.ptr for i, _ in members]
+            cols.append(len(members)); logs.append(lg); npts.append(len(run))
+            for pt in run:
+                words += [*as_q4(pt.x), *as_q4(pt.y)]
+        out = (C.c_uint32 * (4 * sum(c * k for c, k in zip(cols, npts))))()
+        L.call("tstwo_eval_at_points", L.ptr_array(ptrs), L.u32x(cols), L.u32x(logs), L.u32x(npts), len(cols), L.u32x(words), out)
+        o = 0
+        for run, members in groups.values():
+            for i, off in members:
+                for k in range(len(run)):
+                    values[i][off + k] = QM31.from_u32_unchecked(*out[o:o + 4])
+                    o += 4
+        return values
 
     def _n_significant(self) -> int:
         c = self.coeffs.to_numpy()
