@@ -571,6 +571,78 @@ int tstwo_gkr_round_finish(uint32_t *chan, const uint32_t *sums, uint32_t *state
                            const uint32_t y_k[4], const uint32_t inv_eq0[4], const uint32_t alpha[4], uint32_t *round_poly_out,
                            uint32_t *challenge_out);
 
+/* ---- prove_batch without a read-back between its layers (gkr_prover.ts:440-580).  The building blocks below take every scalar
+ * the protocol produces (the out-of-domain point, alpha, lambda, the eq corrections) from DEVICE words an earlier launch on the
+ * stream wrote; all are asynchronous, read nothing back, and give the words of their by-value twins.  Device scalars are 4 words,
+ * 16-byte aligned; a null or misaligned one fails with TSTWO_ERR_BAD_ARG before anything is enqueued. */
+/* tstwo_gkr_gen_eq_evals (gkr.ts:90-104) with y (4 n_y words; may be null for n_y = 0) and v in device memory. */
+int tstwo_gkr_gen_eq_evals_dev(const uint32_t *y_dev, uint32_t n_y, const uint32_t *v_dev, uint32_t *const out[4]);
+/* tstwo_gkr_sum_poly_async / tstwo_gkr_round_dev (gkr.ts:142-311, gkr_prover.ts:313-336) with lambda in device memory. */
+int tstwo_gkr_sum_poly_async_ldev(uint32_t kind, const uint32_t *const eq[4], const uint32_t *const num[4], const uint32_t *const den[4],
+                                  uint32_t n_vars, const uint32_t *lambda_dev, uint32_t *out_dev);
+int tstwo_gkr_round_dev_ldev(uint32_t kind, const uint32_t *const eq[4], const uint32_t *const num[4], const uint32_t *const den[4],
+                             uint32_t *const out_num[4], uint32_t *const out_den[4], uint32_t n_vars, const uint32_t *r_dev,
+                             const uint32_t *lambda_dev, uint32_t *out_dev);
+/* The status word of the entries below: bits are ORed in, never cleared. */
+#define TSTWO_GKR_STATUS_DEGENERATE 1u   /* an eq point at which correctSumAsPolyInFirstVariable divides by zero */
+/* tstwo_gkr_round_finish (sumcheck.ts:99-227, gkr_prover.ts:609-660) with y_k, inv_eq0 and alpha in device memory.  A device y_k
+ * cannot be refused before the launch: for y_k in {0, 1, 1/2, 1/3} the kernel sets TSTWO_GKR_STATUS_DEGENERATE in *status (one
+ * device word) and still finishes — it stores nothing outside its outputs, whose contents are then unspecified. */
+int tstwo_gkr_round_finish_dev(uint32_t *chan, const uint32_t *sums, uint32_t *state, uint32_t n_instances, uint64_t active_mask,
+                               const uint32_t *y_k_dev, const uint32_t *inv_eq0_dev, const uint32_t *alpha_dev,
+                               uint32_t *round_poly_out, uint32_t *challenge_out, uint32_t *status);
+/* One LANE of the two transcript kernels: an instance that is active in the layer (lanes are the active instances in instance
+ * order, as sumcheck.ts batches them).  An array of these lives in device memory.
+ *   src      the columns the layer's mask is read from (numerators [0..4), denominators [4..8); words 0 and 1 of each): the
+ *            folded 2-point layer, or the instance's 1-variable layer where it enters at this layer
+ *   kind     of that layer: GRAND_PRODUCT (one column: src[4..8)), LOGUP_GENERIC (two), LOGUP_SINGLES ((1, 1), then src[4..8))
+ *   inst     the instance's index: where its claims live in `claims` / `output_claims` (8 words per instance)
+ *   shift    layer_begin: the sum-check claim is doubled n_rounds - n_variables times (any value: the factor is 2^(shift mod 31),
+ *            which is 2^shift in M31)
+ *   enter    layer_begin: non-zero = the instance enters here; its output values are word 0 of out_src (as src; numerators are
+ *            read unless kind is GRAND_PRODUCT) */
+typedef struct {
+    const uint32_t *src[8];
+    uint32_t inst, kind, shift, enter;
+    const uint32_t *out_src[8];
+} tstwo_gkr_lane;
+/* The top of a layer of prove_batch (gkr_prover.ts:452-500) by one wave: the output values of the entering lanes (stored to
+ * output_claims and taken as their claims to verify), mix_felts of every lane's claims to verify (one mix per lane, in order), the
+ * draws of alpha then lambda (claims is only read: entering lanes store to output_claims), state[lane] = (rlc(claims, lambda) * 2^shift, 1), and from the n_y coordinates of the layer's
+ * out-of-domain point y_dev: inv_eq0_out[r] = 1 / prod_{j <= r} (1 - y_j) for every round r (prefix products, one inversion step)
+ * and scalars_out = alpha | lambda | 1 - y_0 (12 words; the last 4 only for n_y > 0: the v of the layer's eq table).
+ * TSTWO_GKR_STATUS_DEGENERATE is set where the host raises (a y_j in {0, 1, 1/2, 1/3}).  1 <= n_lanes <= 64, n_y <= 28. */
+int tstwo_gkr_layer_begin(uint32_t *chan, const tstwo_gkr_lane *lanes_dev, uint32_t n_lanes, const uint32_t *claims, uint32_t *output_claims,
+                          uint32_t *state, uint32_t *scalars_out, const uint32_t *y_dev, uint32_t n_y, uint32_t *inv_eq0_out,
+                          uint32_t *status);
+/* The bottom of a layer (gkr_prover.ts:540-575) by one wave: every lane's mask read from src and written to masks_out (16 words a
+ * lane: column 0 at 0 and 1, column 1 at 0 and 1; zero where the kind has one column), mix_felts of each mask in lane order
+ * (mask.columns() flattened), the draw of the challenge (challenge_out, 4 words: appended to the next out-of-domain point), and
+ * claims[inst] = the mask's columns reduced at the challenge (reduceAtPoint; 8 words an instance). */
+int tstwo_gkr_layer_end(uint32_t *chan, const tstwo_gkr_lane *lanes_dev, uint32_t n_lanes, uint32_t *masks_out, uint32_t *claims,
+                        uint32_t *challenge_out);
+/* prove_batch (gkr_prover.ts:440-580) in ONE call: the layers are generated, every layer runs begin / eq table / rounds / last
+ * folds / end on the device, and one read-back at the end fills `block` (host).  Synchronous.  chan = the Blake2s channel's 10
+ * words (host; the Rust draw semantics).  instances: 1 to 64; num / den as for the `kind` arguments above (4-byte aligned, never
+ * written).  The schedule and the block's layout come from csrc/gkr_plan.h (n = instances, n_layers = max log_n; word offsets):
+ *   0    channel state after the proof (10 words)          16   status word
+ *   32 + 16 n   claims to verify, 8 words per instance     32 + 24 n   output claims, 8 words per instance (one value for a
+ *   32 + 32 n + 4 n_layers (n_layers & 1)   the final out-of-domain point (4 n_layers words)       grand product: words 0..3)
+ *   then per layer L = 0 .. n_layers - 1, from 32 + 32 n + 12 n_layers on: L round polynomials of 20 words (the round_poly_out
+ *   of tstwo_gkr_round_finish), then 16 words per active instance (log_n >= n_layers - L, in instance order): its mask.
+ * Everything else in the block is working state.  tstwo_gkr_prove_batch_words gives the block's size in words.
+ * Refused with TSTWO_ERR_BAD_ARG before anything is enqueued: no or more than 64 instances, log_n = 0 or > 28, a 1-variable
+ * LogUpMultiplicities instance (it has no mask), null or misaligned pointers, a block that is too small, a call during graph
+ * capture.  A set status bit fails with TSTWO_ERR_BAD_ARG "sum-check: degenerate eq point" after the read-back. */
+typedef struct {
+    uint32_t kind, log_n;
+    const uint32_t *num[4];
+    const uint32_t *den[4];
+} tstwo_gkr_instance;
+int tstwo_gkr_prove_batch_words(const tstwo_gkr_instance *instances, size_t n_instances, size_t *block_words);
+int tstwo_gkr_prove_batch(const uint32_t chan[10], const tstwo_gkr_instance *instances, size_t n_instances, uint32_t *block,
+                          size_t block_words);
+
 /* ---------------------------------------------------------------- AIR (constraint evaluation, composition polynomial)
  * Rust stwo constraint_framework/component.rs (the reference's constraint_framework/index.ts, air/accumulator.ts,
  * examples/fibonacci.ts).  Constraints read only their own row (mask offset 0).  Kinds for the `kind` argument: */

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """LogUp-GKR on one MI355X: per-op device time (HIP events, median of --reps after --warmup) at n = 20 and 24 with GB/s and
 the fraction of 8 TB/s, the VALU issue bound of each sum kernel (VALU instructions of its loop body, from the ISA, times the
-terms, at the one-port integer peak of DESIGN §4), and prove_batch wall time on each path (sum-check rounds on the device / the
-host loop, run alternately in one process) split into device time, synchronous read-backs and the host remainder.  Prints one
-JSON line.  The time of k_gkr_round_finish per launch comes from a separate `rocprofv3 --kernel-trace --stats -- python
-tools/bench_gkr.py --no-ops --sizes 20 --paths device` run.
+terms, at the one-port integer peak of DESIGN §4), and prove_batch wall time on each path (the whole proof in one library call /
+sum-check rounds on the device / the host loop, run alternately in one process) split into device time, synchronous read-backs and
+the host remainder.  Prints one JSON line.  The time of k_gkr_round_finish per launch comes from a separate `rocprofv3
+--kernel-trace --stats -- python tools/bench_gkr.py --no-ops --sizes 20 --paths device` run; the transcript kernels of the one-call
+path (k_gkr_layer_begin / k_gkr_layer_end) from one with `--paths one_call --sizes "" --batches 1,5,64`.
 
-    python tools/bench_gkr.py [--sizes 20,24] [--reps 20] [--warmup 3] [--prove-reps 9] [--paths device,host] [--no-ops] [--out FILE]
+    python tools/bench_gkr.py [--sizes 20,24] [--reps 20] [--warmup 3] [--prove-reps 9] [--paths one_call,device,host] [--no-ops]
+                              [--batches 1,5,64] [--batch-log 12] [--out FILE]
 """
 from __future__ import annotations
 
@@ -150,7 +152,7 @@ def make_instance(rng, kind, n):
     return G.Layer.logup_singles(den)
 
 
-PATHS = {"device": {"device_rounds": True}, "host": {"device_rounds": False}, "default": {}}
+PATHS = {"one_call": {"one_call": True}, "device": {"device_rounds": True}, "host": {"device_rounds": False}, "default": {}}
 
 
 def bench_prove(layers, reps, paths=("device", "host")):
@@ -166,9 +168,15 @@ def bench_prove(layers, reps, paths=("device", "host")):
             st = {"readbacks": 0, "device_s": 0.0}
             seg = [None]
 
-            def call(name, *args, seg=seg):
-                if seg[0] is None and name.startswith(("tstwo_gkr_", "tstwo_mle_")):     # the first launch of the stretch
-                    seg[0] = L.Event().record()
+            def call(name, *args, seg=seg, st=st):
+                if name == "tstwo_gkr_prove_batch":         # the one-call path: launches and the one read-back inside the call
+                    start = L.Event().record()
+                    res = orig_call(name, *args)
+                    st["device_s"] += start.elapsed_ms(L.Event().record()) * 1e-3
+                    st["readbacks"] += 1
+                    return res
+                if seg[0] is None and name.startswith(("tstwo_gkr_", "tstwo_mle_")) and name != "tstwo_gkr_prove_batch_words":
+                    seg[0] = L.Event().record()              # the first launch of the stretch
                 return orig_call(name, *args)
 
             def dm(pieces, st=st, seg=seg):
@@ -210,13 +218,20 @@ def main():
     ap.add_argument("--prove-reps", type=int, default=9)
     ap.add_argument("--paths", default="device,host", help="prove_batch paths, run alternately: " + ", ".join(PATHS))
     ap.add_argument("--no-ops", action="store_true", help="skip the per-op timings")
+    ap.add_argument("--batches", default="", help="also prove batches of this many LogUpGeneric instances of 2^--batch-log values")
+    ap.add_argument("--batch-log", type=int, default=12)
     ap.add_argument("--out", default=None, help="also write the JSON result to this file (profiles/gkr_device_rounds.json)")
     a = ap.parse_args()
     paths = tuple(a.paths.split(","))
     L.init(0)
     res = {"tool": "bench_gkr", "device": L.device_name(), "valu_one_port_lane_ops": VALU_ONE_PORT, "ops": {}, "prove_batch": {}}
     valu = None if a.no_ops else sum_valu_counts()
-    for n in [int(s) for s in a.sizes.split(",")]:
+    for k in [int(s) for s in a.batches.split(",") if s]:
+        rng = np.random.default_rng(2000 + k)
+        batch = [make_instance(rng, G.LOGUP_GENERIC, a.batch_log) for _ in range(k)]
+        res["prove_batch"][f"batch_{k}x{a.batch_log}"] = bench_prove(batch, a.prove_reps, paths)
+        del batch
+    for n in [int(s) for s in a.sizes.split(",") if s]:
         if not a.no_ops:
             res["ops"][str(n)] = bench_ops(n, a.reps, a.warmup, valu)
             L.call("tstwo_trim")

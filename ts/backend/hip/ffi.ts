@@ -114,6 +114,14 @@ const lib = dlopen(process.env.TSTWO_HIP_LIB ?? "libtstwo_hip.so", {
   tstwo_mle_fix_first_variable_base_dev: { args: [u64, u32, u64, P], returns: i32 },
   tstwo_mle_fix_first_variable_secure_dev: { args: [P, u32, u64, P], returns: i32 },
   tstwo_gkr_round_finish: { args: [u64, u64, u64, u32, u64, P, P, P, u64, u64], returns: i32 },
+  tstwo_gkr_gen_eq_evals_dev: { args: [u64, u32, u64, P], returns: i32 },
+  tstwo_gkr_sum_poly_async_ldev: { args: [u32, P, P, P, u32, u64, u64], returns: i32 },
+  tstwo_gkr_round_dev_ldev: { args: [u32, P, P, P, P, P, u32, u64, u64, u64], returns: i32 },
+  tstwo_gkr_round_finish_dev: { args: [u64, u64, u64, u32, u64, u64, u64, u64, u64, u64, u64], returns: i32 },
+  tstwo_gkr_layer_begin: { args: [u64, u64, u32, u64, u64, u64, u64, u64, u32, u64, u64], returns: i32 },
+  tstwo_gkr_layer_end: { args: [u64, u64, u32, u64, u64, u64], returns: i32 },
+  tstwo_gkr_prove_batch_words: { args: [P, u64, P], returns: i32 },
+  tstwo_gkr_prove_batch: { args: [P, P, u64, P, u64], returns: i32 },
   tstwo_mle_eval_at_point_base: { args: [P, u64, u32, P, P], returns: i32 },
   tstwo_mle_eval_at_point_secure: { args: [P, u64, u32, P, P], returns: i32 },
   tstwo_gkr_logup_denominators: { args: [P, P, u64, P, u32, P], returns: i32 },

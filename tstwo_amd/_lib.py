@@ -66,6 +66,16 @@ class LookupGroup(C.Structure):
     _fields_ = [("limbs", vp * 4), ("bits", C.c_uint32 * 4), ("n_limbs", C.c_uint32), ("weight", vp), ("len", C.c_size_t)]
 
 
+class GkrLane(C.Structure):
+    """tstwo_gkr_lane (include/tstwo_hip.h)."""
+    _fields_ = [("src", vp * 8), ("inst", C.c_uint32), ("kind", C.c_uint32), ("shift", C.c_uint32), ("enter", C.c_uint32), ("out_src", vp * 8)]
+
+
+class GkrInstance(C.Structure):
+    """tstwo_gkr_instance (include/tstwo_hip.h)."""
+    _fields_ = [("kind", C.c_uint32), ("log_n", C.c_uint32), ("num", vp * 4), ("den", vp * 4)]
+
+
 _SIGS = {
     "tstwo_init": [C.c_int],
     "tstwo_shutdown": [],
@@ -171,6 +181,14 @@ _SIGS = {
     "tstwo_mle_fix_first_variable_base_dev": [vp, C.c_uint32, vp, P4],
     "tstwo_mle_fix_first_variable_secure_dev": [P4, C.c_uint32, vp, P4],
     "tstwo_gkr_round_finish": [vp, vp, vp, C.c_uint32, C.c_uint64, u32p, u32p, u32p, vp, vp],
+    "tstwo_gkr_gen_eq_evals_dev": [vp, C.c_uint32, vp, P4],
+    "tstwo_gkr_sum_poly_async_ldev": [C.c_uint32, P4, P4, P4, C.c_uint32, vp, vp],
+    "tstwo_gkr_round_dev_ldev": [C.c_uint32, P4, P4, P4, P4, P4, C.c_uint32, vp, vp, vp],
+    "tstwo_gkr_round_finish_dev": [vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp],
+    "tstwo_gkr_layer_begin": [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, vp, vp],
+    "tstwo_gkr_layer_end": [vp, vp, C.c_uint32, vp, vp, vp],
+    "tstwo_gkr_prove_batch_words": [C.POINTER(GkrInstance), C.c_size_t, C.POINTER(C.c_size_t)],
+    "tstwo_gkr_prove_batch": [u32p, C.POINTER(GkrInstance), C.c_size_t, u32p, C.c_size_t],
     "tstwo_mle_eval_at_point_base": [C.POINTER(vp), C.c_size_t, C.c_uint32, u32p, u32p],
     "tstwo_mle_eval_at_point_secure": [C.POINTER(vp), C.c_size_t, C.c_uint32, u32p, u32p],
     "tstwo_gkr_logup_denominators": [C.POINTER(vp), u32p, C.c_size_t, u32p, C.c_uint32, P4],

@@ -12,9 +12,16 @@
 //                   Fold and FOLD take their challenge by value or from 4 device words an earlier launch wrote (the _dev entries).
 //   round finish    k_gkr_round_finish: the O(instances) end of a sum-check round by one wave — round polynomials, combination,
 //                   Blake2s channel mix + draw, new claims — so that a layer of prove_batch is enqueued without a read-back.
+//   one-call proof  tstwo_gkr_prove_batch: the schedule of gkr_plan.h with every protocol scalar left in device words — the _dev /
+//                   _ldev forms of the kernels above read y, v, lambda, inv_eq0 and alpha from memory, and two single-wave
+//                   transcript kernels (k_gkr_layer_begin, k_gkr_layer_end) do what the host does around a layer's sum-check — so
+//                   that the whole proof is enqueued without a read-back and one block comes back at the end.
 // M31 addition is exact, so the reduction order does not change a bit of the result.
+#include <vector>
+
 #include "common.h"
 #include "blake2s.cuh"
+#include "gkr_plan.h"
 
 using namespace tstwo;
 
@@ -68,6 +75,26 @@ __global__ void __launch_bounds__(kThreads) k_eq_tables(EqY y, qm31 v, u32 hi, u
 #pragma unroll 1
     for (u32 k = 0; k < nb; k++) {
         const qm31 yk = y.y[y0 + k];
+        acc = qm31_mul(acc, ((idx >> (nb - 1 - k)) & 1u) ? yk : qm31_sub(one, yk));
+    }
+    tab[t] = acc;
+}
+// The same with the point (4 hi + 4 lo words) and v (4 words) in device memory, left there by an earlier launch on the stream
+// (tstwo_gkr_layer_end / _begin).  Lane t reads y[y0 + k] for k = 0 .. nb: one address per wave wherever a wave lies within one of
+// the two tables (always from 2^6 high entries on), so the loads are broadcasts out of one cache line.
+__global__ void __launch_bounds__(kThreads) k_eq_tables_dev(const u32 *__restrict__ y, const u32 *__restrict__ v, u32 hi, u32 lo, qm31 *tab) {
+    const u32 t = blockIdx.x * kThreads + threadIdx.x;
+    const u32 nh = 1u << hi, nl = 1u << lo;
+    if (t >= nh + nl) return;
+    const bool high = t < nh;
+    const u32 idx = high ? t : t - nh, nb = high ? hi : lo, y0 = high ? 0 : hi;
+    const qm31 one = {1u, 0u, 0u, 0u};
+    qm31 acc = one;
+    if (high) { const uint4 w = gload4(v); acc = {w.x, w.y, w.z, w.w}; }
+#pragma unroll 1
+    for (u32 k = 0; k < nb; k++) {
+        const uint4 w = gload4(y, 4 * (y0 + k));
+        const qm31 yk = {w.x, w.y, w.z, w.w};
         acc = qm31_mul(acc, ((idx >> (nb - 1 - k)) & 1u) ? yk : qm31_sub(one, yk));
     }
     tab[t] = acc;
@@ -226,74 +253,29 @@ __device__ __forceinline__ void wave_sum8(u32 (&v)[8]) {
 
 template <int KIND, bool FOLD>
 __global__ void __launch_bounds__(kThreads) k_sum(SumArgs a) {
-    __shared__ u32 lds[8 * (kThreads / 64) + 1];       // wave partials; [last] = "this block is the last arriver"
-    u32 acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const u32 nt = a.n_terms, stride = gridDim.x * kThreads;
-    if (FOLD && a.r_dev) a.r = ld_uniform_q(a.r_dev);
-    for (u32 i = blockIdx.x * kThreads + threadIdx.x; i < nt; i += stride) {
-        const u32 p0 = 2 * i, p1 = 2 * (nt + i);
-        const qm31 n00 = num_at<KIND, FOLD>(a, p0), n01 = num_at<KIND, FOLD>(a, p0 + 1);
-        const qm31 n10 = num_at<KIND, FOLD>(a, p1), n11 = num_at<KIND, FOLD>(a, p1 + 1);
-        const qm31 d00 = den_at<FOLD>(a, p0), d01 = den_at<FOLD>(a, p0 + 1);
-        const qm31 d10 = den_at<FOLD>(a, p1), d11 = den_at<FOLD>(a, p1 + 1);
-        const qm31 n20 = qm31_sub(q_double(n10), n00), n21 = qm31_sub(q_double(n11), n01);
-        const qm31 d20 = qm31_sub(q_double(d10), d00), d21 = qm31_sub(q_double(d11), d01);
-        const qm31 e = ld_q(a.eq, i);
-        const qm31 at0 = qm31_mul(e, gate<KIND>(a, n00, d00, n01, d01));
-        const qm31 at2 = qm31_mul(e, gate<KIND>(a, n20, d20, n21, d21));
-        acc[0] = m31_add(acc[0], at0.a); acc[1] = m31_add(acc[1], at0.b); acc[2] = m31_add(acc[2], at0.c); acc[3] = m31_add(acc[3], at0.d);
-        acc[4] = m31_add(acc[4], at2.a); acc[5] = m31_add(acc[5], at2.b); acc[6] = m31_add(acc[6], at2.c); acc[7] = m31_add(acc[7], at2.d);
-    }
-    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr u32 kWaves = kThreads / 64, kLast = 8 * kWaves;
-    wave_sum8(acc);
-    if (lane == 0)
-        for (int k = 0; k < 8; k++) lds[8 * wave + k] = acc[k];
-    __syncthreads();
-    // block partial -> slab[block]; then the in-launch hand-off of a split reduction: stores drained, agent-scope release, drained
-    // again (the release's own wait can be dropped by the compiler), relaxed agent-scope ticket; the block that draws the last
-    // ticket acquires at agent scope and reduces every slab row.  Correct for any placement of the blocks over XCDs; the ticket is
-    // zeroed by a memset ahead of every launch.
-    if (threadIdx.x < 8) {
-        u32 s = 0;
-        for (u32 w = 0; w < kWaves; w++) s = m31_add(s, lds[8 * w + threadIdx.x]);
-        gstore1(a.slab, blockIdx.x * 8 + threadIdx.x, s);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const u32 t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const u32 last = t == gridDim.x - 1;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        lds[kLast] = last;
-    }
-    __syncthreads();
-    if (!lds[kLast]) return;
-    u32 tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (u32 b = threadIdx.x; b < gridDim.x; b += kThreads)
-#pragma unroll
-        for (int k = 0; k < 8; k++) tot[k] = m31_add(tot[k], gload1(a.slab, b * 8 + k));
-    wave_sum8(tot);
-    __syncthreads();                         // every wave has read lds[kLast] before it is overwritten below
-    if (lane == 0)
-        for (int k = 0; k < 8; k++) lds[8 * wave + k] = tot[k];
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        u32 s = 0;
-        for (u32 w = 0; w < kWaves; w++) s = m31_add(s, lds[8 * w + threadIdx.x]);
-        *(volatile TSTWO_GLOBAL u32 *)(a.out + threadIdx.x) = s;
-    }
+#include "gkr_sum_body.inc"
+}
+// The same with lambda left in device memory by an earlier launch (tstwo_gkr_layer_begin): one load, then scalar registers.  The
+// pointer is a kernel parameter of its own: SumArgs, and with it the argument segment and the code of k_sum, stay as they were.
+template <int KIND, bool FOLD>
+__global__ void __launch_bounds__(kThreads) k_sum_ldev(SumArgs a, const u32 *lambda_dev) {
+    a.lambda = ld_uniform_q(lambda_dev);
+#include "gkr_sum_body.inc"
 }
 
 template <int KIND>
-int launch_sum_kind(const SumArgs &a, bool fold, unsigned grid) {
-    if (fold) hipLaunchKernelGGL((k_sum<KIND, true>), dim3(grid), dim3(kThreads), 0, ctx().stream, a);
-    else hipLaunchKernelGGL((k_sum<KIND, false>), dim3(grid), dim3(kThreads), 0, ctx().stream, a);
+int launch_sum_kind(const SumArgs &a, const u32 *lambda_dev, bool fold, unsigned grid) {
+    const dim3 g(grid), b(kThreads);
+    if constexpr (KIND != TSTWO_GKR_GRAND_PRODUCT) {                    // a grand product has no lambda
+        if (lambda_dev) {
+            if (fold) hipLaunchKernelGGL((k_sum_ldev<KIND, true>), g, b, 0, ctx().stream, a, lambda_dev);
+            else hipLaunchKernelGGL((k_sum_ldev<KIND, false>), g, b, 0, ctx().stream, a, lambda_dev);
+            TSTWO_LAUNCH_CHECK();
+            return TSTWO_OK;
+        }
+    }
+    if (fold) hipLaunchKernelGGL((k_sum<KIND, true>), g, b, 0, ctx().stream, a);
+    else hipLaunchKernelGGL((k_sum<KIND, false>), g, b, 0, ctx().stream, a);
     TSTWO_LAUNCH_CHECK();
     return TSTWO_OK;
 }
@@ -305,19 +287,22 @@ Soa4 soa(u32 *const c[4]) { return {{c[0], c[1], c[2], c[3]}}; }
 CSoa4 csoa1(const u32 *c) { return {{c, c, c, c}}; }
 
 // Checks and launches one sum (fold: the fused round); `out` = 8 device-visible words.
-// The fold's challenge is r (host words) or, when r_dev is given, 4 words of device memory written earlier on the stream.
+// The fold's challenge is r (host words) or, when r_dev is given, 4 words of device memory written earlier on the stream; lambda
+// likewise: host words, or (lambda null) the 4 device words at lambda_dev.
 int gkr_sum(u32 kind, const u32 *const eq[4], const u32 *const num[4], const u32 *const den[4], u32 *const onum[4],
-            u32 *const oden[4], u32 n_vars, const u32 r[4], const u32 *r_dev, const u32 lambda[4], u32 *out, bool fold) {
+            u32 *const oden[4], u32 n_vars, const u32 r[4], const u32 *r_dev, const u32 lambda[4], u32 *out, bool fold,
+            const u32 *lambda_dev = nullptr) {
     if (!valid_kind(kind)) return set_error(TSTWO_ERR_BAD_ARG, "unknown GKR layer kind");
     if (n_vars == 0) return set_error(TSTWO_ERR_ZERO_VARIABLES, "Number of variables must not be zero");
     if (n_vars + 1 + (fold ? 1 : 0) > kMaxLog) return set_error(TSTWO_ERR_BAD_ARG, "GKR layer too large");
     TSTWO_REQUIRE_TABLE(eq, 4); TSTWO_REQUIRE_TABLE(den, 4);
-    if (!lambda) return set_error(TSTWO_ERR_BAD_ARG, "null lambda");
+    if (!lambda && !lambda_dev) return set_error(TSTWO_ERR_BAD_ARG, "null lambda");
+    if (!lambda && !aligned16(lambda_dev)) return set_error(TSTWO_ERR_BAD_ARG, "device lambda is not 16-byte aligned");
     SumArgs a{};
     a.eq = csoa(eq);
     a.den = csoa(den);
     a.n_terms = 1u << (n_vars - 1);
-    a.lambda = qarg(lambda);
+    if (lambda) { a.lambda = qarg(lambda); lambda_dev = nullptr; }
     if (kind == TSTWO_GKR_LOGUP_GENERIC) { TSTWO_REQUIRE_TABLE(num, 4); a.num = csoa(num); }
     if (kind == TSTWO_GKR_LOGUP_MULTIPLICITIES) { TSTWO_REQUIRE_TABLE(num, 1); a.num = csoa1(num[0]); }
     if (fold) {
@@ -340,10 +325,10 @@ int gkr_sum(u32 kind, const u32 *const eq[4], const u32 *const num[4], const u32
     const unsigned grid = grid_for(a.n_terms, 4) < kMaxSumBlocks ? grid_for(a.n_terms, 4) : kMaxSumBlocks;
     TSTWO_HIP(hipMemsetAsync(a.ticket, 0, 4, ctx().stream));
     switch (kind) {
-        case TSTWO_GKR_GRAND_PRODUCT: return launch_sum_kind<TSTWO_GKR_GRAND_PRODUCT>(a, fold, grid);
-        case TSTWO_GKR_LOGUP_GENERIC: return launch_sum_kind<TSTWO_GKR_LOGUP_GENERIC>(a, fold, grid);
-        case TSTWO_GKR_LOGUP_MULTIPLICITIES: return launch_sum_kind<TSTWO_GKR_LOGUP_MULTIPLICITIES>(a, fold, grid);
-        default: return launch_sum_kind<TSTWO_GKR_LOGUP_SINGLES>(a, fold, grid);
+        case TSTWO_GKR_GRAND_PRODUCT: return launch_sum_kind<TSTWO_GKR_GRAND_PRODUCT>(a, lambda_dev, fold, grid);
+        case TSTWO_GKR_LOGUP_GENERIC: return launch_sum_kind<TSTWO_GKR_LOGUP_GENERIC>(a, lambda_dev, fold, grid);
+        case TSTWO_GKR_LOGUP_MULTIPLICITIES: return launch_sum_kind<TSTWO_GKR_LOGUP_MULTIPLICITIES>(a, lambda_dev, fold, grid);
+        default: return launch_sum_kind<TSTWO_GKR_LOGUP_SINGLES>(a, lambda_dev, fold, grid);
     }
 }
 
@@ -394,122 +379,474 @@ struct FinishArgs {
     qm31 y, a, alpha;
     u32 *poly_out, *ch_out;
 };
+// k_gkr_round_finish_dev: y, a and alpha are read from 4 device words each; a degenerate y is reported in *status.  A parameter of
+// its own, so that FinishArgs, the argument segment and the code of k_gkr_round_finish stay as they were.
+struct FinishDev {
+    const u32 *y, *a, *alpha;
+    u32 *status;
+};
+constexpr u32 kStatusDegenerate = 1u;        // the status word: an eq point at which the host path divides by zero
+__device__ __forceinline__ bool q_eq_m31(qm31 v, u32 a) { return v.a == a && (v.b | v.c | v.d) == 0u; }
+// y = 1/2: b is undefined; y = 1, 0, 1/3: b = 0, 1, 2 collides with an interpolation point
+__device__ __forceinline__ bool degenerate_y(qm31 y) { return q_eq_m31(y, 0u) || q_eq_m31(y, 1u) || q_eq_m31(y, 1u << 30) || q_eq_m31(y, 0x55555555u); }
 __device__ __forceinline__ qm31 q_of(uint4 v) { return {v.x, v.y, v.z, v.w}; }
 __device__ __forceinline__ uint4 u4_of(qm31 v) { return make_uint4(v.a, v.b, v.c, v.d); }
 
 __global__ void __launch_bounds__(64) k_gkr_round_finish(FinishArgs f) {
+#include "gkr_finish_body.inc"
+}
+__global__ void __launch_bounds__(64) k_gkr_round_finish_dev(FinishArgs f, FinishDev dev) {
+    f.y = ld_uniform_q(dev.y); f.a = ld_uniform_q(dev.a); f.alpha = ld_uniform_q(dev.alpha);
+    // the round still finishes (every loop of the body is bounded and the inversion is a fixed power chain); its outputs mean nothing
+    if (threadIdx.x == 0 && degenerate_y(f.y)) __hip_atomic_fetch_or(dev.status, kStatusDegenerate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#include "gkr_finish_body.inc"
+}
+
+// ---------------------------------------------------------------- the top and the bottom of a layer (gkr_prover.ts:452-500, 540-575)
+// What prove_batch's host loop does around a layer's sum-check, by ONE wave each: lane j owns the j-th active instance (a
+// tstwo_gkr_lane in device memory); the channel is wave-uniform.  The mixes of a layer are a serial hash chain by the definition
+// of the transcript: lane j's felts are broadcast and every lane runs the same compression, as k_gkr_round_finish does.
+typedef const TSTWO_GLOBAL tstwo_gkr_lane *lane_ptr;
+__device__ __forceinline__ qm31 bcast_q(qm31 v, u32 j) {
+    return {(u32)__shfl((int)v.a, (int)j, 64), (u32)__shfl((int)v.b, (int)j, 64), (u32)__shfl((int)v.c, (int)j, 64), (u32)__shfl((int)v.d, (int)j, 64)};
+}
+// mix_felts (channel/blake2.ts:113-118) of the first n_felts (1 .. 4) of f: Blake2s over digest || 16 n_felts bytes.  The felts
+// beyond n_felts are zero, which is the padding of the last block.  FOUR = false: at most 2 felts, always one compression.
+template <bool FOUR>
+__device__ __forceinline__ void chan_mix_felts(u32 (&d)[8], u32 &n_chal, u32 &n_sent, const qm31 (&f)[4], u32 n_felts) {
+    using namespace b2s;
+    u32 h[8] = {IV0 ^ 0x01010020u, IV1, IV2, IV3, IV4, IV5, IV6, IV7};
+    u32 m[16];
+#pragma unroll
+    for (int k = 0; k < 8; k++) m[k] = d[k];
+    m[8] = f[0].a; m[9] = f[0].b; m[10] = f[0].c; m[11] = f[0].d; m[12] = f[1].a; m[13] = f[1].b; m[14] = f[1].c; m[15] = f[1].d;
+    const u32 len = 32u + 16u * n_felts;
+    if (!FOUR || n_felts <= 2) {
+        b2s_compress(h, m, len, true);
+    } else {
+        b2s_compress(h, m, 64u, false);
+        m[0] = f[2].a; m[1] = f[2].b; m[2] = f[2].c; m[3] = f[2].d; m[4] = f[3].a; m[5] = f[3].b; m[6] = f[3].c; m[7] = f[3].d;
+#pragma unroll
+        for (int k = 8; k < 16; k++) m[k] = 0u;
+        b2s_compress(h, m, len, true);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) d[k] = h[k];
+    n_chal += 1;
+    n_sent = 0;
+}
+__device__ __forceinline__ qm31 ld_col0(const u32 *const *c, int first, u32 word) {
+    return {gload1(c[first], word), gload1(c[first + 1], word), gload1(c[first + 2], word), gload1(c[first + 3], word)};
+}
+__device__ __forceinline__ void load_lane_ptrs(const u32 *const TSTWO_GLOBAL *p, const u32 *(&out)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) out[k] = p[k];
+}
+
+struct BeginArgs {
+    u32 *chan;
+    const tstwo_gkr_lane *lanes;
+    u32 n;
+    const u32 *claims;
+    u32 *out_claims, *state, *scalars;
+    const u32 *y;
+    u32 n_y;
+    u32 *inv, *status;
+};
+__global__ void __launch_bounds__(64) k_gkr_layer_begin(BeginArgs t) {
     using namespace b2s;
     const u32 lane = threadIdx.x;
-    const bool in = lane < f.n, act = in && ((f.mask >> lane) & 1u);
+    const bool in = lane < t.n;
     const qm31 zero = {0u, 0u, 0u, 0u}, one = {1u, 0u, 0u, 0u};
-    constexpr u32 kHalf = 1u << 30;                                   // 1/2 in M31
-    // requested first: the channel words are needed last
     u32 d[8];
 #pragma unroll
-    for (int k = 0; k < 8; k++) d[k] = gload1(f.chan, k);
-    u32 n_chal = gload1(f.chan, 8), n_sent = gload1(f.chan, 9);
-    qm31 claim = zero, corr = zero, f0 = zero, f2 = zero;
-    if (in) { claim = q_of(gload4(f.state, 8 * lane)); corr = q_of(gload4(f.state, 8 * lane + 4)); }
-    if (act) { f0 = q_of(gload4(f.sums, 8 * lane)); f2 = q_of(gload4(f.sums, 8 * lane + 4)); }
-
-    // wave-uniform: D = 1 - 2y, 1/y and 1/D from one inversion, b, A = a D
-    const qm31 y = f.y, one_y = qm31_sub(one, y), D = qm31_sub(one_y, y);
-    const qm31 inv_yd = qm31_inv(qm31_mul(y, D));
-    const qm31 inv_y = qm31_mul(inv_yd, D), inv_d = qm31_mul(inv_yd, y);
-    const qm31 b = qm31_mul(one_y, inv_d), A = qm31_mul(f.a, D);
-
-    // lane i: the coefficients of p_i
-    qm31 c0, c1 = zero, c2 = zero, c3 = zero;
-    if (act) {
-        const qm31 ca = qm31_mul(corr, A);
-        const qm31 g0 = qm31_mul(f0, ca), g2 = qm31_mul(f2, ca);
-        const qm31 w0 = qm31_neg(qm31_mul_m31(g0, kHalf)), w2 = qm31_neg(qm31_mul_m31(g2, kHalf));
-        const qm31 w1 = qm31_mul(qm31_sub(qm31_mul(claim, D), qm31_mul(g0, one_y)), inv_y);
-        const qm31 q2 = qm31_add(qm31_add(w0, w1), w2);
-        const qm31 w01 = qm31_add(w0, w1);                            // q1 = -(3 w0 + 2 w1 + w2) = -(w0 + (w0 + w1) + q2)
-        const qm31 q1 = qm31_neg(qm31_add(qm31_add(w0, w01), q2));
-        c0 = qm31_mul(b, g0);                                         // -b q0, q0 = 2 w0 = -g0
-        c1 = qm31_sub(qm31_neg(g0), qm31_mul(b, q1));
-        c2 = qm31_sub(q1, qm31_mul(b, q2));
-        c3 = q2;
-    } else {
-        c0 = qm31_mul_m31(claim, kHalf);                              // the constant claim / 2 (zero beyond the instances)
-    }
-
-    // rp = sum_i alpha^i p_i (sumcheck.ts combine): alpha^lane by square and multiply, then a sum over the wave
-    qm31 pw = one, sq = f.alpha;
-#pragma unroll 1
-    for (u32 k = 0; ((f.n - 1) >> k) != 0; k++) {
-        if ((lane >> k) & 1u) pw = qm31_mul(pw, sq);
-        sq = qm31_mul(sq, sq);
-    }
-    u32 rp[16];
-    {
-        const qm31 t0 = qm31_mul(c0, pw);
-        qm31 t1 = zero, t2 = zero, t3 = zero;
-        if (act) { t1 = qm31_mul(c1, pw); t2 = qm31_mul(c2, pw); t3 = qm31_mul(c3, pw); }
-        rp[0] = t0.a; rp[1] = t0.b; rp[2] = t0.c; rp[3] = t0.d; rp[4] = t1.a; rp[5] = t1.b; rp[6] = t1.c; rp[7] = t1.d;
-        rp[8] = t2.a; rp[9] = t2.b; rp[10] = t2.c; rp[11] = t2.d; rp[12] = t3.a; rp[13] = t3.b; rp[14] = t3.c; rp[15] = t3.d;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < 16; k++) rp[k] = m31_add(rp[k], (u32)__shfl_xor((int)rp[k], off, 64));
-#pragma unroll
-    for (int k = 0; k < 16; k++) rp[k] = (u32)__builtin_amdgcn_readfirstlane((int)rp[k]);
-    u32 n_coeffs = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-        if (rp[4 * j] | rp[4 * j + 1] | rp[4 * j + 2] | rp[4 * j + 3]) n_coeffs = j + 1;
-
-    // mix_felts(rp.coeffs[:n_coeffs]) (channel/blake2.ts:113-118): Blake2s over digest || 16 n_coeffs bytes.  The words of the
-    // trimmed coefficients are zero, which is the padding of the last block.
-    {
-        u32 h[8] = {IV0 ^ 0x01010020u, IV1, IV2, IV3, IV4, IV5, IV6, IV7};
-        u32 m[16];
-#pragma unroll
-        for (int k = 0; k < 8; k++) { m[k] = d[k]; m[8 + k] = rp[k]; }
-        const u32 len = 32u + 16u * n_coeffs;
-        if (n_coeffs <= 2) {
-            b2s_compress(h, m, len, true);
+    for (int k = 0; k < 8; k++) d[k] = gload1(t.chan, k);
+    u32 n_chal = gload1(t.chan, 8), n_sent = gload1(t.chan, 9);
+    // lane j: its claims to verify — the output values where it enters, else what the layer below left
+    qm31 c0 = zero, c1 = zero;
+    u32 n_felts = 0, shift = 0;
+    if (in) {
+        const lane_ptr me = (lane_ptr)t.lanes + lane;
+        const u32 inst = me->inst;
+        const bool gp = me->kind == TSTWO_GKR_GRAND_PRODUCT;
+        n_felts = gp ? 1u : 2u;
+        shift = me->shift;
+        if (me->enter) {
+            const u32 *src[8];
+            load_lane_ptrs(me->out_src, src);
+            const qm31 den = {gload1(src[4]), gload1(src[5]), gload1(src[6]), gload1(src[7])};
+            if (gp) {
+                c0 = den;
+            } else {
+                c0 = {gload1(src[0]), gload1(src[1]), gload1(src[2]), gload1(src[3])};
+                c1 = den;
+            }
+            gstore4(t.out_claims, 8 * inst, u4_of(c0));
+            gstore4(t.out_claims, 8 * inst + 4, u4_of(c1));
         } else {
-            b2s_compress(h, m, 64u, false);
-#pragma unroll
-            for (int k = 0; k < 8; k++) { m[k] = rp[8 + k]; m[8 + k] = 0u; }
-            b2s_compress(h, m, len, true);
+            c0 = q_of(gload4(t.claims, 8 * inst));
+            c1 = q_of(gload4(t.claims, 8 * inst + 4));
         }
+    }
+    // one mix per lane, in lane order
+#pragma unroll 1
+    for (u32 j = 0; j < t.n; j++) {
+        const qm31 f[4] = {bcast_q(c0, j), bcast_q(c1, j), zero, zero};
+        const u32 nf = (u32)__builtin_amdgcn_readfirstlane(__shfl((int)n_felts, (int)j, 64));
+        chan_mix_felts<false>(d, n_chal, n_sent, f, nf);
+    }
+    u32 fa[4] = {0u, 0u, 0u, 0u}, fl[4] = {0u, 0u, 0u, 0u};
+    chan_mix_draw(d, n_chal, n_sent, nullptr, false, true, fa);
+    chan_mix_draw(d, n_chal, n_sent, nullptr, false, true, fl);
+    const qm31 lambda = {fl[0], fl[1], fl[2], fl[3]};
+    if (in) {
+        // random_linear_combination(claims, lambda) 2^shift (sumcheck.ts proveBatch doubles the claims of the shorter oracles)
+        const qm31 claim = qm31_mul_m31(qm31_add(c0, qm31_mul(c1, lambda)), 1u << (shift % 31u));      // 2^31 = 1 in M31: any shift gives a reduced factor
+        gstore4(t.state, 8 * lane, u4_of(claim));
+        gstore4(t.state, 8 * lane + 4, u4_of(one));
+    }
+    // inv_eq0 of round r: 1 / prod_{j <= r} (1 - y_j).  Lane r holds y_r; an inclusive scan gives the prefix products, and every
+    // lane inverts its own in the same instruction stream (one inversion step for the layer).
+    qm31 y = zero;
+    if (lane < t.n_y) y = q_of(gload4(t.y, 4 * lane));
+    qm31 pre = lane < t.n_y ? qm31_sub(one, y) : one;
 #pragma unroll
-        for (int k = 0; k < 8; k++) d[k] = h[k];
-        n_chal += 1;
-        n_sent = 0;
+    for (int off = 1; off < 32; off <<= 1) {
+        const qm31 up = {(u32)__shfl_up((int)pre.a, off, 64), (u32)__shfl_up((int)pre.b, off, 64), (u32)__shfl_up((int)pre.c, off, 64),
+                         (u32)__shfl_up((int)pre.d, off, 64)};
+        if (lane >= (u32)off) pre = qm31_mul(pre, up);
+    }
+    const qm31 inv = qm31_inv(pre);                     // a fixed power chain: zero in, zero out (and the status bit below)
+    const bool bad = lane < t.n_y && (degenerate_y(y) || qm31_is_zero(pre));
+    if (lane < t.n_y) gstore4(t.inv, 4 * lane, u4_of(inv));
+    const bool any_bad = __ballot(bad) != 0ull;
+    if (lane == 0) {
+        if (any_bad) __hip_atomic_fetch_or(t.status, kStatusDegenerate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        gstore4(t.scalars, 0, make_uint4(fa[0], fa[1], fa[2], fa[3]));
+        gstore4(t.scalars, 4, u4_of(lambda));
+        if (t.n_y) gstore4(t.scalars, 8, u4_of(qm31_sub(one, y)));      // eq([0], [y_0]): the v of EqEvals.generate
+#pragma unroll
+        for (int k = 0; k < 8; k++) gstore1(t.chan, k, d[k]);
+        gstore1(t.chan, 8, n_chal);
+        gstore1(t.chan, 9, n_sent);
+    }
+}
+
+struct EndArgs {
+    u32 *chan;
+    const tstwo_gkr_lane *lanes;
+    u32 n;
+    u32 *masks, *claims, *ch_out;
+};
+__global__ void __launch_bounds__(64) k_gkr_layer_end(EndArgs t) {
+    using namespace b2s;
+    const u32 lane = threadIdx.x;
+    const bool in = lane < t.n;
+    const qm31 zero = {0u, 0u, 0u, 0u}, one = {1u, 0u, 0u, 0u};
+    u32 d[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) d[k] = gload1(t.chan, k);
+    u32 n_chal = gload1(t.chan, 8), n_sent = gload1(t.chan, 9);
+    // lane j: its mask (tryIntoMask, gkr_prover.ts:353-395) — column 0 at 0 and 1, column 1 at 0 and 1
+    qm31 a0 = zero, b0 = zero, a1 = zero, b1 = zero;
+    u32 n_felts = 0, inst = 0;
+    bool gp = false;
+    if (in) {
+        const lane_ptr me = (lane_ptr)t.lanes + lane;
+        const u32 kind = me->kind;
+        inst = me->inst;
+        gp = kind == TSTWO_GKR_GRAND_PRODUCT;
+        n_felts = gp ? 2u : 4u;
+        const u32 *src[8];
+        load_lane_ptrs(me->src, src);
+        const qm31 den0 = ld_col0(src, 4, 0), den1 = ld_col0(src, 4, 1);
+        if (gp) {
+            a0 = den0; b0 = den1;
+        } else {
+            a1 = den0; b1 = den1;
+            if (kind == TSTWO_GKR_LOGUP_SINGLES) { a0 = one; b0 = one; }
+            else { a0 = ld_col0(src, 0, 0); b0 = ld_col0(src, 0, 1); }
+        }
+        gstore4(t.masks, 16 * lane, u4_of(a0));
+        gstore4(t.masks, 16 * lane + 4, u4_of(b0));
+        gstore4(t.masks, 16 * lane + 8, u4_of(a1));
+        gstore4(t.masks, 16 * lane + 12, u4_of(b1));
+    }
+#pragma unroll 1
+    for (u32 j = 0; j < t.n; j++) {
+        const qm31 f[4] = {bcast_q(a0, j), bcast_q(b0, j), bcast_q(a1, j), bcast_q(b1, j)};
+        const u32 nf = (u32)__builtin_amdgcn_readfirstlane(__shfl((int)n_felts, (int)j, 64));
+        chan_mix_felts<true>(d, n_chal, n_sent, f, nf);
     }
     u32 felt[4] = {0u, 0u, 0u, 0u};
     chan_mix_draw(d, n_chal, n_sent, nullptr, false, true, felt);
     const qm31 ch = {felt[0], felt[1], felt[2], felt[3]};
-
-    // claim_i <- p_i(ch); corr_i <- corr_i eq(ch, y) for the active instances
-    if (in) {
-        qm31 v = c0;
-        if (act) {
-            v = qm31_add(qm31_mul(qm31_add(qm31_mul(qm31_add(qm31_mul(c3, ch), c2), ch), c1), ch), c0);
-            const qm31 e = qm31_add(qm31_mul(ch, y), qm31_mul(qm31_sub(one, ch), one_y));
-            gstore4(f.state, 8 * lane + 4, u4_of(qm31_mul(corr, e)));
-        }
-        gstore4(f.state, 8 * lane, u4_of(v));
+    if (in) {                                           // reduceAtPoint: foldMleEvals of each column
+        gstore4(t.claims, 8 * inst, u4_of(fold_q(ch, a0, b0)));
+        gstore4(t.claims, 8 * inst + 4, u4_of(gp ? zero : fold_q(ch, a1, b1)));
     }
     if (lane == 0) {
-        gstore4(f.poly_out, 0, make_uint4(n_coeffs, 0u, 0u, 0u));
+        gstore4(t.ch_out, 0, u4_of(ch));
 #pragma unroll
-        for (int j = 0; j < 4; j++) gstore4(f.poly_out, 4 + 4 * j, make_uint4(rp[4 * j], rp[4 * j + 1], rp[4 * j + 2], rp[4 * j + 3]));
-        gstore4(f.ch_out, 0, u4_of(ch));
-#pragma unroll
-        for (int k = 0; k < 8; k++) gstore1(f.chan, k, d[k]);
-        gstore1(f.chan, 8, n_chal);
-        gstore1(f.chan, 9, n_sent);
+        for (int k = 0; k < 8; k++) gstore1(t.chan, k, d[k]);
+        gstore1(t.chan, 8, n_chal);
+        gstore1(t.chan, 9, n_sent);
     }
 }
 
 bool q_is(const u32 v[4], u32 a) { return v[0] == a && v[1] == 0 && v[2] == 0 && v[3] == 0; }
+
+// ---- checks + launches of the entries that take their scalars from device memory (the public entries and tstwo_gkr_prove_batch)
+bool dev_scalar_ok(const void *p) { return p && aligned16(p); }
+
+int eq_evals_dev(const u32 *y_dev, u32 n_y, const u32 *v_dev, u32 *const out[4]) {
+    if (n_y > kMaxLog) return set_error(TSTWO_ERR_BAD_ARG, "eq table too large");
+    if (!dev_scalar_ok(v_dev) || (n_y && !dev_scalar_ok(y_dev))) return set_error(TSTWO_ERR_BAD_ARG, "eq table: null or misaligned device scalar");
+    TSTWO_REQUIRE_TABLE(out, 4);
+    const u32 lo = n_y / 2, hi = n_y - lo, nt = (1u << hi) + (1u << lo);
+    if (int rc = ensure_scratch(kTabOff + (size_t)nt * sizeof(qm31))) return rc;
+    qm31 *tab = (qm31 *)((uint8_t *)ctx().scratch + kTabOff);
+    hipLaunchKernelGGL(k_eq_tables_dev, dim3(ceil_div(nt, kThreads)), dim3(kThreads), 0, ctx().stream, y_dev, v_dev, hi, lo, tab);
+    TSTWO_LAUNCH_CHECK();
+    const Soa4 o = soa(out);
+    const u32 n = 1u << n_y;
+    if (lo >= 2 && all_aligned16(o)) hipLaunchKernelGGL(k_eq_expand<4>, dim3(grid_for(n / 4, 32)), dim3(kThreads), 0, ctx().stream, tab, hi, lo, o);
+    else hipLaunchKernelGGL(k_eq_expand<1>, dim3(grid_for(n, 32)), dim3(kThreads), 0, ctx().stream, tab, hi, lo, o);
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
+}
+
+int round_finish_dev(u32 *chan, const u32 *sums, u32 *state, u32 n_instances, uint64_t active_mask, const u32 *y_dev, const u32 *a_dev,
+                     const u32 *alpha_dev, u32 *round_poly_out, u32 *challenge_out, u32 *status) {
+    TSTWO_REQUIRE_PTRS(chan, sums, state, round_poly_out, challenge_out, status);
+    if (n_instances == 0 || n_instances > 64) return set_error(TSTWO_ERR_BAD_ARG, "sum-check: 1 to 64 instances per round");
+    if (((uintptr_t)chan & 3) || ((uintptr_t)status & 3) || !aligned16(sums) || !aligned16(state) || !aligned16(round_poly_out) ||
+        !aligned16(challenge_out))
+        return set_error(TSTWO_ERR_BAD_ARG, "sum-check: misaligned device pointer");
+    if (!dev_scalar_ok(y_dev) || !dev_scalar_ok(a_dev) || !dev_scalar_ok(alpha_dev))
+        return set_error(TSTWO_ERR_BAD_ARG, "sum-check: null or misaligned device scalar");
+    FinishArgs f{};
+    f.chan = chan; f.sums = sums; f.state = state; f.n = n_instances;
+    f.mask = n_instances == 64 ? active_mask : active_mask & ((1ull << n_instances) - 1);
+    f.poly_out = round_poly_out; f.ch_out = challenge_out;
+    const FinishDev d{y_dev, a_dev, alpha_dev, status};
+    hipLaunchKernelGGL(k_gkr_round_finish_dev, dim3(1), dim3(64), 0, ctx().stream, f, d);
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
+}
+
+int layer_begin(u32 *chan, const tstwo_gkr_lane *lanes, u32 n, const u32 *claims, u32 *out_claims, u32 *state, u32 *scalars, const u32 *y_dev,
+                u32 n_y, u32 *inv, u32 *status) {
+    TSTWO_REQUIRE_PTRS(chan, lanes, claims, out_claims, state, scalars, inv, status);
+    if (n == 0 || n > 64) return set_error(TSTWO_ERR_BAD_ARG, "layer begin: 1 to 64 lanes");
+    if (n_y > kMaxLog) return set_error(TSTWO_ERR_BAD_ARG, "layer begin: more than 28 coordinates");
+    if (n_y && !dev_scalar_ok(y_dev)) return set_error(TSTWO_ERR_BAD_ARG, "layer begin: null or misaligned device scalar");
+    if (((uintptr_t)chan & 3) || ((uintptr_t)status & 3) || ((uintptr_t)lanes & 7) || !aligned16(claims) || !aligned16(out_claims) ||
+        !aligned16(state) || !aligned16(scalars) || !aligned16(inv))
+        return set_error(TSTWO_ERR_BAD_ARG, "layer begin: misaligned device pointer");
+    const BeginArgs t{chan, lanes, n, claims, out_claims, state, scalars, y_dev, n_y, inv, status};
+    hipLaunchKernelGGL(k_gkr_layer_begin, dim3(1), dim3(64), 0, ctx().stream, t);
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
+}
+
+int layer_end(u32 *chan, const tstwo_gkr_lane *lanes, u32 n, u32 *masks, u32 *claims, u32 *ch_out) {
+    TSTWO_REQUIRE_PTRS(chan, lanes, masks, claims, ch_out);
+    if (n == 0 || n > 64) return set_error(TSTWO_ERR_BAD_ARG, "layer end: 1 to 64 lanes");
+    if (((uintptr_t)chan & 3) || ((uintptr_t)lanes & 7) || !aligned16(masks) || !aligned16(claims) || !aligned16(ch_out))
+        return set_error(TSTWO_ERR_BAD_ARG, "layer end: misaligned device pointer");
+    const EndArgs t{chan, lanes, n, masks, claims, ch_out};
+    hipLaunchKernelGGL(k_gkr_layer_end, dim3(1), dim3(64), 0, ctx().stream, t);
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
+}
+
+// ---------------------------------------------------------------- prove_batch in one call (gkr_prover.ts:440-580)
+// One instance's layer as the kernels see it: 4 numerator pointers (a base column repeats its one pointer; null without
+// numerators) and 4 denominator pointers.
+struct LayerView {
+    u32 kind;
+    u32 *num[4], *den[4];
+};
+// generated layer k of instance p inside the pool: all LogUp kinds generate LogUpGeneric layers (numerators, then denominators)
+LayerView generated_layer(u32 *pool, const GkrPlanInst &p, u32 k) {
+    LayerView v{};
+    v.kind = p.kind == kGkrGrandProduct ? kGkrGrandProduct : kGkrGeneric;
+    u32 *base = pool + gkr_layer_off(p, k);
+    const uint64_t w = gkr_col_words(k);
+    for (int c = 0; c < 4; c++) {
+        v.num[c] = p.gen_cols == 8 ? base + c * w : nullptr;
+        v.den[c] = base + (p.gen_cols == 8 ? 4 + c : c) * w;
+    }
+    return v;
+}
+LayerView input_layer(const tstwo_gkr_instance &in) {
+    LayerView v{};
+    v.kind = in.kind;
+    for (int c = 0; c < 4; c++) {
+        // never written: the plan folds an input into the instance's own buffers (GKR_FOLD_NEW)
+        v.num[c] = in.kind == kGkrGeneric ? (u32 *)in.num[c] : in.kind == kGkrMultiplicities ? (u32 *)in.num[0] : nullptr;
+        v.den[c] = (u32 *)in.den[c];
+    }
+    return v;
+}
+int launch_next_layer(const LayerView &in, u32 log_n, const LayerView &out) {
+    const u32 n_out = 1u << (log_n - 1);
+    const dim3 g(grid_for(n_out, 32)), b(kThreads);
+    const CSoa4 num = csoa(in.num), den = csoa(in.den);
+    const Soa4 onum = soa(out.num), oden = soa(out.den);
+    hipStream_t st = ctx().stream;
+    switch (in.kind) {
+        case kGkrGrandProduct: hipLaunchKernelGGL(k_next_layer<TSTWO_GKR_GRAND_PRODUCT>, g, b, 0, st, CSoa4{}, den, Soa4{}, oden, n_out); break;
+        case kGkrGeneric: hipLaunchKernelGGL(k_next_layer<TSTWO_GKR_LOGUP_GENERIC>, g, b, 0, st, num, den, onum, oden, n_out); break;
+        case kGkrMultiplicities: hipLaunchKernelGGL(k_next_layer<TSTWO_GKR_LOGUP_MULTIPLICITIES>, g, b, 0, st, num, den, onum, oden, n_out); break;
+        default: hipLaunchKernelGGL(k_next_layer<TSTWO_GKR_LOGUP_SINGLES>, g, b, 0, st, CSoa4{}, den, onum, oden, n_out); break;
+    }
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
+}
+void fill_lane_ptrs(const u32 *(&dst)[8], const LayerView &v) {
+    for (int c = 0; c < 4; c++) { dst[c] = v.num[c]; dst[4 + c] = v.den[c]; }
+}
+
+int plan_of(const tstwo_gkr_instance *instances, size_t n, GkrPlan &pl) {
+    if (n && !instances) return set_error(TSTWO_ERR_BAD_ARG, "null host argument");
+    u32 kinds[kGkrMaxInstances], logs[kGkrMaxInstances];
+    for (size_t i = 0; i < n && i < kGkrMaxInstances; i++) { kinds[i] = instances[i].kind; logs[i] = instances[i].log_n; }
+    if (const char *why = gkr_plan(kinds, logs, n, pl)) return set_error(TSTWO_ERR_BAD_ARG, why);
+    return TSTWO_OK;
+}
+
+// Everything the call allocated goes back to the allocator on every way out, behind a synchronisation (launches may be in flight).
+struct ProveBuffers {
+    void *pool = nullptr, *block = nullptr, *lanes = nullptr;
+    ~ProveBuffers() {
+        (void)hipStreamSynchronize(ctx().stream);
+        for (void *p : {pool, block, lanes}) if (p) tstwo_free(p);
+    }
+};
+
+int prove_batch_run(const u32 chan[10], const tstwo_gkr_instance *instances, const GkrPlan &pl, u32 *block_host) {
+    const u32 n = pl.n_inst, n_layers = pl.n_layers;
+    ProveBuffers mem;
+    if (int rc = tstwo_malloc(&mem.pool, pl.pool_words * 4)) return rc;
+    if (int rc = tstwo_malloc(&mem.block, (size_t)pl.block_words * 4)) return rc;
+    size_t n_lanes_total = 0;
+    for (const GkrPlanLayer &l : pl.layers) n_lanes_total += l.n_active;
+    if (int rc = tstwo_malloc(&mem.lanes, n_lanes_total * sizeof(tstwo_gkr_lane))) return rc;
+    if (int rc = ensure_scratch(kTabOff + ((size_t)2 << (kMaxLog / 2 + 1)) * sizeof(qm31))) return rc;
+    u32 *const pool = (u32 *)mem.pool, *const blk = (u32 *)mem.block;
+    hipStream_t st = ctx().stream;
+
+    // the layers of every instance: [0 .. log_n) generated, [log_n] the caller's
+    std::vector<std::vector<LayerView>> lay(n);
+    u32 widest = 0;                                      // an instance with n_layers variables: its dead layers hold the eq tables
+    for (u32 i = 0; i < n; i++) {
+        const GkrPlanInst &p = pl.inst[i];
+        for (u32 k = 0; k < p.log_n; k++) lay[i].push_back(generated_layer(pool, p, k));
+        lay[i].push_back(input_layer(instances[i]));
+        if (p.log_n == n_layers && pl.inst[widest].log_n != n_layers) widest = i;
+        for (u32 k = p.log_n; k >= 1; k--)
+            if (int rc = launch_next_layer(lay[i][k], k, lay[i][k - 1])) return rc;
+    }
+    TSTWO_HIP(hipMemsetAsync(blk, 0, (size_t)pl.block_words * 4, st));
+    TSTWO_HIP(hipMemcpyAsync(blk + pl.chan_off, chan, 10 * sizeof(u32), hipMemcpyHostToDevice, st));
+
+    // the lanes of every layer, known before anything runs: where each mask will lie once the layer's folds are done
+    std::vector<tstwo_gkr_lane> lanes(n_lanes_total);
+    std::vector<size_t> lane0(n_layers);
+    {
+        size_t at = 0;
+        for (u32 L = 0; L < n_layers; L++) {
+            lane0[L] = at;
+            for (u32 i = 0; i < n; i++) {
+                const GkrPlanInst &p = pl.inst[i];
+                const int n_v = gkr_n_v(p, L);
+                if (n_v < 0) continue;
+                tstwo_gkr_lane &ln = lanes[at++];
+                ln = tstwo_gkr_lane{};
+                const bool input = (u32)n_v + 1 == p.log_n;
+                // the reduced layer ends as 2 points: in place for a generated layer, in the dead layer below for an input that
+                // was folded (n_v >= 1), the input itself where it has one variable
+                const LayerView &src = input && n_v >= 1 ? lay[i][p.log_n - 1] : lay[i][n_v + 1];
+                const u32 kind = input ? (p.kind == kGkrMultiplicities ? kGkrGeneric : p.kind) : src.kind;
+                fill_lane_ptrs(ln.src, src);
+                ln.inst = i; ln.kind = kind; ln.shift = L - (u32)n_v; ln.enter = n_v == 0;
+                fill_lane_ptrs(ln.out_src, lay[i][0]);
+            }
+        }
+    }
+    TSTWO_HIP(hipMemcpyAsync(mem.lanes, lanes.data(), n_lanes_total * sizeof(tstwo_gkr_lane), hipMemcpyHostToDevice, st));
+    const tstwo_gkr_lane *lanes_dev = (const tstwo_gkr_lane *)mem.lanes;
+
+    u32 *const status = blk + pl.status_off, *const chan_dev = blk + pl.chan_off;
+    for (u32 L = 0; L < n_layers; L++) {
+        const GkrPlanLayer &gl = pl.layers[L];
+        u32 *const ood_cur = blk + pl.ood_off[L & 1], *const ood_next = blk + pl.ood_off[(L + 1) & 1];
+        const tstwo_gkr_lane *ld = lanes_dev + lane0[L];
+        if (int rc = layer_begin(chan_dev, ld, gl.n_active, blk + pl.ctv_off, blk + pl.out_off, blk + pl.state_off, blk + pl.alpha_off, ood_cur,
+                                 L, blk + pl.inv_off, status))
+            return rc;
+        // EqEvals.generate(ood): eq((0, x), y) = genEqEvals(y[1:], 1 - y[0]), into the widest instance's dead layer of L - 1 variables
+        const LayerView eqv = L ? lay[widest][L - 1] : LayerView{};
+        if (L)
+            if (int rc = eq_evals_dev(ood_cur + 4, L - 1, blk + pl.eqv_off, eqv.den)) return rc;
+        // per lane: the layer being reduced, and the challenge not yet applied to it
+        struct Cur { LayerView v; u32 n_vars; const u32 *pending; u32 inst; };
+        std::vector<Cur> cur;
+        for (u32 j = 0; j < gl.n_active; j++) {
+            const u32 i = lanes[lane0[L] + j].inst;
+            const u32 n_v = (u32)gkr_n_v(pl.inst[i], L);
+            cur.push_back({lay[i][n_v + 1], n_v + 1, nullptr, i});
+        }
+        auto target = [&](const Cur &c, GkrFold how) {
+            return how == GKR_FOLD_IN_PLACE ? c.v : lay[c.inst][pl.inst[c.inst].log_n - 1];
+        };
+        for (u32 rnd = 0; rnd < L; rnd++) {
+            const u32 rem = L - rnd;
+            const uint64_t mask = gkr_round_lanes(pl, L, rem);
+            for (u32 j = 0; j < gl.n_active; j++) {
+                if (!((mask >> j) & 1)) continue;
+                Cur &c = cur[j];
+                const GkrFold how = gkr_round_fold(pl, pl.inst[c.inst], L, rem);
+                u32 *const slot = blk + pl.sums_off + 8 * j;
+                if (how == GKR_NO_FOLD) {
+                    if (int rc = gkr_sum(c.v.kind, eqv.den, c.v.num, c.v.den, nullptr, nullptr, rem, nullptr, nullptr, nullptr, slot, false,
+                                         blk + pl.lambda_off))
+                        return rc;
+                } else {
+                    const LayerView to = target(c, how);
+                    if (int rc = gkr_sum(c.v.kind, eqv.den, c.v.num, c.v.den, to.num, to.den, rem, nullptr, c.pending, nullptr, slot, true,
+                                         blk + pl.lambda_off))
+                        return rc;
+                    const bool had_num = c.v.kind == kGkrGeneric || c.v.kind == kGkrMultiplicities;
+                    const u32 kind = c.v.kind == kGkrMultiplicities ? kGkrGeneric : c.v.kind;
+                    c.v = to;
+                    c.v.kind = kind;
+                    if (!had_num) for (int k = 0; k < 4; k++) c.v.num[k] = nullptr;
+                    c.n_vars--;
+                }
+                c.pending = ood_next + 4 * rnd;              // the challenge this round is about to draw
+            }
+            if (int rc = round_finish_dev(chan_dev, blk + pl.sums_off, blk + pl.state_off, gl.n_active, mask, ood_cur + 4 * rnd,
+                                          blk + pl.inv_off + 4 * rnd, blk + pl.alpha_off, blk + gl.poly_off + 20 * rnd, ood_next + 4 * rnd, status))
+                return rc;
+        }
+        // the last challenge of the layer: a plain fold leaves the 2-point layer the mask is read from
+        for (Cur &c : cur) {
+            if (!c.pending) continue;
+            const LayerView to = target(c, gkr_last_fold(pl, pl.inst[c.inst], L));
+            if (c.v.kind == kGkrGeneric || c.v.kind == kGkrMultiplicities)
+                if (int rc = mle_fold(c.v.kind == kGkrMultiplicities, c.v.num, c.n_vars, nullptr, c.pending, to.num)) return rc;
+            if (int rc = mle_fold(false, c.v.den, c.n_vars, nullptr, c.pending, to.den)) return rc;
+        }
+        if (int rc = layer_end(chan_dev, ld, gl.n_active, blk + gl.mask_off, blk + pl.ctv_off, ood_next + 4 * L)) return rc;
+    }
+    TSTWO_HIP(hipMemcpyAsync(block_host, blk, (size_t)pl.block_words * 4, hipMemcpyDeviceToHost, st));
+    TSTWO_HIP(hipStreamSynchronize(st));
+    if (block_host[pl.status_off] & kStatusDegenerate) return set_error(TSTWO_ERR_BAD_ARG, "sum-check: degenerate eq point");
+    return TSTWO_OK;
+}
 
 }  // namespace
 
@@ -652,6 +989,69 @@ int tstwo_mle_fix_first_variable_base_dev(const u32 *in, u32 log_n, const u32 *r
 int tstwo_mle_fix_first_variable_secure_dev(const u32 *const in[4], u32 log_n, const u32 *r_dev, u32 *const out[4]) {
     TSTWO_REQUIRE_READY();
     return mle_fold(false, in, log_n, nullptr, r_dev, out);
+}
+
+int tstwo_gkr_gen_eq_evals_dev(const u32 *y_dev, u32 n_y, const u32 *v_dev, u32 *const out[4]) {
+    TSTWO_REQUIRE_READY();
+    return eq_evals_dev(y_dev, n_y, v_dev, out);
+}
+
+int tstwo_gkr_sum_poly_async_ldev(u32 kind, const u32 *const eq[4], const u32 *const num[4], const u32 *const den[4], u32 n_vars,
+                                  const u32 *lambda_dev, u32 *out_dev) {
+    TSTWO_REQUIRE_READY();
+    TSTWO_REQUIRE_PTRS(out_dev, lambda_dev);
+    return gkr_sum(kind, eq, num, den, nullptr, nullptr, n_vars, nullptr, nullptr, nullptr, out_dev, false, lambda_dev);
+}
+
+int tstwo_gkr_round_dev_ldev(u32 kind, const u32 *const eq[4], const u32 *const num[4], const u32 *const den[4], u32 *const out_num[4],
+                             u32 *const out_den[4], u32 n_vars, const u32 *r_dev, const u32 *lambda_dev, u32 *out_dev) {
+    TSTWO_REQUIRE_READY();
+    TSTWO_REQUIRE_PTRS(out_dev, r_dev, lambda_dev);
+    return gkr_sum(kind, eq, num, den, out_num, out_den, n_vars, nullptr, r_dev, nullptr, out_dev, true, lambda_dev);
+}
+
+int tstwo_gkr_round_finish_dev(u32 *chan, const u32 *sums, u32 *state, u32 n_instances, uint64_t active_mask, const u32 *y_k_dev,
+                               const u32 *inv_eq0_dev, const u32 *alpha_dev, u32 *round_poly_out, u32 *challenge_out, u32 *status) {
+    TSTWO_REQUIRE_READY();
+    return round_finish_dev(chan, sums, state, n_instances, active_mask, y_k_dev, inv_eq0_dev, alpha_dev, round_poly_out, challenge_out, status);
+}
+
+int tstwo_gkr_layer_begin(u32 *chan, const tstwo_gkr_lane *lanes_dev, u32 n_lanes, const u32 *claims, u32 *output_claims, u32 *state,
+                          u32 *scalars_out, const u32 *y_dev, u32 n_y, u32 *inv_eq0_out, u32 *status) {
+    TSTWO_REQUIRE_READY();
+    return layer_begin(chan, lanes_dev, n_lanes, claims, output_claims, state, scalars_out, y_dev, n_y, inv_eq0_out, status);
+}
+
+int tstwo_gkr_layer_end(u32 *chan, const tstwo_gkr_lane *lanes_dev, u32 n_lanes, u32 *masks_out, u32 *claims, u32 *challenge_out) {
+    TSTWO_REQUIRE_READY();
+    return layer_end(chan, lanes_dev, n_lanes, masks_out, claims, challenge_out);
+}
+
+int tstwo_gkr_prove_batch_words(const tstwo_gkr_instance *instances, size_t n_instances, size_t *block_words) {
+    if (!block_words) return set_error(TSTWO_ERR_BAD_ARG, "null host argument");
+    GkrPlan pl;
+    if (int rc = plan_of(instances, n_instances, pl)) return rc;
+    *block_words = pl.block_words;
+    return TSTWO_OK;
+}
+
+int tstwo_gkr_prove_batch(const u32 chan[10], const tstwo_gkr_instance *instances, size_t n_instances, u32 *block, size_t block_words) {
+    TSTWO_REQUIRE_READY();
+    if (!chan || !block) return set_error(TSTWO_ERR_BAD_ARG, "null host argument");
+    GkrPlan pl;
+    if (int rc = plan_of(instances, n_instances, pl)) return rc;
+    if (block_words < pl.block_words) return set_error(TSTWO_ERR_BAD_ARG, "prove_batch: the block is too small (tstwo_gkr_prove_batch_words)");
+    for (size_t i = 0; i < n_instances; i++) {
+        const tstwo_gkr_instance &in = instances[i];
+        const int n_num = in.kind == kGkrGeneric ? 4 : in.kind == kGkrMultiplicities ? 1 : 0;
+        TSTWO_REQUIRE_TABLE(in.den, 4);
+        TSTWO_REQUIRE_TABLE(in.num, (size_t)n_num);
+        for (int c = 0; c < 4; c++)
+            if (((uintptr_t)in.den[c] & 3) || (c < n_num && ((uintptr_t)in.num[c] & 3)))
+                return set_error(TSTWO_ERR_BAD_ARG, "prove_batch: misaligned device pointer");
+    }
+    if (stream_is_capturing()) return set_error(TSTWO_ERR_BAD_ARG, "prove_batch during graph capture (it reads its result back)");
+    return prove_batch_run(chan, instances, pl, block);
 }
 
 }  // extern "C"

@@ -11,7 +11,9 @@ what the host would do between two rounds (round polynomials, their combination,
 leaves the challenge in device memory for the next round's fold; per layer one upload and one read-back (channel, round
 polynomials, assignment, masks).  Elsewhere, and with device_rounds=False, the protocol of a round runs on the host: one read-back
 per round (the (f(0), f(2)) slots of every active instance) and one per layer (the 2-point masks).  The first read-back also takes
-every instance's output values and first mask.
+every instance's output values and first mask.  prove_batch(one_call=True) hands the whole proof to tstwo_gkr_prove_batch: the
+transcript between the layers stays on the device too, and one block (channel, claims, round polynomials, masks, the final point)
+is read back at the end.
 
 The two ends: logup_input_layer builds a LogUp input layer from M31 trace columns (denominators sum_i alpha^i col_i - z by
 tstwo_gkr_logup_denominators; numerators none, a base column or a secure MLE), and verify_input_claims checks what
@@ -721,9 +723,87 @@ def device_rounds_supported(channel, n_instances: int) -> bool:
     return isinstance(channel, Blake2sChannel) and not channel.ts_compat and n_instances <= MAX_DEVICE_INSTANCES
 
 
-def prove_batch(channel, input_layer_by_instance, device_rounds=None):
+def one_call_layout(n_vars_by_instance):
+    """Word offsets of what tstwo_gkr_prove_batch leaves in its block (include/tstwo_hip.h; csrc/gkr_plan.h): a dict with `status`,
+    `claims`, `outputs` (8 words per instance), `ood` (the final point), per layer `polys[L]` (20 words a round), `masks[L]` (16
+    words per active instance, in instance order) and `active[L]` (those instances), and `words`, the block's size."""
+    nv = list(n_vars_by_instance)
+    n, n_layers = len(nv), max(nv)
+    claims = 32 + 16 * n
+    ood0 = claims + 16 * n
+    off = ood0 + 12 * n_layers
+    polys, masks, active = [], [], []
+    for layer in range(n_layers):
+        act = [i for i in range(n) if nv[i] >= n_layers - layer]
+        polys.append(off)
+        masks.append(off + 20 * layer)
+        active.append(act)
+        off += 20 * layer + 16 * len(act)
+    return {"status": 16, "claims": claims, "outputs": claims + 8 * n, "ood": ood0 + 4 * n_layers * (n_layers & 1), "polys": polys,
+            "masks": masks, "active": active, "words": off}
+
+
+def _prove_batch_one_call(channel, layers_in):
+    """prove_batch through tstwo_gkr_prove_batch: one library call, one read-back.  The refusals of the other two paths are raised
+    here, before the call, with their exceptions."""
+    n_inst = len(layers_in)
+    if not device_rounds_supported(channel, n_inst):
+        raise ValueError("one_call needs a Blake2sChannel with the Rust draw semantics and at most 64 instances")
+    nv = [lay.n_variables() for lay in layers_in]
+    if min(nv) == 0:
+        raise ValueError("Some output claims were not set during proving (an input layer of 0 variables is an output layer)")
+    for lay in layers_in:
+        if lay.kind == LOGUP_MULTIPLICITIES and lay.n_variables() == 1:
+            raise NotImplementedError("LogUpMultiplicities should never reach tryIntoMask")
+    inst = (L.GkrInstance * n_inst)()
+    for rec, lay in zip(inst, layers_in):
+        rec.kind, rec.log_n = lay.kind, lay.n_variables()
+        num = lay.num.ptr_list() if lay.num is not None else []
+        rec.num = (L.vp * 4)(*(num + [None] * (4 - len(num))))
+        rec.den = (L.vp * 4)(*lay.den.ptr_list())
+    L.ensure_init()
+    words = C.c_size_t(0)
+    L.call("tstwo_gkr_prove_batch_words", inst, n_inst, C.byref(words))
+    lay_out = one_call_layout(nv)
+    assert words.value == lay_out["words"], "the block layout of include/tstwo_hip.h"
+    block = np.zeros(words.value, dtype=np.uint32)
+    digest = np.frombuffer(channel.digest(), dtype="<u4")
+    chan = L.u32x(list(digest) + [channel.n_challenges, channel.n_sent])
+    try:
+        L.call("tstwo_gkr_prove_batch", chan, inst, n_inst, block.ctypes.data_as(L.u32p), words.value)
+    except L.TstwoError as e:
+        if str(e) == "sum-check: degenerate eq point":
+            raise ZeroDivisionError("0 has no inverse") from None
+        raise
+    channel._digest = block[:8].astype("<u4").tobytes()
+    channel.n_challenges, channel.n_sent = int(block[8]), int(block[9])
+    n_cols = [1 if lay.kind == GRAND_PRODUCT else 2 for lay in layers_in]
+    felts = lambda off, k: [_qs(block[off + 4 * j:off + 4 * j + 4]) for j in range(k)]          # noqa: E731
+    n_layers = max(nv)
+    masks = [[] for _ in range(n_inst)]
+    sumcheck_proofs = []
+    for layer in range(n_layers):
+        polys = []
+        for rnd in range(layer):
+            p = lay_out["polys"][layer] + 20 * rnd
+            polys.append(UnivariatePoly(felts(p + 4, int(block[p]))))
+        sumcheck_proofs.append(SumcheckProof(polys))
+        for j, i in enumerate(lay_out["active"][layer]):
+            m = felts(lay_out["masks"][layer] + 16 * j, 4)
+            masks[i].append(GkrMask([(m[0], m[1]), (m[2], m[3])][:n_cols[i]]))
+    outputs = [felts(lay_out["outputs"] + 8 * i, n_cols[i]) for i in range(n_inst)]
+    claims = [felts(lay_out["claims"] + 8 * i, n_cols[i]) for i in range(n_inst)]
+    ood = felts(lay_out["ood"], n_layers)
+    return GkrBatchProof(sumcheck_proofs, masks, outputs), GkrArtifact(ood, claims, nv)
+
+
+def prove_batch(channel, input_layer_by_instance, device_rounds=None, one_call=False):
     """Batch-proves the instances' circuits (gkr_prover.ts proveBatch).  The input layers are left untouched; every layer the
     prover generates is freed once consumed.  Returns (GkrBatchProof, GkrArtifact).
+
+    one_call: True = the whole proof in one library call (tstwo_gkr_prove_batch: the transcript stays on the device between the
+    layers, one read-back at the end); ValueError where device_rounds_supported is false.  The same proof, artifact and channel
+    state as the two paths below; device_rounds is then not looked at.
 
     device_rounds: True = the sum-check rounds run on the device (tstwo_gkr_round_finish: nothing is read back inside a layer;
     ValueError where that path cannot be taken); False = the host loop, one read-back per round; None = the device path where it
@@ -732,6 +812,8 @@ def prove_batch(channel, input_layer_by_instance, device_rounds=None):
     n_inst = len(layers_in)
     if n_inst == 0:
         raise ValueError("no instances")
+    if one_call:
+        return _prove_batch_one_call(channel, layers_in)
     if device_rounds is None:
         device_rounds = device_rounds_supported(channel, n_inst)
     elif device_rounds and not device_rounds_supported(channel, n_inst):
@@ -845,4 +927,4 @@ def prove_batch(channel, input_layer_by_instance, device_rounds=None):
 __all__ = ["GRAND_PRODUCT", "LOGUP_GENERIC", "LOGUP_MULTIPLICITIES", "LOGUP_SINGLES", "EqEvals", "GkrArtifact", "GkrBatchProof",
            "GkrInputClaimMismatch", "GkrMask", "GkrMultivariatePolyOracle", "HipGkrOps", "HipMleOps", "Layer", "Mle", "check_logup_sum",
            "correct_sum_as_poly_in_first_variable", "device_rounds_supported", "eval_mles_at_point", "fold_mle_evals", "inv_eq0_table",
-           "logup_denominators", "logup_input_layer", "prove_batch", "round_finish", "verify_input_claims"]
+           "logup_denominators", "logup_input_layer", "one_call_layout", "prove_batch", "round_finish", "verify_input_claims"]
