@@ -35,7 +35,7 @@ synchronisation on any path the shapes here take):
                  tables travel by value.
   quotients.hip  tstwo_quotients_accumulate_async, tstwo_quotients_accumulate_samples_async: constants blob into the scratch
                  through small_h2d (the blobs here are far below 16 KiB), launches, no flag read.
-  gkr.hip        tstwo_gkr_next_layer_*, tstwo_mle_fix_first_variable_*: one launch.  tstwo_gkr_sum_poly_async, tstwo_gkr_round:
+  gkr_ops.hip    tstwo_gkr_next_layer_*, tstwo_mle_fix_first_variable_*: one launch.  tstwo_gkr_sum_poly_async, tstwo_gkr_round:
                  hipMemsetAsync of the ticket in the scratch, one launch.  tstwo_gkr_gen_eq_evals: two launches via the scratch.
   air.hip        tstwo_air_wide_fib_trace, tstwo_air_constraint_quotients (coefficients by value), tstwo_air_eval_program
                  (program through small_h2d into the scratch).   logup.hip  tstwo_logup_column (descriptors likewise).

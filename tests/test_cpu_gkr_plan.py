@@ -1,6 +1,6 @@
 """The schedule of tstwo_gkr_prove_batch (no GPU): csrc/gkr_plan.h, compiled on its own with the address and undefined behaviour
-sanitizers, against tests/gkr_plan.py; what the batches of the -m gpu file reach; and the resource usage of the new kernels of
-csrc/gkr.hip, compiled for gfx950 without a device."""
+sanitizers, against tests/gkr_plan.py; what the batches of the -m gpu file reach; and the resource usage of the kernels of
+csrc/gkr_ops.hip and csrc/gkr_transcript.hip, compiled for gfx950 without a device."""
 import itertools
 import os
 import re
@@ -89,33 +89,43 @@ def test_gpu_batches_reach_every_branch():
     assert "64 instances" in GP.branches(GP.Plan(GP.named_batch("64"))) and "shift 1" in GP.branches(GP.Plan(GP.named_batch("small")))
 
 
-NEW_KERNELS = {"k_eq_tables_dev": 1, "k_sum_ldev": 6, "k_gkr_round_finish_dev": 1, "k_gkr_layer_begin": 1, "k_gkr_layer_end": 1}
+# Every kernel that takes a protocol scalar by value or from device words, by a pattern of its mangled name: (VGPRs, waves per SIMD)
+# of whichever of its two former twins (one per scalar source) was worse.  The one kernel that serves both sources is held to that.
+MERGED_KERNELS = {
+    "5k_sumILi0ELb0E": (56, 8), "5k_sumILi1ELb0E": (89, 5), "5k_sumILi2ELb0E": (73, 6), "5k_sumILi3ELb0E": (62, 8),
+    "5k_sumILi0ELb1E": (57, 8), "5k_sumILi1ELb1E": (88, 5), "5k_sumILi2ELb1E": (88, 5), "5k_sumILi3ELb1E": (61, 8),
+    "18k_gkr_round_finishE": (77, 6),
+    "11k_eq_tablesE": (64, 8),      # its twins had 30 each; a latency-bound kernel of a few blocks, held to what 8 waves per SIMD allow
+}
+KERNEL_COUNTS = {"k_eq_tables": 1, "k_eq_expand": 2, "k_next_layer": 4, "k_fold": 4, "k_sum": 8, "k_gkr_round_finish": 1, "k_gkr_layer_begin": 1,
+                 "k_gkr_layer_end": 1}
 
 
 def test_new_kernels_compile_for_gfx950_without_scratch(tmp_path):
-    """csrc/gkr.hip compiles for gfx950 without a device; the kernels that read their scalars from device memory and the two
-    transcript kernels report no scratch, and every lambda-from-device sum has the registers of its by-value twin."""
-    p = subprocess.run([B._hipcc(), *B.FLAGS, "--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-                        os.path.join(CSRC, "gkr.hip"), "-o", str(tmp_path / "gkr.o")], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-2000:]
-    usage, kernel = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"remark: \s*(.+?): (\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            kernel = usage.setdefault(m.group(2), {})
-        elif kernel is not None:
-            kernel[m.group(1)] = m.group(2)
-    for name, count in NEW_KERNELS.items():
-        found = {k: u for k, u in usage.items() if re.search(rf"\d{name}(?![a-z_])", k)}
-        assert len(found) == count, (name, sorted(found))
-        for k, u in sorted(found.items()):
-            print(k, "VGPRs", u["VGPRs"], "SGPRs", u["TotalSGPRs"], "occupancy", u["Occupancy [waves/SIMD]"], "scratch", u["ScratchSize [bytes/lane]"])
-    for k, u in usage.items():
+    """The GKR translation units compile for gfx950 without a device; there is ONE kernel per operation whether its scalars come by
+    value or from device memory, none reports scratch, and each kernel that serves both sources has no more registers and no fewer
+    waves per SIMD than the worse of the two kernels it replaced."""
+    usage = {}
+    for unit in ("gkr_ops", "gkr_transcript", "gkr_prove"):
+        p = subprocess.run([B._hipcc(), *B.FLAGS, "--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
+                            os.path.join(CSRC, unit + ".hip"), "-o", str(tmp_path / (unit + ".o"))], capture_output=True, text=True)
+        assert p.returncode == 0, p.stderr[-2000:]
+        kernel = None
+        for line in p.stderr.splitlines():
+            m = re.search(r"remark: \s*(.+?): (\S+)", line)
+            if not m:
+                continue
+            if m.group(1) == "Function Name":
+                kernel = usage.setdefault(m.group(2), {})
+            elif kernel is not None:
+                kernel[m.group(1)] = m.group(2)
+    for name, count in KERNEL_COUNTS.items():
+        found = sorted(k for k in usage if re.search(rf"\d{name}(?![a-z_])", k))
+        assert len(found) == count, (name, found)
+    assert len(usage) == sum(KERNEL_COUNTS.values()), sorted(usage)
+    for k, u in sorted(usage.items()):
+        print(k, "VGPRs", u["VGPRs"], "SGPRs", u["TotalSGPRs"], "occupancy", u["Occupancy [waves/SIMD]"], "scratch", u["ScratchSize [bytes/lane]"])
         assert u["ScratchSize [bytes/lane]"] == "0", (k, u)
-    for k, u in usage.items():
-        if "k_sum_ldev" in k:
-            assert k.endswith("SumArgsEPKj")                      # (SumArgs, const u32 *): the pointer is a parameter of its own
-            twin = k.replace("10k_sum_ldev", "5k_sum")[:-len("PKj")]
-            assert int(u["VGPRs"]) <= int(usage[twin]["VGPRs"]), (k, u["VGPRs"], usage[twin]["VGPRs"])
+    for pattern, (vgprs, waves) in MERGED_KERNELS.items():
+        (k,) = [k for k in usage if pattern in k]
+        assert int(usage[k]["VGPRs"]) <= vgprs and int(usage[k]["Occupancy [waves/SIMD]"]) >= waves, (k, usage[k], vgprs, waves)

@@ -63,9 +63,9 @@ def loop_valu(asm: str, sym: str) -> int:
 
 def sum_valu_counts():
     with tempfile.TemporaryDirectory() as td:
-        s = os.path.join(td, "gkr.s")
+        s = os.path.join(td, "gkr_ops.s")
         subprocess.check_call(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only",
-                               os.path.join(ROOT, "tstwo_amd", "csrc", "gkr.hip"), "-o", s], stderr=subprocess.DEVNULL)
+                               os.path.join(ROOT, "tstwo_amd", "csrc", "gkr_ops.hip"), "-o", s], stderr=subprocess.DEVNULL)
         asm = open(s).read()
     return {k: loop_valu(asm, v) for k, v in SUM_KERNELS.items()}
 

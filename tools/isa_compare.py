@@ -62,6 +62,9 @@ def kernels_of(obj_dir, tus):
     isa.OBJ = obj_dir            # _disasm reads the test module's object directory: point it at the side being read
     out = {}
     for tu in tus:
+        sections = subprocess.check_output([os.path.join(isa.LLVM, "llvm-readelf"), "-S", os.path.join(obj_dir, tu + ".o")], text=True)
+        if ".hip_fatbin" not in sections:         # host code only (gkr_prove): no code object, no kernels
+            continue
         with tempfile.TemporaryDirectory() as tmp:
             code = isa._disasm(tu, pathlib.Path(tmp))
             notes = _notes(os.path.join(tmp, "dev.co"))

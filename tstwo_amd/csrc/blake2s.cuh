@@ -208,6 +208,30 @@ __device__ __forceinline__ void chan_mix_draw(u32 (&d)[8], u32 &n_chal, u32 &n_s
         for (int k = 0; k < 4; k++) felt[k] = w[k] >= M31_P ? w[k] - M31_P : w[k];       // M31.reduce of a value < 2P
     }
 }
+// mix_felts (channel/blake2.ts:113-118) of the first n_felts QM31s of w (N = 8: at most 2 felts, 16: at most 4): Blake2s over
+// digest || 16 n_felts bytes, by every lane on its own (one or two compressions).  The words of w beyond the felts are zero, which
+// is the padding of the last block.
+template <int N>
+__device__ __forceinline__ void chan_mix_felts(u32 (&d)[8], u32 &n_chal, u32 &n_sent, const u32 (&w)[N], u32 n_felts) {
+    static_assert(N == 8 || N == 16, "2 or 4 felts");
+    u32 h[8] = {IV0 ^ 0x01010020u, IV1, IV2, IV3, IV4, IV5, IV6, IV7};
+    u32 m[16];
+#pragma unroll
+    for (int k = 0; k < 8; k++) { m[k] = d[k]; m[8 + k] = w[k]; }
+    const u32 len = 32u + 16u * n_felts;
+    if (N == 8 || n_felts <= 2) {
+        b2s_compress(h, m, len, true);
+    } else {
+        b2s_compress(h, m, 64u, false);
+#pragma unroll
+        for (int k = 0; k < 8; k++) { m[k] = w[N - 8 + k]; m[8 + k] = 0u; }
+        b2s_compress(h, m, len, true);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) d[k] = h[k];
+    n_chal += 1;
+    n_sent = 0;
+}
 
 }  // namespace b2s
 }  // namespace tstwo

@@ -2,7 +2,7 @@
 GkrMultivariatePolyOracle (lookups/gkr_prover.ts) and prove_batch (gkr_prover.ts:440-580).
 
 MLEs live in HBM: an Mle<SecureField> is a SecureColumnByCoords (4 SoA columns), an Mle<BaseField> one HipColumn; the first
-variable is the most significant bit of the index.  Every pass over 2^n values is a kernel of csrc/gkr.hip; the host keeps the
+variable is the most significant bit of the index.  Every pass over 2^n values is a kernel of csrc/gkr_ops.hip; the host keeps the
 O(layers) protocol (sumcheck.py) and the channel between the layers.
 
 prove_batch enqueues a whole layer without reading anything back where it can (a Blake2s channel with the Rust draw semantics, at
