@@ -25,14 +25,15 @@ from tstwo_amd import _lib as L  # noqa: E402
 from gpu_util import dev, ptrs, vp  # noqa: E402
 from test_gpu_merkle_plan import assert_wraps, n_cus  # noqa: E402
 
-PAIR_LOG, CAP = 1, 3                                     # TSTWO_MERKLE_PAIR_LOG / TSTWO_MERKLE_CAP of the child
-SMALL_LOGS = (1, 6, 7, 8, 10)                            # one pair, half a wave, exactly one wave, 2 and 8 workgroups of pairs
-MANY_TREES, MANY_COLS = (2, 8), 32
-MANY_LOGS = (8, 17)                                      # 2^8: committed tree by tree (commit_many shares launches from 2^17 leaves up); 2^17:
+# the shapes live in merkle_plan.py (PAIR_TEST), where the coverage condition of test_cpu_merkle_plan.py reads them too
+PAIR_LOG, CAP = MP.PAIR_TEST["pair_log"], MP.PAIR_TEST["cap"]      # 1, 3: TSTWO_MERKLE_PAIR_LOG / TSTWO_MERKLE_CAP of the child
+SMALL_LOGS = MP.PAIR_TEST["small_logs"]                  # (1, 6, 7, 8, 10): one pair, half a wave, exactly one wave, 2 and 8 workgroups of pairs
+MANY_TREES, MANY_COLS = MP.PAIR_TEST["many_trees"], MP.PAIR_TEST["many_cols"]      # (2, 8), 32
+MANY_LOGS = MP.PAIR_TEST["many_logs"]                    # (8, 17).  2^8: committed tree by tree (commit_many shares launches from 2^17 leaves up); 2^17:
                                                          # ONE pair launch for all trees — 8 trees under CAP have 96 workgroups each for 256
                                                          # workgroups of pairs: three rows per lane, a partial last one
-WRAP_COLS, WRAP_LOG = 16, 19                             # 2^18 pairs under a cap of 768 workgroups: two pairs per lane, a partial second row
-SHIPPED_COLS, SHIPPED_LOG = 32, 19
+WRAP_COLS, WRAP_LOG = MP.PAIR_TEST["wrap"]               # 16, 19: 2^18 pairs under a cap of 768 workgroups: two pairs per lane, a partial second row
+SHIPPED_COLS, SHIPPED_LOG = MP.PAIR_TEST["shipped"]      # 32, 19
 
 
 @pytest.fixture(scope="module", autouse=True)

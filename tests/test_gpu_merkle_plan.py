@@ -1,5 +1,5 @@
-"""-m gpu: every branch of the Merkle launch plan (commit_tree, commit_layer, commit_column_free, commit_upper_levels in
-tstwo_amd/csrc/merkle.hip) and the grid-stride paths of its one-lane-per-node kernels, every layer bit for bit against a
+"""-m gpu: every branch of the Merkle launch plan (tstwo_amd/csrc/merkle_plan.h, walked by merkle.hip) and the grid-stride paths
+of its one-lane-per-node kernels, every layer bit for bit against a
 reference: the hashlib model of tests/merkle_plan.py up to 2^17 leaves, the oracle above.  Which shape takes which launches is
 accounted for without a GPU in test_cpu_merkle_plan.py."""
 import ctypes as C
@@ -129,7 +129,7 @@ def test_shipped_wrap_points(kind):
 CAP = 3            # TSTWO_MERKLE_CAP of the child: 768 workgroups on 256 CUs, a lane stride of 196608 nodes
 TREE_CASES = {"5x18": [18] * 5, "260x18": [18] * 260, "3x19+5x18": [19] * 3 + [18] * 5, "1x19+260x18": [19] + [18] * 260,
               "16x18": [18] * 16, "32x18": [18] * 32, "48x18": [18] * 48, "64x18": [18] * 64, "4x18": [18] * 4}
-MANY = (5, 16, 17)                                       # trees, columns, log size of the tstwo_merkle_commit_many case
+MANY = MP.CAP_TEST_MANY                                  # (5, 16, 17): trees, columns, log size of the tstwo_merkle_commit_many case
 FRI_LOG, FRI_LAST = 20, 12                               # circle evaluation of 2^20 rows: the first fused fold + leaf launch has 2^18 nodes
 
 

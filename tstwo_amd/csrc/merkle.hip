@@ -8,9 +8,11 @@
 // Holds the layer kernels (k_merkle_layer, k_merkle_leaf_static, k_merkle_leaf_pair, k_merkle_leaf4, k_merkle_inner[_set],
 // k_merkle_subtree2c); the latency path below 2^kUpLog nodes, a quad of lanes per node (k_merkle_upq, k_merkle_leaf4_upq) with
 // the channel step that can ride on a root (ChanHook, k_channel_mix_draw); the FRI commit tail (k_fri_tail) and the grind
-// (k_grind); then the host side — the ONE launch plan (launch_leaf_static, commit_column_free, commit_upper_levels under
-// commit_layer / commit_tree) and the entries built on it: tstwo_merkle_commit[_layer|_many], merkle_commit_then_channel,
-// launch_fri_tail, tstwo_channel_mix_root_draw_felt, tstwo_grind_blake2s.  Reading trees back is decommit.hip's.
+// (k_grind); then the host side.  Which launches an input takes — kernel, layer, levels, grid, trees, columns, who carries the fold
+// and the channel step — is merkle_plan.h's, decided before anything is launched; run_plan here issues a plan's steps from the
+// pointers of the call, and every entry is "check the pointers, plan, run_plan": tstwo_merkle_commit[_layer|_many],
+// merkle_commit_then_channel.  Then launch_fri_tail, tstwo_channel_mix_root_draw_felt, tstwo_grind_blake2s.  Reading trees back is
+// decommit.hip's.
 #include <string.h>
 
 #include <type_traits>
@@ -18,6 +20,7 @@
 
 #include "blake2s.cuh"
 #include "common.h"
+#include "merkle_plan.h"
 
 using namespace tstwo;
 using namespace tstwo::b2s;
@@ -123,7 +126,6 @@ __global__ void __launch_bounds__(256) k_merkle_layer(const uint4 *__restrict__ 
 //     clamp + scalar load + select per word per block.
 // Up to kMaxTrees equally shaped trees per launch (tstwo_merkle_commit_many): blockIdx.y selects the tree — its columns are
 // cols.p[blockIdx.y * 16 * NBLK ...] of the by-value table, its layers buffer ts.t[blockIdx.y].
-constexpr int kMaxTrees = 8;
 struct TreeSet { uint4 *t[kMaxTrees]; };
 template <int NBLK>
 __global__ void __launch_bounds__(256) k_merkle_leaf_static(HashColPtrs cols, TreeSet outs, size_t n_nodes) {
@@ -559,46 +561,6 @@ __global__ void __launch_bounds__(WG) k_merkle_leaf4_upq(u32 *__restrict__ c0, u
     if (log_leaf == levels) chan_step_from_lds(hk, sh);
 }
 
-// Column-free levels log_child-1 .. log_stop of the tree, a few fused launches instead of one launch per level.
-// hook (null, or hook->chan null: none): a channel step on the root of a single tree.  When log_stop is 0 the last launch, one
-// workgroup, produces the root and takes the step with it; *hook is then cleared.
-// Layers below 2^kUpLog nodes are latency-bound: tstwo_merkle_commit builds them with the fused multi-level launches above
-// (k_merkle_upq) instead of one launch per layer.
-constexpr int kUpLog = 16;
-int commit_upper_levels(TreeSet ts, unsigned n_trees, u32 log_child, u32 log_stop, ChanHook *hook) {
-    Context &c = ctx();
-    const ChanHook none = {nullptr, nullptr};
-    ChanHook root_hook = none;               // passed to the launches that finish the tree (the last one)
-    if (hook && hook->chan && n_trees == 1 && log_stop == 0 && log_child > log_stop) {
-        root_hook = *hook;
-        *hook = none;
-    }
-    while (log_child > log_stop) {
-        const u32 remaining = log_child - log_stop;
-        const u32 parents_log = log_child - 1;
-        if (parents_log >= 9 && remaining >= 9 && remaining <= 16) {
-            // 256 quads per workgroup, 9 levels each, FIRST: the wide levels (256 and 128 compressions on one CU are the slow
-            // part of a single-workgroup tree top) run on 2^(parents_log-8) CUs side by side, and what is left (<= 7 levels)
-            // fits one 64-quad workgroup, one wave per SIMD.  (The other order — 64-quad workgroups first, one 256-quad
-            // workgroup to finish — put those wide levels on one CU.)
-            hipLaunchKernelGGL(k_merkle_upq<1024>, dim3(1u << (parents_log - 8), n_trees), dim3(1024), 0, c.stream, ts, log_child, 9u, none);
-            log_child -= 9;
-        } else if (parents_log <= 6) {            // <= 64 parents: one 64-quad workgroup finishes the tree
-            hipLaunchKernelGGL(k_merkle_upq<256>, dim3(1, n_trees), dim3(256), 0, c.stream, ts, log_child, remaining, root_hook);
-            log_child -= remaining;
-        } else if (parents_log <= 8) {            // <= 256 parents: ONE workgroup of 256 quads finishes the tree (up to 9 levels)
-            hipLaunchKernelGGL(k_merkle_upq<1024>, dim3(1, n_trees), dim3(1024), 0, c.stream, ts, log_child, remaining, root_hook);
-            log_child -= remaining;
-        } else {                                  // >= 512 parents: 64 quads per workgroup, 64 -> 1 = up to 7 levels each
-            u32 levels = remaining < 7 ? remaining : 7;
-            hipLaunchKernelGGL(k_merkle_upq<256>, dim3(1u << (parents_log - 6), n_trees), dim3(256), 0, c.stream, ts, log_child, levels, none);
-            log_child -= levels;
-        }
-    }
-    TSTWO_LAUNCH_CHECK();
-    return TSTWO_OK;
-}
-
 __global__ void __launch_bounds__(64) k_channel_mix_draw(u32 *__restrict__ chan, const u32 *__restrict__ root, u32 *__restrict__ felt,
                                                         u32 do_mix, u32 do_draw) {
     u32 d[8], f[4] = {0, 0, 0, 0};
@@ -731,223 +693,144 @@ __global__ void __launch_bounds__(256) k_grind(GrindDigest d, u32 pow_bits, unsi
     if (tz >= pow_bits) atomicMin(best, nonce);
 }
 
-// Workgroups of a one-lane-per-node launch over n_nodes nodes of each of n_trees trees: at most merkle_cap per CU, then lanes
-// grid-stride over more nodes; a set of trees has the same lanes in flight as one tree's launch.
-unsigned layer_blocks(size_t n_nodes, unsigned n_trees) {
-    const unsigned blocks = ceil_div(n_nodes, 256);
-    const unsigned cap = (unsigned)ctx().n_cus * (unsigned)knobs().merkle_cap / n_trees;
-    return blocks <= cap ? blocks : cap ? cap : 1;
+// ---- host.  merkle_plan.h decides; what follows checks pointers, asks for the plan and issues it.
+static_assert(kMerkleMaxHashCols == kMaxHashCols && kMerkleCapDefault == Knobs{}.merkle_cap && kMerklePairLogDefault == Knobs{}.merkle_pair_log,
+              "merkle_plan.h restates common.h's constants");
+
+// The pointers of one tree of a call.  layers: its layers buffer, layer k at byte 32 (2^k - 1).  tstwo_merkle_commit_layer has no
+// such buffer: `out` is its one layer, `prev` that layer's children, and every column belongs to the layer (log_sizes is null).
+struct TreePtrs {
+    const u32 *const *cols;
+    const u32 *log_sizes;
+    size_t n_cols;
+    uint8_t *layers, *out;
+    const uint8_t *prev;
+};
+
+MerkleEnv plan_env() { return {(u32)ctx().n_cus, knobs().merkle_cap, knobs().merkle_pair_log}; }
+
+// What the plan reads of a tree.  A request with a null pointer (null_arg) is not looked into.
+MerkleTree shape_of(const TreePtrs &t) {
+    MerkleTree m = {t.log_sizes, t.n_cols, true, aligned16(t.layers), !t.layers || !t.cols || !t.log_sizes};
+    if (m.null_arg) return m;
+    u32 max_log = 0;
+    for (size_t i = 0; i < t.n_cols; i++) max_log = t.log_sizes[i] > max_log ? t.log_sizes[i] : max_log;
+    for (size_t i = 0; i < t.n_cols; i++)
+        if (t.log_sizes[i] == max_log && ((uintptr_t)t.cols[i] & 7)) m.cols_aligned8 = false;
+    return m;
 }
 
-// The leaf layer (2^log_size nodes at leaf.t[tree]) of n_trees >= 1 trees of cols_per_tree = 16 / 32 / 48 / 64 columns each, tree
-// after tree in hp.
-int launch_leaf_static(const HashColPtrs &hp, size_t cols_per_tree, const TreeSet &leaf, unsigned n_trees, u32 log_size) {
-    const size_t n_nodes = (size_t)1 << log_size;
-    const dim3 grid(layer_blocks(n_nodes, n_trees), n_trees);
-    hipStream_t stream = ctx().stream;
-    switch (cols_per_tree / 16) {
-        case 1: hipLaunchKernelGGL(k_merkle_leaf_static<1>, grid, dim3(256), 0, stream, hp, leaf, n_nodes); break;
-        case 2: hipLaunchKernelGGL(k_merkle_leaf_static<2>, grid, dim3(256), 0, stream, hp, leaf, n_nodes); break;
-        case 3: hipLaunchKernelGGL(k_merkle_leaf_static<3>, grid, dim3(256), 0, stream, hp, leaf, n_nodes); break;
-        default: hipLaunchKernelGGL(k_merkle_leaf_static<4>, grid, dim3(256), 0, stream, hp, leaf, n_nodes); break;
-    }
-    TSTWO_LAUNCH_CHECK();
+// The steps of the call being served: one vector for the life of the library, so that a commit allocates nothing for its plan.
+std::vector<MerkleStep> &plan_steps() {
+    static std::vector<MerkleStep> steps;
+    steps.clear();
+    return steps;
+}
+
+int plan_error(const char *why) { return why ? set_error(why == kMerkleFoldNotCarried ? TSTWO_ERR_HIP : TSTWO_ERR_BAD_ARG, why) : TSTWO_OK; }
+
+// The pointers a tree committed on its own must have.
+int check_tree(const TreePtrs &t) {
+    if (!t.layers) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null layers buffer");
+    if (t.n_cols && !t.log_sizes) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null log size table");
+    TSTWO_REQUIRE_TABLE(t.cols, t.n_cols);
     return TSTWO_OK;
 }
 
-// Whether the leaf layer of such trees is hashed together with the layer above it (k_merkle_leaf_pair): from 2^merkle_pair_log
-// leaves up (below that a tree is a handful of latency-bound launches and the static leaf keeps its lane per row), when layer
-// log_size - 1 has no columns of its own and every column is 8-byte aligned (the kernel's loads fetch two words; a column at an odd
-// word offset keeps the static leaf, which needs 4-byte alignment only).
-bool leaf_takes_pair(u32 log_size, bool columns_below, const u32 *const *cols, size_t n_cols) {
-    if (!(log_size >= 1 && log_size <= 30 && (int)log_size >= knobs().merkle_pair_log && !columns_below)) return false;
-    for (size_t i = 0; i < n_cols; i++)
-        if ((uintptr_t)cols[i] & 7) return false;
-    return true;
-}
-// Layers log_size (at leaf.t[tree]) and log_size - 1 of n_trees trees: one lane per pair of sibling leaves.
-int launch_leaf_pair(const HashColPtrs &hp, size_t cols_per_tree, const TreeSet &leaf, unsigned n_trees, u32 log_size) {
-    const size_t n_pairs = (size_t)1 << (log_size - 1);
-    const dim3 grid(layer_blocks(n_pairs, n_trees), n_trees);
+// Issues every step of a plan.  trees: the pointers the plan's tree numbers refer to; fold / hook: what the steps that carry the
+// fold / take the channel step are given.
+int run_plan(const std::vector<MerkleStep> &steps, const TreePtrs *trees, const FoldSpec *fold, const ChanHook &hook) {
     hipStream_t stream = ctx().stream;
-    switch (cols_per_tree / 16) {
-        case 1: hipLaunchKernelGGL((k_merkle_leaf_pair<1, kPairNT>), grid, dim3(256), 0, stream, hp, leaf, n_pairs); break;
-        case 2: hipLaunchKernelGGL((k_merkle_leaf_pair<2, kPairNT>), grid, dim3(256), 0, stream, hp, leaf, n_pairs); break;
-        case 3: hipLaunchKernelGGL((k_merkle_leaf_pair<3, kPairNT>), grid, dim3(256), 0, stream, hp, leaf, n_pairs); break;
-        default: hipLaunchKernelGGL((k_merkle_leaf_pair<4, kPairNT>), grid, dim3(256), 0, stream, hp, leaf, n_pairs); break;
-    }
-    TSTWO_LAUNCH_CHECK();
-    return TSTWO_OK;
-}
-
-// Column-free layers log_child-1 .. log_stop of every tree of a set, the launch plan of every tree above its columns: layers of
-// at least 2^kUpLog nodes two per launch (k_merkle_subtree2c; measured for 32 x 2^22: 0.308 ms, against 0.313 for one launch per
-// layer and 0.326 / 0.332 for runs of 3 / 4 layers), a single leftover one on its own, the smaller ones by commit_upper_levels
-// (which also takes `hook`).
-int commit_column_free(const TreeSet &ts, unsigned n_trees, u32 log_child, u32 log_stop, ChanHook *hook) {
-    hipStream_t stream = ctx().stream;
-    for (; log_child >= log_stop + 2 && log_child - 2 >= (u32)kUpLog; log_child -= 2) {
-        const size_t tops = (size_t)1 << (log_child - 2);           // >= 2^kUpLog nodes: whole k_merkle_subtree2c workgroups
-        hipLaunchKernelGGL(k_merkle_subtree2c, dim3((unsigned)(tops / 256), n_trees), dim3(256), 0, stream, ts, log_child);
-    }
-    if (log_child > log_stop && log_child - 1 >= (u32)kUpLog) {
-        log_child -= 1;
-        hipLaunchKernelGGL(k_merkle_inner_set, dim3(layer_blocks((size_t)1 << log_child, n_trees), n_trees), dim3(256), 0, stream, ts, log_child);
-    }
-    TSTWO_LAUNCH_CHECK();
-    return commit_upper_levels(ts, n_trees, log_child, log_stop, hook);
-}
-
-// fold (null: none): the 4 columns of a leaf layer are first written as the fold it describes, inside the leaf launch.
-int commit_layer(u32 log_size, const uint8_t *prev, const u32 *const *cols, size_t n_cols, uint8_t *out, const FoldSpec *fold) {
-    Context &c = ctx();
-    if (log_size > 31) return set_error(TSTWO_ERR_BAD_ARG, "merkle: log size out of range");
-    if (!out) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null output layer");
-    if (!aligned16(out) || !aligned16(prev)) return set_error(TSTWO_ERR_BAD_ARG, "merkle: layers must be 16-byte aligned");
-    if (fold && (prev || log_size > 30 || n_cols != 4)) return set_error(TSTWO_ERR_HIP, "fri commit: the fold was not carried by the leaf launch");
-    const size_t n_nodes = (size_t)1 << log_size;
-    const u32 child_words = prev ? 16u : 0u;
-    const u32 W = child_words + (u32)n_cols;
-    const unsigned blocks = layer_blocks(n_nodes, 1);
-    if (!prev && log_size <= 30 && (n_cols == 16 || n_cols == 32 || n_cols == 48 || n_cols == 64)) {
-        HashColPtrs hp;
-        for (size_t k = 0; k < n_cols; k++) hp.p[k] = cols[k];
-        TreeSet one = {};
-        one.t[0] = (uint4 *)out;
-        return launch_leaf_static(hp, n_cols, one, 1, log_size);
-    }
-    if (!prev && log_size <= 30 && n_cols == 4) {
-        u32 *w0 = const_cast<u32 *>(cols[0]), *w1 = const_cast<u32 *>(cols[1]), *w2 = const_cast<u32 *>(cols[2]), *w3 = const_cast<u32 *>(cols[3]);
-        if (fold)
-            hipLaunchKernelGGL(k_merkle_leaf4<true>, dim3(blocks), dim3(256), 0, c.stream, w0, w1, w2, w3, (uint4 *)out, n_nodes, *fold);
-        else
-            hipLaunchKernelGGL(k_merkle_leaf4<false>, dim3(blocks), dim3(256), 0, c.stream, w0, w1, w2, w3, (uint4 *)out, n_nodes, FoldSpec{});
-        TSTWO_LAUNCH_CHECK();
-        return TSTWO_OK;
-    }
-    if (prev && n_cols == 0) {
-        hipLaunchKernelGGL(k_merkle_inner, dim3(blocks), dim3(256), 0, c.stream, (const uint4 *)prev, (uint4 *)out, n_nodes);
-        TSTWO_LAUNCH_CHECK();
-        return TSTWO_OK;
-    }
-    // columns are absorbed kMaxHashCols per launch; launch boundaries fall on 64-byte block boundaries
-    size_t col_base = 0;
-    bool first = true;
-    do {
-        size_t take = n_cols - col_base;
-        // words available to this launch must end on a block boundary unless it is the final launch
-        if (take > (size_t)kMaxHashCols) take = kMaxHashCols;
-        bool final_launch = (col_base + take == n_cols);
-        if (!final_launch) {
-            // make (child_words + col_base + take) a multiple of 16
-            size_t end_word = child_words + col_base + take;
-            take -= end_word % 16;
+    for (const MerkleStep &s : steps) {
+        const TreePtrs &t = trees[s.tree];
+        const dim3 grid(s.grid, s.n_trees), wg(s.wg);
+        const size_t n_nodes = (size_t)1 << s.log;
+        TreeSet ts = {}, at = {};                        // every tree's layers buffer, and its layer s.log in it
+        for (u32 r = 0; r < s.n_trees; r++) {
+            ts.t[r] = (uint4 *)trees[s.tree + r].layers;
+            at.t[r] = t.out ? (uint4 *)t.out : ts.t[r] + 2 * (n_nodes - 1);
         }
-        HashColPtrs hp;
-        for (size_t k = 0; k < take; k++) hp.p[k] = cols[col_base + k];
-        LayerParams lp;
-        lp.total_words = W;
-        lp.w_begin = first ? 0u : (u32)(child_words + col_base);
-        lp.w_end = final_launch ? (W > 0 ? W : 1u) + 16u : (u32)(child_words + col_base + take);
-        lp.col_word0 = (u32)(child_words + col_base);
-        lp.n_cols = (u32)take;
-        lp.load_state = first ? 0u : 1u;
-        lp.is_final = final_launch ? 1u : 0u;
-        if (prev)
-            hipLaunchKernelGGL(k_merkle_layer<true>, dim3(blocks), dim3(256), 0, c.stream, (const uint4 *)prev, hp, (uint4 *)out, n_nodes, lp);
-        else
-            hipLaunchKernelGGL(k_merkle_layer<false>, dim3(blocks), dim3(256), 0, c.stream, (const uint4 *)nullptr, hp, (uint4 *)out, n_nodes, lp);
-        col_base += take;
-        first = false;
-    } while (col_base < n_cols);
+        const auto children = [&] { return t.out ? (const uint4 *)t.prev : ts.t[0] + 2 * (2 * n_nodes - 1); };      // of layer s.log
+        HashColPtrs hp;                                 // the columns read: s.n_cols from the s.col0-th column of log size s.log, tree after tree
+        u32 n = 0;
+        for (u32 r = 0; r < s.n_trees && s.n_cols; r++) {
+            const TreePtrs &q = trees[s.tree + r];
+            u32 skip = s.col0;
+            for (size_t i = 0; i < q.n_cols && n < (r + 1) * s.n_cols; i++) {
+                if (q.log_sizes && q.log_sizes[i] != s.log) continue;
+                if (skip) skip--;
+                else hp.p[n++] = q.cols[i];
+            }
+        }
+        const ChanHook hk = s.hook ? hook : ChanHook{nullptr, nullptr};
+        switch (s.kind) {
+            case MerkleStep::LEAF_STATIC:
+                switch (s.n_cols / 16) {
+                    case 1: hipLaunchKernelGGL(k_merkle_leaf_static<1>, grid, wg, 0, stream, hp, at, n_nodes); break;
+                    case 2: hipLaunchKernelGGL(k_merkle_leaf_static<2>, grid, wg, 0, stream, hp, at, n_nodes); break;
+                    case 3: hipLaunchKernelGGL(k_merkle_leaf_static<3>, grid, wg, 0, stream, hp, at, n_nodes); break;
+                    default: hipLaunchKernelGGL(k_merkle_leaf_static<4>, grid, wg, 0, stream, hp, at, n_nodes); break;
+                }
+                break;
+            case MerkleStep::LEAF_PAIR:
+                switch (s.n_cols / 16) {
+                    case 1: hipLaunchKernelGGL((k_merkle_leaf_pair<1, kPairNT>), grid, wg, 0, stream, hp, at, n_nodes / 2); break;
+                    case 2: hipLaunchKernelGGL((k_merkle_leaf_pair<2, kPairNT>), grid, wg, 0, stream, hp, at, n_nodes / 2); break;
+                    case 3: hipLaunchKernelGGL((k_merkle_leaf_pair<3, kPairNT>), grid, wg, 0, stream, hp, at, n_nodes / 2); break;
+                    default: hipLaunchKernelGGL((k_merkle_leaf_pair<4, kPairNT>), grid, wg, 0, stream, hp, at, n_nodes / 2); break;
+                }
+                break;
+            case MerkleStep::LEAF4:
+            case MerkleStep::LEAF4_UPQ: {
+                u32 *w0 = const_cast<u32 *>(hp.p[0]), *w1 = const_cast<u32 *>(hp.p[1]), *w2 = const_cast<u32 *>(hp.p[2]), *w3 = const_cast<u32 *>(hp.p[3]);
+                const FoldSpec fs = s.fold ? *fold : FoldSpec{};
+                if (s.kind == MerkleStep::LEAF4) {
+                    const auto kernel = s.fold ? k_merkle_leaf4<true> : k_merkle_leaf4<false>;
+                    hipLaunchKernelGGL(kernel, grid, wg, 0, stream, w0, w1, w2, w3, at.t[0], n_nodes, fs);
+                } else {
+                    const auto kernel = s.wg == 1024 ? (s.fold ? k_merkle_leaf4_upq<1024, true> : k_merkle_leaf4_upq<1024, false>)
+                                                     : (s.fold ? k_merkle_leaf4_upq<256, true> : k_merkle_leaf4_upq<256, false>);
+                    hipLaunchKernelGGL(kernel, grid, wg, 0, stream, w0, w1, w2, w3, ts.t[0], s.log, s.levels, hk, fs);
+                }
+                break;
+            }
+            case MerkleStep::LAYER: {
+                const LayerParams lp = {s.lp.total_words, s.lp.w_begin, s.lp.w_end, s.lp.col_word0, s.lp.n_cols, s.lp.load_state, s.lp.is_final};
+                if (s.has_prev) hipLaunchKernelGGL(k_merkle_layer<true>, grid, wg, 0, stream, children(), hp, at.t[0], n_nodes, lp);
+                else hipLaunchKernelGGL(k_merkle_layer<false>, grid, wg, 0, stream, (const uint4 *)nullptr, hp, at.t[0], n_nodes, lp);
+                break;
+            }
+            case MerkleStep::INNER: hipLaunchKernelGGL(k_merkle_inner, grid, wg, 0, stream, children(), at.t[0], n_nodes); break;
+            case MerkleStep::INNER_SET: hipLaunchKernelGGL(k_merkle_inner_set, grid, wg, 0, stream, ts, s.log); break;
+            case MerkleStep::SUBTREE2C: hipLaunchKernelGGL(k_merkle_subtree2c, grid, wg, 0, stream, ts, s.log); break;
+            case MerkleStep::UPQ: {
+                const auto kernel = s.wg == 1024 ? k_merkle_upq<1024> : k_merkle_upq<256>;
+                hipLaunchKernelGGL(kernel, grid, wg, 0, stream, ts, s.log, s.levels, hk);
+                break;
+            }
+            case MerkleStep::CHANNEL: {                  // no launch of the tree took the step
+                int rc = tstwo_channel_mix_root_draw_felt(hook.chan, t.layers, hook.felt);
+                if (rc) return rc;
+                break;
+            }
+        }
+    }
     TSTWO_LAUNCH_CHECK();
     return TSTWO_OK;
 }
 
 // tstwo_merkle_commit, with the two steps of a FRI commit layer that can ride on the tree's launches.  fold (null: none): the
-// tree's 4 columns are first written as that fold, inside the leaf launch; a launch sequence that cannot carry it is an error.
-// hook (null: none): the channel step on the root, taken by the single-workgroup launch that produces the root and then
-// cleared; a hook still set on return means no launch could take it.
+// tree's 4 columns are first written as that fold, inside the leaf launch.  hook (chan null: none): the channel step on the root.
 int commit_tree(const u32 *const *cols, const u32 *log_sizes, size_t n_cols, uint8_t *layers, uint8_t root[32], const FoldSpec *fold,
-                ChanHook *hook) {
+                const ChanHook &hook) {
     TSTWO_REQUIRE_READY();
-    if (!layers) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null layers buffer");
-    if (n_cols && !log_sizes) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null log size table");
-    TSTWO_REQUIRE_TABLE(cols, n_cols);
-    u32 max_log = 0;
-    for (size_t i = 0; i < n_cols; i++) {
-        if (log_sizes[i] > 31) return set_error(TSTWO_ERR_BAD_ARG, "merkle: log size out of range");
-        if (log_sizes[i] > max_log) max_log = log_sizes[i];
-    }
-    const auto has_cols = [&](u32 lg) {
-        for (size_t i = 0; i < n_cols; i++)
-            if (log_sizes[i] == lg) return true;
-        return false;
-    };
-    TreeSet one = {};
-    one.t[0] = (uint4 *)layers;
-    // a tree of exactly 4 equally long columns with at most 2^kUpLog rows (every FRI layer but the first few): leaves and the
-    // first 7 (or all, below 2^10 rows) levels in one launch
-    if (n_cols == 4 && max_log >= 1 && (int)max_log <= kUpLog && log_sizes[0] == max_log && log_sizes[1] == max_log && log_sizes[2] == max_log &&
-        log_sizes[3] == max_log) {
-        u32 *w0 = const_cast<u32 *>(cols[0]), *w1 = const_cast<u32 *>(cols[1]), *w2 = const_cast<u32 *>(cols[2]), *w3 = const_cast<u32 *>(cols[3]);
-        const FoldSpec fs = fold ? *fold : FoldSpec{};
-        // up to 2^9 rows: one workgroup of 256 quads takes the whole tree and the channel step; above: 64 quads, 7 levels each
-        const bool whole = max_log <= 9;
-        const u32 levels = whole ? max_log : 7u;
-        const ChanHook hk = whole && hook ? *hook : ChanHook{nullptr, nullptr};
-        const auto kernel = whole ? (fold ? k_merkle_leaf4_upq<1024, true> : k_merkle_leaf4_upq<1024, false>)
-                                  : (fold ? k_merkle_leaf4_upq<256, true> : k_merkle_leaf4_upq<256, false>);
-        hipLaunchKernelGGL(kernel, dim3(1u << (max_log - levels)), dim3(whole ? 1024 : 256), 0, ctx().stream, w0, w1, w2, w3, (uint4 *)layers,
-                           max_log, levels, hk, fs);
-        TSTWO_LAUNCH_CHECK();
-        if (whole && hook) *hook = {nullptr, nullptr};
-        int rc = whole ? TSTWO_OK : commit_upper_levels(one, 1, max_log - levels, 0, hook);
-        if (rc) return rc;
-        if (root) return small_d2h(root, layers, 32);
-        return TSTWO_OK;
-    }
-    const u32 **lc = n_cols ? new const u32 *[n_cols] : nullptr;
-    const uint8_t *prev = nullptr;
-    int rc = TSTWO_OK;
-    int lg = (int)max_log;
-    while (lg >= 0 && rc == TSTWO_OK) {   // vcs/prover.ts:24-27
-        size_t k = 0;
-        for (size_t i = 0; i < n_cols; i++)
-            if (log_sizes[i] == (u32)lg) lc[k++] = cols[i];
-        uint8_t *dst = layers + 32 * (((size_t)1 << lg) - 1);
-        // layer k starts at 32*(2^k-1): 16-byte aligned for every k >= 0 when `layers` is
-        if (k == 0 && prev != nullptr) {
-            // a run of column-free layers below lg+1: one launch plan for all of them (stop above the next layer that has columns)
-            int stop = lg;
-            while (stop > 0 && !has_cols((u32)stop - 1)) stop--;
-            rc = commit_column_free(one, 1, (u32)lg + 1, (u32)stop, hook);
-            prev = layers + 32 * (((size_t)1 << stop) - 1);
-            lg = stop - 1;
-            continue;
-        }
-        if (!prev && !fold && (k == 16 || k == 32 || k == 48 || k == 64) && aligned16(dst) && leaf_takes_pair((u32)lg, has_cols((u32)lg - 1), lc, k)) {
-            // the static leaf's shapes, with the column-free layer above the leaves riding on the leaf launch
-            HashColPtrs hp;
-            for (size_t i = 0; i < k; i++) hp.p[i] = lc[i];
-            TreeSet leaf = {};
-            leaf.t[0] = (uint4 *)dst;
-            rc = launch_leaf_pair(hp, k, leaf, 1, (u32)lg);
-            prev = layers + 32 * (((size_t)1 << (lg - 1)) - 1);
-            lg -= 2;
-            continue;
-        }
-        rc = commit_layer((u32)lg, prev, lc, k, dst, prev ? nullptr : fold);      // the leaf layer carries the fold
-        prev = dst;
-        lg--;
-    }
-    delete[] lc;
+    const TreePtrs t = {cols, log_sizes, n_cols, layers, nullptr, nullptr};
+    std::vector<MerkleStep> &steps = plan_steps();
+    int rc = check_tree(t);
+    if (rc == TSTWO_OK) rc = plan_error(merkle_plan_tree(shape_of(t), fold != nullptr, hook.chan != nullptr, plan_env(), 0, steps));
+    if (rc == TSTWO_OK) rc = run_plan(steps, &t, fold, hook);
     if (rc) return rc;
-    if (root) {
-        int rc2 = small_d2h(root, layers, 32);
-        if (rc2) return rc2;
-    }
-    return TSTWO_OK;
+    return root ? small_d2h(root, layers, 32) : TSTWO_OK;
 }
 }  // namespace
 
@@ -958,10 +841,7 @@ int merkle_commit_then_channel(const u32 *const *cols, const u32 *log_sizes, siz
                                const u32 *const *fold_in, const u32 *inv_x, const u32 *alpha_dev) {
     FoldSpec fs = {};
     if (fold_in) fs = {{fold_in[0], fold_in[1], fold_in[2], fold_in[3]}, inv_x, alpha_dev};
-    ChanHook hook = {chan, felt};
-    int rc = commit_tree(cols, log_sizes, n_cols, layers, nullptr, fold_in ? &fs : nullptr, &hook);
-    if (rc) return rc;
-    return hook.chan ? tstwo_channel_mix_root_draw_felt(chan, layers, felt) : TSTWO_OK;      // no launch of the tree took the step
+    return commit_tree(cols, log_sizes, n_cols, layers, nullptr, fold_in ? &fs : nullptr, {chan, felt});
 }
 // fri.hip's commit loop hands the layers from 2^log0 <= 2^9 rows down to the last one to k_fri_tail (see there).
 int launch_fri_tail(u32 *const (*eval)[4], uint8_t *const *trees, u32 n_layers, u32 log0, const u32 *itw, u32 tw_log, u32 *chan, u32 *alphas,
@@ -1034,13 +914,16 @@ int tstwo_merkle_commit_layer(u32 log_size, const uint8_t *prev, const u32 *cons
     TSTWO_REQUIRE_READY();
     if (n_cols && !cols) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null column table");
     TSTWO_REQUIRE_TABLE(cols, n_cols);
-    return commit_layer(log_size, prev, cols, n_cols, out, nullptr);
+    if (!out && log_size <= 31) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null output layer");      // (the plan reports a log size out of range)
+    const TreePtrs t = {cols, nullptr, n_cols, nullptr, out, prev};
+    std::vector<MerkleStep> &steps = plan_steps();
+    int rc = plan_error(merkle_plan_layer(log_size, prev != nullptr, n_cols, false, aligned16(out) && aligned16(prev), plan_env(), 0, steps));
+    return rc ? rc : run_plan(steps, &t, nullptr, {});
 }
 
 int tstwo_merkle_commit(const u32 *const *cols, const u32 *log_sizes, size_t n_cols, uint8_t *layers, uint8_t root[32]) {
-    return commit_tree(cols, log_sizes, n_cols, layers, root, nullptr, nullptr);
+    return commit_tree(cols, log_sizes, n_cols, layers, root, nullptr, {});
 }
-
 
 // Several trees in ONE launch sequence (a TreeVec committed together: the 8 trees of BASELINE config 5's trace on one GPU,
 // pcs/prover.ts:62-64).  A tree ends in ~65 us of launches with almost nothing to do (the layers below 2^19 nodes: 1 M of a
@@ -1051,43 +934,28 @@ int tstwo_merkle_commit(const u32 *const *cols, const u32 *log_sizes, size_t n_c
 int tstwo_merkle_commit_many(const tstwo_commit_request *reqs, size_t n_trees, uint8_t *roots) {
     TSTWO_REQUIRE_READY();
     if (n_trees && !reqs) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null request table");
-    bool uniform = n_trees >= 2 && n_trees <= (size_t)kMaxTrees;
-    size_t n_cols = n_trees ? reqs[0].n_cols : 0;
+    std::vector<TreePtrs> trees(n_trees);
+    std::vector<MerkleTree> shapes(n_trees);
+    for (size_t r = 0; r < n_trees; r++) {
+        trees[r] = {reqs[r].cols, reqs[r].log_sizes, reqs[r].n_cols, reqs[r].layers, nullptr, nullptr};
+        shapes[r] = shape_of(trees[r]);
+    }
+    // which pointers must be there depends on the path: the rule is asked first, then the whole plan (which asks it again)
+    bool uniform = false;
     u32 lg = 0;
-    for (size_t r = 0; r < n_trees && uniform; r++) {
-        const tstwo_commit_request &q = reqs[r];
-        if (!q.layers || !q.cols || !q.log_sizes) return set_error(TSTWO_ERR_BAD_ARG, "merkle: null argument");
-        uniform = q.n_cols == n_cols && (n_cols == 16 || n_cols == 32 || n_cols == 48 || n_cols == 64) && n_cols * n_trees <= (size_t)kMaxHashCols &&
-                  aligned16(q.layers);
-        for (size_t k = 0; k < q.n_cols && uniform; k++) {
-            if (!q.cols[k]) return set_error(TSTWO_ERR_BAD_ARG, "null device pointer in table");
-            if (r == 0 && k == 0) lg = q.log_sizes[0];
-            uniform = q.log_sizes[k] == lg;
-        }
+    int rc = plan_error(merkle_set_uniform(shapes.data(), n_trees, &uniform, &lg));
+    for (size_t r = 0; r < n_trees && rc == TSTWO_OK; r++) {
+        if (uniform) TSTWO_REQUIRE_TABLE(trees[r].cols, trees[r].n_cols);
+        else rc = check_tree(trees[r]);
     }
-    uniform = uniform && lg >= (u32)kUpLog + 1 && lg <= 30;
-    if (!uniform) {
-        for (size_t r = 0; r < n_trees; r++) {
-            int rc = tstwo_merkle_commit(reqs[r].cols, reqs[r].log_sizes, reqs[r].n_cols, reqs[r].layers, nullptr);
-            if (rc) return rc;
-        }
-    } else {
-        HashColPtrs hp;
-        TreeSet leaf = {}, ts = {};
-        for (size_t r = 0; r < n_trees; r++) {
-            for (size_t k = 0; k < n_cols; k++) hp.p[r * n_cols + k] = reqs[r].cols[k];
-            ts.t[r] = (uint4 *)reqs[r].layers;
-            leaf.t[r] = (uint4 *)(reqs[r].layers + 32 * (((size_t)1 << lg) - 1));
-        }
-        const bool pair = leaf_takes_pair(lg, false, hp.p, n_cols * n_trees);      // one log size: no columns below the leaves
-        int rc = pair ? launch_leaf_pair(hp, n_cols, leaf, (unsigned)n_trees, lg) : launch_leaf_static(hp, n_cols, leaf, (unsigned)n_trees, lg);
-        if (rc == TSTWO_OK) rc = commit_column_free(ts, (unsigned)n_trees, pair ? lg - 1 : lg, 0, nullptr);
-        if (rc) return rc;
-    }
+    std::vector<MerkleStep> &steps = plan_steps();
+    if (rc == TSTWO_OK) rc = plan_error(merkle_plan_set(shapes.data(), n_trees, plan_env(), steps));
+    if (rc == TSTWO_OK) rc = run_plan(steps, trees.data(), nullptr, {});
+    if (rc) return rc;
     if (!roots) return TSTWO_OK;
-    std::vector<const uint8_t *> trees(n_trees);
-    for (size_t r = 0; r < n_trees; r++) trees[r] = reqs[r].layers;
-    return download_roots(trees.data(), n_trees, roots);
+    std::vector<const uint8_t *> bufs(n_trees);
+    for (size_t r = 0; r < n_trees; r++) bufs[r] = reqs[r].layers;
+    return download_roots(bufs.data(), n_trees, roots);
 }
 
 }  // extern "C"
