@@ -371,7 +371,11 @@ int tstwo_gather_words(const void *const *srcs, const uint64_t *idx, uint32_t wo
 /* ---------------------------------------------------------------- GrindOps (backend/cpu/grind.ts:31-42, proof_of_work.ts)
  * Smallest nonce >= start_nonce such that Blake2sChannel.mix_u64(nonce) applied to a channel with digest `digest`
  * yields a digest with at least pow_bits trailing zero bits (channel/blake2.ts:96-111: the first 16 digest bytes read
- * as a little-endian u128).  The reference's sequential loop returns the same (first) nonce.  Synchronises. */
+ * as a little-endian u128).  The reference's sequential loop returns the same (first) nonce.  Synchronises.
+ * Nonce 2^64 - 1 is never tested and never returned (it is the search's "none found" value): the search covers
+ * [start_nonce, 2^64 - 2], in batches whose sizes csrc/grind_plan.h sets, and one that reaches 2^64 - 1 without a hit — at once for
+ * start_nonce = 2^64 - 1 — fails with TSTWO_ERR_BAD_ARG "grind: nonce space exhausted", *nonce_out untouched.  Refused likewise:
+ * pow_bits > 128, a null digest or nonce_out.  The same holds for tstwo_grind_poseidon252 below. */
 int tstwo_grind_blake2s(const uint8_t digest[32], uint32_t pow_bits, uint64_t start_nonce, uint64_t *nonce_out);
 
 /* ---------------------------------------------------------------- Poseidon252 Merkle channel

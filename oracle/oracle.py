@@ -108,6 +108,7 @@ def lib():
             "orc_decompose": (C.c_int, [P4, sz, P4, C.POINTER(QM31)]),
             "orc_blake2s": (None, [C.c_char_p, sz, u8p]),
             "orc_blake2s_compress": (None, [u32p, u32p, u32, u32, u32, u32, u32p]),
+            "orc_grind_blake2s": (C.c_int, [C.c_char_p, u32, u64, u64, C.POINTER(u64)]),
             "orc_hash_node": (None, [u8p, u8p, u32p, sz, u8p]),
             "orc_commit_on_layer": (None, [u32, u8p, C.POINTER(u32p), sz, u8p]),
             "orc_merkle_commit": (C.c_int, [C.POINTER(u32p), u32p, sz, u8p, u8p]),
@@ -261,6 +262,14 @@ def blake2s_compress(h, m, count_lo, count_hi, lastblock, lastnode):
     out = np.zeros(8, dtype=np.uint32)
     lib().orc_blake2s_compress(_p(h), _p(m), count_lo, count_hi, lastblock, lastnode, _p(out))
     return out
+
+
+def grind_blake2s(digest: bytes, pow_bits: int, start: int = 0, limit: int = 1 << 24):
+    """The sequential loop from `start` over at most `limit` nonces: the first nonce that qualifies, or None."""
+    assert len(digest) == 32
+    first = C.c_uint64(0)
+    found = lib().orc_grind_blake2s(bytes(digest), pow_bits, start, limit, C.byref(first))
+    return first.value if found else None
 
 
 def hash_node(children, values) -> bytes:

@@ -543,6 +543,22 @@ void orc_blake2s(const uint8_t *msg, size_t len, uint8_t out[32]) {
     b2s_update(&S, msg, len);
     b2s_final(&S, out);
 }
+/* backend/cpu/grind.ts:31-42 over a Blake2sChannel: mix_u64(nonce) = blake2s(digest || LE64(nonce)) (channel/blake2.ts:120-148),
+ * trailing_zeros = those of the first 16 digest bytes as a little-endian u128 (blake2.ts:96-111).  One nonce after the other. */
+int orc_grind_blake2s(const uint8_t digest32[32], u32 pow_bits, uint64_t start, uint64_t limit, uint64_t *first) {
+    uint8_t msg[40], h[32];
+    memcpy(msg, digest32, 32);
+    uint64_t nonce = start;
+    for (uint64_t done = 0; done < limit; done++, nonce++) {
+        for (int k = 0; k < 8; k++) msg[32 + k] = (uint8_t)(nonce >> (8 * k));
+        orc_blake2s(msg, 40, h);
+        u32 tz = 0;
+        while (tz < 128 && !((h[tz >> 3] >> (tz & 7)) & 1)) tz++;
+        if (tz >= pow_bits) { *first = nonce; return 1; }
+        if (nonce == UINT64_MAX) break;
+    }
+    return 0;
+}
 /* vcs/blake2_merkle.ts:9-24 */
 void orc_hash_node(const uint8_t *left32, const uint8_t *right32, const u32 *values, size_t n_values, uint8_t out[32]) {
     b2s_state S;

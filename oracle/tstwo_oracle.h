@@ -124,6 +124,10 @@ int orc_decompose(const uint32_t *const in[4], size_t n, uint32_t *const out[4],
 void orc_blake2s(const uint8_t *msg, size_t len, uint8_t out[32]);
 void orc_blake2s_compress(const uint32_t h[8], const uint32_t m[16], uint32_t count_lo,
                           uint32_t count_hi, uint32_t lastblock, uint32_t lastnode, uint32_t out[8]);
+/* The sequential proof-of-work loop (backend/cpu/grind.ts:31-42) over a Blake2sChannel with digest `digest32`, from nonce `start`
+ * over at most `limit` nonces (never past 2^64 - 1): 1 and *first = the first nonce whose mix_u64 leaves at least pow_bits trailing
+ * zeros (the first 16 digest bytes as a little-endian u128), 0 and *first untouched if none of them does. */
+int orc_grind_blake2s(const uint8_t digest32[32], uint32_t pow_bits, uint64_t start, uint64_t limit, uint64_t *first);
 /* hashNode (vcs/blake2_merkle.ts:9-24) */
 void orc_hash_node(const uint8_t *left32, const uint8_t *right32, const uint32_t *values, size_t n_values,
                    uint8_t out[32]);

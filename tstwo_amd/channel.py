@@ -148,8 +148,9 @@ class HipGrindOps:
     sequential reference loop returns the same first nonce."""
 
     @staticmethod
-    def grind(channel, pow_bits: int) -> int:
-        """Dispatches on the channel: Blake2sChannel (tstwo_grind_blake2s) or Poseidon252Channel (tstwo_grind_poseidon252)."""
+    def grind(channel, pow_bits: int, start_nonce: int = 0) -> int:
+        """Dispatches on the channel: Blake2sChannel (tstwo_grind_blake2s) or Poseidon252Channel (tstwo_grind_poseidon252).
+        The smallest qualifying nonce >= start_nonce (the reference starts at 0)."""
         import ctypes as C
 
         import numpy as np
@@ -157,13 +158,13 @@ class HipGrindOps:
         from . import _lib as L
         from .poseidon import Poseidon252Channel, grind_poseidon252
         if isinstance(channel, Poseidon252Channel):
-            return grind_poseidon252(channel, pow_bits)
+            return grind_poseidon252(channel, pow_bits, start_nonce)
         L.ensure_init()
         d = np.frombuffer(channel.digest(), dtype=np.uint8).copy()
         out = C.c_uint64(0)
-        L.call("tstwo_grind_blake2s", d.ctypes.data_as(L.u8p), pow_bits, 0, C.byref(out))
+        L.call("tstwo_grind_blake2s", d.ctypes.data_as(L.u8p), int(pow_bits), int(start_nonce), C.byref(out))
         return out.value
 
 
-def grind(channel, pow_bits: int) -> int:
-    return HipGrindOps.grind(channel, pow_bits)
+def grind(channel, pow_bits: int, start_nonce: int = 0) -> int:
+    return HipGrindOps.grind(channel, pow_bits, start_nonce)

@@ -20,6 +20,7 @@
 
 #include "blake2s.cuh"
 #include "common.h"
+#include "grind_plan.h"
 #include "merkle_plan.h"
 
 using namespace tstwo;
@@ -880,22 +881,17 @@ int tstwo_grind_blake2s(const uint8_t digest[32], u32 pow_bits, uint64_t start_n
     GrindDigest d;
     for (int i = 0; i < 8; i++)
         d.w[i] = (u32)digest[4 * i] | ((u32)digest[4 * i + 1] << 8) | ((u32)digest[4 * i + 2] << 16) | ((u32)digest[4 * i + 3] << 24);
-    unsigned long long base = start_nonce;
-    const unsigned long long none = ~0ull;
-    for (;;) {
-        // batches grow with the expected work so easy targets return after one small launch
-        unsigned long long batch = 1ull << 20;
-        if (base - start_nonce >= (1ull << 22)) batch = 1ull << 26;
-        if (none - base < batch) batch = none - base;
-        if (batch == 0) return set_error(TSTWO_ERR_BAD_ARG, "grind: nonce space exhausted");
+    const unsigned long long none = kGrindNone;
+    for (GrindSearch s = grind_begin(GRIND_BLAKE2S, start_nonce); grind_next(s);) {      // grind_plan.h
         TSTWO_HIP(hipMemsetAsync(best, 0xFF, sizeof(none), c.stream));      // none = all ones
-        hipLaunchKernelGGL(k_grind, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, c.stream, d, pow_bits, base, batch, best);
+        hipLaunchKernelGGL(k_grind, dim3((unsigned)((s.batch + kGrindLanes - 1) / kGrindLanes)), dim3(kGrindLanes), 0, c.stream, d, pow_bits,
+                           (unsigned long long)s.base, (unsigned long long)s.batch, best);
         TSTWO_LAUNCH_CHECK();
         unsigned long long found = none;
         { int rc2 = small_d2h(&found, best, sizeof(found)); if (rc2) return rc2; }
         if (found != none) { *nonce_out = found; return TSTWO_OK; }
-        base += batch;
     }
+    return set_error(TSTWO_ERR_BAD_ARG, "grind: nonce space exhausted");
 }
 
 // Device-resident Blake2sChannel (state: 10 words = digest[8], n_challenges, n_sent).  root: 32 bytes in device memory

@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "felt252.cuh"
+#include "grind_plan.h"
 
 using namespace tstwo;
 using felt::F;
@@ -252,17 +253,12 @@ int tstwo_grind_poseidon252(const u32 digest[8], u32 pow_bits, uint64_t start_no
     unsigned long long *best = (unsigned long long *)c.scratch;
     FeltArg d;
     for (int k = 0; k < 8; k++) d.v[k] = digest[k];
-    unsigned long long base = start_nonce;
-    const unsigned long long none = ~0ull;
-    // a nonce costs ~2 permutations (~1.5e5 lane instructions): batches start small, so that easy targets return after one short
-    // launch, and grow 4x up to 2^22 nonces (~10 ms)
-    unsigned long long batch = 1ull << 16;
-    for (;;) {
-        if (none - base < batch) batch = none - base;
-        if (batch == 0) return set_error(TSTWO_ERR_BAD_ARG, "grind: nonce space exhausted");
+    static_assert(kThreads == (int)kGrindLanes, "grind_plan.h restates the workgroup of k_p252_grind");
+    const unsigned long long none = kGrindNone;
+    for (GrindSearch s = grind_begin(GRIND_P252, start_nonce); grind_next(s);) {      // grind_plan.h
         TSTWO_HIP(hipMemsetAsync(best, 0xFF, sizeof(none), c.stream));
-        hipLaunchKernelGGL(k_p252_grind, dim3((unsigned)((batch + kThreads - 1) / kThreads)), dim3(kThreads), 0, c.stream, d, pow_bits, base,
-                           batch, best);
+        hipLaunchKernelGGL(k_p252_grind, dim3((unsigned)((s.batch + kThreads - 1) / kThreads)), dim3(kThreads), 0, c.stream, d, pow_bits,
+                           (unsigned long long)s.base, (unsigned long long)s.batch, best);
         TSTWO_LAUNCH_CHECK();
         unsigned long long found = none;
         if (int rc2 = small_d2h(&found, best, sizeof(found))) return rc2;
@@ -270,9 +266,8 @@ int tstwo_grind_poseidon252(const u32 digest[8], u32 pow_bits, uint64_t start_no
             *nonce_out = found;
             return TSTWO_OK;
         }
-        base += batch;
-        if (batch < (1ull << 22)) batch <<= 2;
     }
+    return set_error(TSTWO_ERR_BAD_ARG, "grind: nonce space exhausted");
 }
 
 }  // extern "C"
