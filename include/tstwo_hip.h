@@ -757,6 +757,25 @@ int tstwo_air_eval_columns(const uint32_t *const *cols, size_t n_cols, uint32_t 
 int tstwo_air_columns_compile(const uint32_t *program, size_t program_len, size_t n_cols, size_t n_out, uint64_t *kernel_id);
 int tstwo_air_eval_columns_compiled(uint64_t kernel_id, const uint32_t *const *cols, size_t n_cols, uint32_t log_size,
                                     uint32_t *const *out, size_t n_out);
+/* Which constraint fails on which trace row (Rust stwo assert_constraints_on_trace): the same programs on the trace domain, each
+ * constraint ending in a reduction instead of a store.  A trace satisfies the AIR exactly when every constraint is zero on every
+ * row of CanonicCoset(log_size).
+ *   cols, n_cols, log_size: those of tstwo_air_eval_columns (main columns, then preprocessed, then interaction ones, named by
+ *   position); the columns are never written.  1 <= log_size <= 28.
+ * Program: the encoding, limits and error texts of tstwo_air_eval_program, TSTWO_AIR_OP_ACC the terminal, TSTWO_AIR_OP_LOAD at
+ *   offset o reading what tstwo_air_eval_columns reads.  Here the ACC's w1 is the index of the constraint the ACC belongs to: the
+ *   indices start at 0, never decrease, rise by at most 1 from one ACC to the next and end at n_constraints - 1 ("constraint
+ *   index decreases", "... skips", "... out of range", "first constraint index is not 0", "last constraint index is not
+ *   n_constraints - 1").  So a QM31 constraint lowered into four base-field ACCs is reported as one.
+ *   1 <= n_constraints <= TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS; there may be more ACCs.
+ * report: 2 * n_constraints device words, 16-byte aligned, all overwritten on the stream: word 2c = the number of rows on which
+ *   constraint c is non-zero as a field element (a row counts once, however many of its ACCs are non-zero there), word 2c + 1
+ *   = the smallest such row in coset order (the k for which a load at offset o reads row k + o: the row of the trace as it was
+ *   written), or 0xffffffff when there is none.  Both are order-independent integers: the report is exact whatever the schedule.
+ * Every limit is checked before anything is enqueued (TSTWO_ERR_BAD_ARG, prefix "air check: ").  The program is uploaded through
+ * the small-upload ring: refused during graph capture.  Asynchronous. */
+int tstwo_air_check_constraints(const uint32_t *const *cols, size_t n_cols, uint32_t log_size, const uint32_t *program,
+                                size_t program_len, size_t n_constraints, uint32_t *report);
 
 /* ---------------------------------------------------------------- LogUp interaction trace
  * Rust stwo constraint_framework/logup.rs (LogupTraceGenerator, LogupColGenerator); tstwo_amd/logup.py drives it.

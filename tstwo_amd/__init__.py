@@ -46,8 +46,8 @@ from .constraint_framework import (FrameworkComponent, MulAddComponent, MulAddEv
 from .logup import (INTERACTION_TRACE_IDX, LogupColGenerator, LogupTraceGenerator, LookupElements, LookupGroup,  # noqa: F401
                     RelationEntry, coset_iota, derive_interaction_trace, deriveInteractionTrace, lookup_multiplicities,
                     lookup_multiplicities_keyed)
-from .prover import (ConstraintsNotSatisfied, InvalidLogupSum, InvalidStructure, OodsNotMatching, StarkProof, prove,  # noqa: F401
-                     verify)
+from .prover import (ConstraintsNotSatisfied, ConstraintViolation, InvalidLogupSum, InvalidStructure, OodsNotMatching,  # noqa: F401
+                     StarkProof, diagnose, prove, verify)
 
 __all__ = [n for n in dir() if not n.startswith("_")]
 from .semantics import get_semantics, set_semantics  # noqa: F401,E402

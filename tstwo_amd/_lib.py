@@ -211,6 +211,7 @@ _SIGS = {
     "tstwo_air_eval_columns": [C.POINTER(vp), C.c_size_t, C.c_uint32, u32p, C.c_size_t, C.POINTER(vp), C.c_size_t],
     "tstwo_air_columns_compile": [u32p, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)],
     "tstwo_air_eval_columns_compiled": [C.c_uint64, C.POINTER(vp), C.c_size_t, C.c_uint32, C.POINTER(vp), C.c_size_t],
+    "tstwo_air_check_constraints": [C.POINTER(vp), C.c_size_t, C.c_uint32, u32p, C.c_size_t, C.c_size_t, vp],
     "tstwo_logup_column": [C.POINTER(LogupFrac), C.c_size_t, C.POINTER(vp), C.c_uint32, P4],
     "tstwo_logup_finalize_last": [P4, C.c_uint32, u32p],
     "tstwo_lookup_multiplicities": [C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp],

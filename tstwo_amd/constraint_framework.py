@@ -12,6 +12,9 @@ A fourth, RelationEvaluator, keeps the relation entries of `evaluate` as they we
 their batching: logup.derive_interaction_trace builds the interaction trace from them, with compile_columns / evaluate_columns
 (tstwo_air_eval_columns; with native=True a kernel compiled from the columns program, compile_columns_native /
 tstwo_air_eval_columns_compiled) for every multiplicity or value that is an expression of columns.
+check_program (tstwo_air_check_constraints) runs a constraint program on the TRACE domain and reports, per constraint, on how many
+rows it is non-zero and the first of them in coset order; FrameworkComponent.constraint_failures / assert_constraints drive it
+(Rust stwo assert_constraints_on_trace), prover.diagnose does so for a committed trace.
 The prover evaluates a component's constraints on the whole evaluation domain with one launch: WideFibonacciEval and MulAddEval
 (exactly these types, not subclasses) run on the hand-written kernel of tstwo_air_constraint_quotients, every other eval on the
 program interpreter or, for a FrameworkComponent made with native=True, on a kernel compiled from the program at construction
@@ -29,6 +32,7 @@ from __future__ import annotations
 import bisect
 import ctypes as C
 import time
+from collections import namedtuple
 
 from . import _lib as L
 from .air import (AIR_MUL_ADD, AIR_WIDE_FIB, ORIGINAL_TRACE_IDX, PREPROCESSED_TRACE_IDX, DomainEvaluationAccumulator,
@@ -843,6 +847,46 @@ def evaluate_columns(cols, log_size: int, program: Program, n_out: int, *, nativ
     return out
 
 
+NO_ROW = 0xffffffff                     # tstwo_air_check_constraints: "the constraint fails on no row"
+
+
+def check_program(cols, log_size: int, program: Program, groups=None) -> list:
+    """tstwo_air_check_constraints: [(n_rows, first_row | None)] per constraint of a compile_program program over `cols`,
+    HipColumns on CanonicCoset(log_size).circle_domain() in storage order (main, then preprocessed, then interaction): the
+    number of rows on which the constraint is non-zero and the first of them in coset order (the row of the trace as it was
+    written).  groups[k] is the constraint the k-th ACC belongs to (the identity by default; a secure constraint is 4 ACCs with
+    one index).  One launch, one read-back of 2 words per constraint."""
+    from .backend import HipColumn
+    n = 1 << log_size
+    if any(c.len() != n for c in cols):
+        raise ValueError("every column must hold 2^log_size values")
+    words = list(program.words)
+    accs = [pc for pc in range(program.n_instr) if words[2 * pc] & 0xff == OP_ACC]
+    groups = list(range(len(accs))) if groups is None else [int(g) for g in groups]
+    if len(groups) != len(accs):
+        raise ValueError(f"groups names {len(groups)} ACCs, the program has {len(accs)}")
+    if not groups:
+        raise ValueError("the program has no constraints")
+    for pc, g in zip(accs, groups):
+        words[2 * pc + 1] = g & 0xffffffff
+    n_constraints = groups[-1] + 1
+    report = HipColumn.uninitialized(2 * n_constraints)
+    L.call("tstwo_air_check_constraints", L.ptr_array([c.ptr for c in cols]), len(cols), log_size, L.u32x(words), program.n_instr,
+           n_constraints, L.vp(report.ptr))
+    r = report.to_numpy()
+    return [(int(r[2 * c]), None if int(r[2 * c + 1]) == NO_ROW else int(r[2 * c + 1])) for c in range(n_constraints)]
+
+
+# one failing constraint of a component: its index (add_constraint calls in the order `evaluate` makes them), the number of rows
+# on which it is non-zero and the first of them in coset order
+ConstraintFailure = namedtuple("ConstraintFailure", "constraint n_rows first_row")
+
+
+def _trace_column(x):
+    """A HipColumn of a column given as one, as an evaluation (`.values`) or as an array."""
+    return _col(getattr(x, "values", x))
+
+
 # ------------------------------------------------------------------ FrameworkComponent (Rust constraint_framework/component.rs)
 class FrameworkComponent:
     """A component defined by a FrameworkEval (`log_size()`, `max_constraint_log_degree_bound()`, `evaluate(eval)`).  Its main
@@ -890,6 +934,7 @@ class FrameworkComponent:
         self.trace_locations = alloc.next_for_structure(structure)
         self.kind = _HAND_WRITTEN_KINDS.get(type(eval_))
         self.program = None
+        self._check_program = None       # hand-written kinds: compiled by constraint_failures at its first use
         if self.kind is None:
             pe = ProgramEvaluator(claimed_sum, self.log_size)
             eval_.evaluate(pe)
@@ -911,6 +956,42 @@ class FrameworkComponent:
         native constraint kernel (native=True)."""
         from .logup import derive_interaction_trace
         return derive_interaction_trace(self.eval, main, preprocessed, native=self.native is not None)
+
+    # --- which constraint fails on which row (Rust assert_constraints_on_trace)
+    def _constraint_program(self) -> Program:
+        """The compiled constraints: `program`, or for the hand-written kinds (which prove on their own kernel) the program the
+        other evals take, compiled at the first use."""
+        if self.program is not None:
+            return self.program
+        if self._check_program is None:
+            pe = ProgramEvaluator(self.claimed_sum, self.log_size)
+            self.eval.evaluate(pe)
+            pe.check_finished()
+            self._check_program = pe.compile(self.n_columns, len(self.preprocessed_column_indices))
+        return self._check_program
+
+    def constraint_failures(self, main, preprocessed=(), interaction=()) -> list:
+        """The constraints the trace breaks, as ConstraintFailure(constraint, n_rows, first_row) in constraint order; [] for a
+        trace that satisfies the AIR.  main / preprocessed / interaction: the component's own columns (HipColumns, evaluations or
+        arrays) on CanonicCoset(log_size).circle_domain() in storage order; preprocessed[i] is the column
+        get_preprocessed_column(i) reads.  A secure (LogUp) constraint is reported once.  One launch (check_program)."""
+        cols = [_trace_column(c) for c in list(main) + list(preprocessed) + list(interaction)]
+        want = (self.n_columns, len(self.preprocessed_column_indices), self.n_interaction_columns)
+        if (len(main), len(preprocessed), len(interaction)) != want:
+            raise ValueError(f"the component reads {want[0]} main, {want[1]} preprocessed and {want[2]} interaction columns, "
+                             f"not {len(main)}, {len(preprocessed)} and {len(interaction)}")
+        if self.n_constraints == 0:
+            return []
+        groups = [c for c, secure in enumerate(self.secure_flags) for _ in range(4 if secure else 1)]
+        report = check_program(cols, self.log_size, self._constraint_program(), groups)
+        return [ConstraintFailure(c, n, first) for c, (n, first) in enumerate(report) if n]
+
+    def assert_constraints(self, main, preprocessed=(), interaction=()) -> None:
+        """Raises prover.ConstraintViolation (a ConstraintsNotSatisfied) naming the first failing constraint and its first row."""
+        failures = self.constraint_failures(main, preprocessed, interaction)
+        if failures:
+            from .prover import ConstraintViolation
+            raise ConstraintViolation(None, failures, 1 << self.log_size)
 
     # --- Component
     def max_constraint_log_degree_bound(self) -> int:

@@ -12,6 +12,9 @@
 //     one output column (tstwo_air_eval_columns: the numerators and denominator terms of a LogUp interaction trace, derived
 //     from `evaluate` by tstwo_amd/logup.py derive_interaction_trace).  It shares the interpreter with k_air_program
 //     (fetch, exec_op, the LDS register file) and has no accumulators, coefficients or denominators.
+//   k_air_check<W>  the same programs on the trace domain with a reduction in place of the store: per constraint the number of
+//     rows on which it is non-zero and the first of them in coset order (tstwo_air_check_constraints: a trace satisfies the AIR
+//     exactly when every count is 0).  The third user of the interpreter.
 //   tstwo_air_eval_compiled  the contract and argument checks of k_air_program's entry, run by a kernel that air_native.hip
 //     compiled from the program (air_codegen.h writes its source; the program validator of all three entries lives there).
 //   tstwo_air_eval_columns_compiled  the same for k_air_columns: the entry's argument checks, a kernel compiled from the STORE
@@ -81,6 +84,15 @@ struct ColArgs {
 // k_air_columns(ColPtrs cols, ColPtrs out, ColArgs): the output table is the second kernel argument (kSecondTableOff)
 static_assert(2 * sizeof(ColPtrs) + sizeof(ColArgs) <= 4096, "kernel arguments exceed 4 KiB");
 static_assert(TSTWO_AIR_COLUMNS_MAX_OUT <= kMaxColsPerLaunch, "the output table travels by value");
+
+struct CheckArgs {
+    const u32 *prog;                         // device: 2 words per instruction; the host sets dst = 1 in the last ACC of a constraint
+    u32 *report;                             // device: (failing rows, first failing coset row) per constraint
+    u32 n_instr, n_rows, log, n_constraints;
+    u32 tally;                               // word offset of the workgroup's (count, first row) pairs in LDS, behind the registers
+};
+static_assert(sizeof(ColPtrs) + sizeof(CheckArgs) <= 4096, "kernel arguments exceed 4 KiB");
+constexpr u32 kNoRow = 0xffffffffu;          // the report's "no failing row"
 
 // ---------------------------------------------------------------- shared by both kernels
 template <int W>
@@ -269,10 +281,15 @@ __device__ __forceinline__ u32 neighbour_row(u32 r, u32 eval_log, u32 log_expand
 // 2 t + odd where t = rev(j) for even k and ~rev(j) (over L bits) for odd k (csrc/logup.hip); the inverse is the same two steps
 // backwards, so a neighbour costs two bit reversals.
 __device__ __forceinline__ u32 rev_bits(u32 x, u32 bits) { return bits ? __builtin_bitreverse32(x) >> (32 - bits) : 0; }
-__device__ __forceinline__ u32 trace_neighbour_row(u32 r, u32 log, int off) {
+// the coset row k of bit-reversed position r (k_air_check reports rows in this order: the trace as the user wrote it)
+__device__ __forceinline__ u32 coset_row(u32 r, u32 log) {
     const u32 L = log - 1, mask = (1u << L) - 1;
     const u32 odd = r & 1, t = r >> 1;
-    const u32 k = 2 * rev_bits(odd ? ~t & mask : t, L) + odd;
+    return 2 * rev_bits(odd ? ~t & mask : t, L) + odd;
+}
+__device__ __forceinline__ u32 trace_neighbour_row(u32 r, u32 log, int off) {
+    const u32 L = log - 1, mask = (1u << L) - 1;
+    const u32 k = coset_row(r, log);
     const u32 k2 = (k + (u32)off) & ((1u << log) - 1);
     const u32 odd2 = k2 & 1, t2 = rev_bits(k2 >> 1, L);
     return 2 * (odd2 ? ~t2 & mask : t2) + odd2;
@@ -419,6 +436,84 @@ __global__ void __launch_bounds__(kWave) k_air_columns(ColPtrs cols, ColPtrs out
                 continue;
             }
             exec_op<W>(cols, regs, in, row, nb);
+        }
+    }
+}
+
+// The interpreter on the trace domain with a reduction in place of a store (tstwo_air_check_constraints): an ACC ORs r[x] of the
+// lane's W rows into `nz`, and the last ACC of a constraint (marked by the host in dst; a secure constraint is four ACCs) takes
+// one ballot over the wave.  A clean trace pays nothing more.  A non-zero ballot counts the failing rows, finds the smallest of
+// them in coset order (coset_row: computed on this path only) and adds both to the workgroup's pair for the constraint in LDS,
+// behind the registers; workgroups are one wave, so lane 0 updates the pairs plainly.  Behind the grid-stride loop the workgroup
+// issues one atomic add and one atomic min per constraint that failed in it, so the global atomics are bounded by workgroups x
+// constraints even when every row fails.  k_air_check_init has written (0, kNoRow) to every pair of the report before.
+// Can a register hold 2^31 - 1?  CONST is refused from 2^31 - 1 on, and m31_add / _sub / _neg / _mul / _sqr give canonical values
+// for canonical operands, but LOAD copies the column's word as it is: a column that holds P (zero, not canonical) puts P in a
+// register, and an ACC may read that register directly.  So every value is reduced (min(v, v - P): P -> 0, canonical values
+// stay) before it is ORed in.
+// The trip count is wave-uniform and no lane leaves the loop: below 64 lanes of rows the others run row 0 and vote zero.
+__global__ void __launch_bounds__(kThreads) k_air_check_init(u32 *report, u32 n_constraints) {
+    const u32 c = threadIdx.x;
+    if (c < n_constraints) { report[2 * c] = 0; report[2 * c + 1] = kNoRow; }
+}
+static_assert(TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS <= kThreads, "k_air_check_init is one workgroup");
+
+template <int W>
+__global__ void __launch_bounds__(kWave) k_air_check(ColPtrs cols, CheckArgs a) {
+    extern __shared__ u32 regs[];
+    u32 *tally = regs + a.tally;
+    const k32 prog = (k32)a.prog;
+    const u32 lane = threadIdx.x;
+    for (u32 c = lane; c < a.n_constraints; c += kWave) { tally[2 * c] = 0; tally[2 * c + 1] = kNoRow; }
+    __syncthreads();
+    const u32 n_lanes = a.n_rows / W, stride = gridDim.x * kWave;
+    const TraceNeighbour nb = {a.log};
+    for (u32 t0 = blockIdx.x * kWave; t0 < n_lanes; t0 += stride) {
+        const bool live = t0 + lane < n_lanes;
+        const u32 row = live ? (t0 + lane) * W : 0;
+        u32 nz[W];
+#pragma unroll
+        for (int e = 0; e < W; e++) nz[e] = 0;
+#pragma unroll 1
+        for (u32 pc = 0; pc < a.n_instr; pc++) {
+            const Instr in = fetch(prog, pc);
+            if (in.op == TSTWO_AIR_OP_ACC) {
+                u32 v[W];
+                lds_read<W>(regs, in.x, v);
+#pragma unroll
+                for (int e = 0; e < W; e++) nz[e] |= min(v[e], v[e] - M31_P);
+                if (in.dst == 0) continue;          // more ACCs of this constraint follow
+                u32 any = 0;
+#pragma unroll
+                for (int e = 0; e < W; e++) any |= nz[e];
+                if (__ballot(live && any != 0)) {   // wave-uniform
+                    u32 count = 0, first = kNoRow;
+#pragma unroll
+                    for (int e = 0; e < W; e++)
+                        if (live && nz[e] != 0) { count++; first = min(first, coset_row(row + e, a.log)); }
+#pragma unroll
+                    for (int s = kWave / 2; s; s >>= 1) {
+                        count += (u32)__shfl_xor((int)count, s);
+                        first = min(first, (u32)__shfl_xor((int)first, s));
+                    }
+                    if (lane == 0) {
+                        tally[2 * in.w1] += count;
+                        tally[2 * in.w1 + 1] = min(tally[2 * in.w1 + 1], first);
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < W; e++) nz[e] = 0;
+                continue;
+            }
+            exec_op<W>(cols, regs, in, row, nb);
+        }
+    }
+    __syncthreads();
+    for (u32 c = lane; c < a.n_constraints; c += kWave) {
+        const u32 count = tally[2 * c];
+        if (count) {
+            __hip_atomic_fetch_add(a.report + 2 * c, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_min(a.report + 2 * c + 1, tally[2 * c + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -685,6 +780,59 @@ int tstwo_air_eval_columns_compiled(uint64_t kernel_id, const u32 *const *cols, 
     const unsigned grid = grid_for(a.n_rows / (vec ? 4 : 1));
     a.stride = grid * kThreads;
     return air_native_launch_columns(kernel_id, vec, grid, cp, op, a);
+}
+
+int tstwo_air_check_constraints(const u32 *const *cols, size_t n_cols, u32 log_size, const u32 *program, size_t program_len,
+                                size_t n_constraints, u32 *report) {
+    TSTWO_REQUIRE_READY();
+    if (log_size < 1 || log_size > kMaxLog) return bad("air check: log_size out of range");
+    if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return bad("air check: number of columns out of range");
+    if (n_constraints == 0 || n_constraints > TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS) return bad("air check: number of constraints out of range");
+    if (program_len == 0 || program_len > TSTWO_AIR_PROGRAM_MAX_INSTR) return bad("air check: program length out of range");
+    if (!program) return bad("null host argument");
+    TSTWO_REQUIRE_TABLE(cols, n_cols);
+    if (!report || !aligned16(report)) return bad("air check: null or misaligned report");
+    // the program words travel through the small-upload ring, which a captured graph cannot replay
+    if (stream_is_capturing()) return bad("host-array upload during graph capture (the air check program cannot be recorded)");
+    u32 n_regs = 0;
+    if (const char *why = check_assert_program(program, program_len, n_cols, n_constraints, n_regs)) return bad(std::string("air check: ") + why);
+    // the uploaded copy marks the last ACC of every constraint in dst (ignored by every other entry): the kernel votes there
+    static_assert(2 * TSTWO_AIR_PROGRAM_MAX_INSTR * 4 <= kUpSlotBytes, "program upload exceeds one ring slot");
+    u32 staged[2 * TSTWO_AIR_PROGRAM_MAX_INSTR];
+    std::copy(program, program + 2 * program_len, staged);
+    u32 *last_acc = nullptr;
+    for (size_t pc = 0; pc < program_len; pc++) {
+        u32 *w = staged + 2 * pc;
+        if ((w[0] & 0xffu) != TSTWO_AIR_OP_ACC) continue;
+        w[0] &= ~0xff00u;
+        if (last_acc && last_acc[1] != w[1]) last_acc[0] |= 1u << 8;
+        last_acc = w;
+    }
+    last_acc[0] |= 1u << 8;                     // check_assert_program saw at least one ACC
+    const size_t bytes = 2 * program_len * sizeof(u32);
+    if (int rc = ensure_scratch(bytes)) return rc;
+    if (int rc = small_h2d(ctx().scratch, staged, bytes)) return rc;
+    ColPtrs cp;
+    if (int rc = fill_col_table(cp, cols, n_cols, 0)) return rc;
+    CheckArgs a = {};
+    a.prog = ctx().scratch;
+    a.report = report;
+    a.n_instr = (u32)program_len;
+    a.log = log_size;
+    a.n_rows = 1u << log_size;
+    a.n_constraints = (u32)n_constraints;
+    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, nullptr, 0);
+    const size_t regs_bytes = interpreter_lds(n_regs, vec);
+    a.tally = (u32)(regs_bytes / sizeof(u32));
+    const size_t lds = regs_bytes + 2 * n_constraints * sizeof(u32);
+    const unsigned grid = interpreter_grid(a.n_rows, vec);
+    // the report in a launch of its own: the kernel's workgroups add to it in any order, and the grid may wrap
+    hipLaunchKernelGGL(k_air_check_init, dim3(1), dim3(kThreads), 0, ctx().stream, report, a.n_constraints);
+    TSTWO_LAUNCH_CHECK();
+    if (vec) hipLaunchKernelGGL(k_air_check<4>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, a);
+    else hipLaunchKernelGGL(k_air_check<1>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, a);
+    TSTWO_LAUNCH_CHECK();
+    return TSTWO_OK;
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // air_codegen.h — a constraint program (the words of tstwo_air_eval_program) as HIP source text (host only: no HIP, no context).
 // check_program validates the programs of every entry (tstwo_air_eval_program, tstwo_air_eval_columns,
-// tstwo_air_program_compile, tstwo_air_columns_compile); air_codegen writes, for one program, two extern "C" kernels with the contract of k_air_program
+// tstwo_air_check_constraints, tstwo_air_program_compile, tstwo_air_columns_compile); air_codegen writes, for one program, two extern "C" kernels with the contract of k_air_program
 // (air.hip): for every row r, accum[r] += (sum_k coeff_k e_k(r)) * denom_inv[r >> trace_log].  tests/test_cpu_air_codegen.py
 // builds tests/air_codegen_main.cpp around this header alone.
 //
@@ -78,6 +78,29 @@ inline const char *check_acc_program(const uint32_t *program, size_t program_len
     if (const char *why = check_program(program, program_len, n_cols, TSTWO_AIR_OP_ACC, n_regs, [&](uint32_t) { n_acc++; return (const char *)nullptr; }))
         return why;
     if (n_acc != n_constraints) return "the number of ACC instructions differs from n_constraints";
+    return nullptr;
+}
+
+// What tstwo_air_check_constraints accepts: an ACC program whose ACCs carry, in w1, the index of the constraint they belong to
+// (a secure constraint is four ACCs with one index).  The indices start at 0, never decrease, rise by at most 1 from one ACC to
+// the next and end at n_constraints - 1; the number of ACCs is free.
+inline const char *check_assert_program(const uint32_t *program, size_t program_len, size_t n_cols, size_t n_constraints, uint32_t &n_regs) {
+    if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return "number of columns out of range";
+    if (program_len == 0 || program_len > TSTWO_AIR_PROGRAM_MAX_INSTR) return "program length out of range";
+    if (n_constraints == 0 || n_constraints > TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS) return "number of constraints out of range";
+    size_t n_acc = 0;
+    uint32_t last = 0;
+    auto on_acc = [&](uint32_t c) -> const char * {
+        if (n_acc == 0 && c != 0) return "first constraint index is not 0";
+        if (c < last) return "constraint index decreases";
+        if (c > last + 1) return "constraint index skips";
+        if (c >= n_constraints) return "constraint index out of range";
+        last = c;
+        n_acc++;
+        return (const char *)nullptr;
+    };
+    if (const char *why = check_program(program, program_len, n_cols, TSTWO_AIR_OP_ACC, n_regs, on_acc)) return why;
+    if (n_acc == 0 || last != n_constraints - 1) return "last constraint index is not n_constraints - 1";
     return nullptr;
 }
 

@@ -9,13 +9,16 @@ composition value from the sampled coordinates equals the one the constraints gi
 the composition root, nothing is read back from the device."""
 from __future__ import annotations
 
+from collections import namedtuple
 from dataclasses import dataclass
 
-from .air import ComponentProvers, Components, Trace
-from .circle import CirclePoint
+from .air import INTERACTION_TRACE_IDX, ORIGINAL_TRACE_IDX, PREPROCESSED_TRACE_IDX, ComponentProvers, Components, Trace
+from .circle import CanonicCoset, CirclePoint
+from .constraint_framework import ConstraintFailure
 from .fields import QM31
 from .pcs import CommitmentSchemeProof
 from .pcs_verifier import VerificationError
+from .poly import evaluate_polynomials
 
 SECURE_EXTENSION_DEGREE = 4
 
@@ -25,6 +28,24 @@ class ConstraintsNotSatisfied(Exception):
 
     def __init__(self, msg: str = "Constraints not satisfied."):
         super().__init__(msg)
+
+
+class ConstraintViolation(ConstraintsNotSatisfied):
+    """ConstraintsNotSatisfied with the place: `component` (its index among the components proved, None from
+    FrameworkComponent.assert_constraints), `constraint` (add_constraint calls in the order `evaluate` makes them), `row` (the
+    first failing row in coset order: the row of the trace as it was written) and `n_rows` (on how many rows it fails) of the
+    first failing constraint, and `failures`, every record (constraint_failures / diagnose)."""
+
+    def __init__(self, component, failures, total_rows: int):
+        first = failures[0]
+        self.component, self.failures = component, list(failures)
+        self.constraint, self.n_rows, self.row = first.constraint, first.n_rows, first.first_row
+        where = "" if component is None else f"component {component}: "
+        super().__init__(f"{where}constraint {self.constraint} is non-zero on {self.n_rows} of {total_rows} rows, first at row {self.row}")
+
+
+# one failing constraint of a proof's components (diagnose): ConstraintFailure with the component's index in front
+ComponentFailure = namedtuple("ComponentFailure", "component constraint n_rows first_row")
 
 
 class InvalidStructure(VerificationError):
@@ -83,10 +104,33 @@ def _uses_logup(components) -> bool:
     return any(getattr(c, "n_interaction_columns", 0) for c in components)
 
 
-def prove(components, channel, commitment_scheme) -> StarkProof:
+def diagnose(components, commitment_scheme) -> list:
+    """Which constraint of which component the committed trace breaks, on which row: ComponentFailure(component, constraint,
+    n_rows, first_row) records in component and constraint order, [] for a trace that satisfies every AIR.  For every component
+    the committed polynomials it reads (all three trees) are evaluated on CanonicCoset(log_size).circle_domain(), one
+    evaluate_polynomials per tree, and FrameworkComponent.constraint_failures runs one check launch over them.  Needs nothing
+    that `prove` does not hold."""
+    trace = Trace.of(commitment_scheme)
+    out = []
+    for i, comp in enumerate(components):
+        domain = CanonicCoset(comp.log_size).circle_domain()
+        trees = [(ORIGINAL_TRACE_IDX, list(comp._columns())), (PREPROCESSED_TRACE_IDX, list(comp.preprocessed_column_indices))]
+        if comp.n_interaction_columns:
+            trees.append((INTERACTION_TRACE_IDX, list(comp._columns(INTERACTION_TRACE_IDX))))
+        cols = [evaluate_polynomials([trace.polys[tree][ci] for ci in indices], domain, commitment_scheme.twiddles) if indices else []
+                for tree, indices in trees]
+        out += [ComponentFailure(i, *f) for f in comp.constraint_failures(*cols)]
+    return out
+
+
+_diagnose = diagnose                    # `prove` has a flag of the same name
+
+
+def prove(components, channel, commitment_scheme, diagnose: bool = False) -> StarkProof:
     """components: FrameworkComponents whose trace trees (preprocessed, main, and the interaction tree when a component uses
     LogUp: logup.py's caller protocol) are already committed in `commitment_scheme` (a CommitmentSchemeProver).  Raises
-    ConstraintsNotSatisfied when the trace breaks a constraint."""
+    ConstraintsNotSatisfied when the trace breaks a constraint; with diagnose=True the exception is a ConstraintViolation that
+    names the first failing component, constraint and row (prover.diagnose, run only after the failure), when the check finds one."""
     trace = Trace.of(commitment_scheme)
     if _uses_logup(components) and len(trace.polys) != 3:
         raise ValueError(f"LogUp components need 3 committed trace trees (preprocessed, main, interaction), not {len(trace.polys)}")
@@ -103,6 +147,12 @@ def prove(components, channel, commitment_scheme) -> StarkProof:
     proof = StarkProof(commitment_scheme.prove_values(_sample_points(comps, oods_point), channel))
     # sanity check: the sampled composition value against the constraints at the OODS point
     if proof.extract_composition_oods_eval() != comps.eval_composition_polynomial_at_point(oods_point, proof.sampled_values, random_coeff):
+        if diagnose:
+            failures = _diagnose(components, commitment_scheme)
+            if failures:
+                first = failures[0].component
+                raise ConstraintViolation(first, [ConstraintFailure(*f[1:]) for f in failures if f.component == first],
+                                          1 << components[first].log_size)
         raise ConstraintsNotSatisfied()
     return proof
 
