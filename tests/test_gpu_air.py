@@ -2,11 +2,15 @@
 (tests/air_model.py), the composition polynomial against the model's, and prove -> verify for wide Fibonacci, the Rust tutorial's
 example 05 and a multi-component set, with tampered proofs rejected and no read-back in the composition phase."""
 import copy
+import ctypes as C
+import re
 
 import numpy as np
 import pytest
 
 import air_model as M
+import air_plan as AP
+import air_program_model as X
 from tstwo_amd import _lib as L
 from tstwo_amd import air as A
 from tstwo_amd import constraint_framework as F
@@ -89,6 +93,96 @@ def test_constraint_quotients_rejects_bad_arguments():
         A.evaluate_constraint_quotients(A.AIR_WIDE_FIB, cols, 2, 1, [q((1, 0, 0, 0))], [1, 1], acc)
     with pytest.raises(L.TstwoError):     # mul-add takes exactly 3 columns
         A.evaluate_constraint_quotients(A.AIR_MUL_ADD, cols, 2, 1, [q((1, 0, 0, 0))], [1, 1], acc)
+
+
+# ------------------------------------------------------------------ one row per lane, and the grid-stride loops
+# Sizes from the plan's model (tests/air_plan.py) for the part the tests run on: the smallest logs at which the lanes of
+# k_wide_fib_trace, k_constraint_quotients and k_air_program take a second turn round the grid, in fours and (every pointer one
+# word off a 16-byte boundary) row by row; and a small size row by row, which nothing above runs.
+STRIDE_CASES = [("w1-small", 1, 6), ("w4-stride", 4, None), ("w1-stride", 1, None)]
+STRIDE_IDS = [c[0] for c in STRIDE_CASES]
+
+
+def _n_cus():
+    return int(re.search(r"(\d+) CUs", L.device_name()).group(1))
+
+
+def _stride_shape(entry, w, small_log, log_expand, n_cols, n_terminal, program_len=0, n_regs=0):
+    """(log of the rows, word offset of every pointer); asserts from the model that the call runs at W = w and strides, or does not."""
+    log = small_log if small_log is not None else AP.first_striding_log(entry, w, _n_cus())
+    i = AP.Input(entry, AP.MUL_ADD, log, log_expand, n_cols, n_terminal, program_len, n_regs, w == 4, _n_cus())
+    assert AP.plan(i).w == w and AP.strides(i) == (small_log is None), i
+    assert small_log is not None or not AP.strides(i._replace(log=log - 1))
+    return log, 0 if w == 4 else 1
+
+
+def _shifted(arrays, k):
+    """Device copies that begin k words into their buffers, and the pointers to them."""
+    bufs = [col(np.concatenate([np.zeros(k, dtype=np.uint64), np.asarray(a, dtype=np.uint64)])) for a in arrays]
+    return bufs, [b.ptr + 4 * k for b in bufs]
+
+
+@pytest.mark.parametrize("name,w,small_log", STRIDE_CASES, ids=STRIDE_IDS)
+def test_wide_fib_trace_kernel_at_both_widths_and_beyond_the_grid(name, w, small_log):
+    log, k = _stride_shape("wide_fib_trace", w, small_log, 0, 2, 0)
+    rng = np.random.default_rng(300 + log)
+    a, b = rng.integers(0, P, size=1 << log, dtype=np.uint64), rng.integers(0, P, size=1 << log, dtype=np.uint64)
+    (da, db), (pa, pb) = _shifted([a, b], k)
+    outs = [HipColumn.zeros((1 << log) + k) for _ in range(2)]
+    L.call("tstwo_air_wide_fib_trace", C.c_void_p(pa), C.c_void_p(pb), log, L.ptr_array([o.ptr + 4 * k for o in outs]), 2)
+    for o, want in zip(outs, (a, b)):
+        got = o.to_numpy()
+        assert np.array_equal(got[k:], want.astype(np.uint32)) and not got[:k].any()
+    if name == "w1-small":          # more than the two columns that are copies: the recurrence, row by row
+        outs = [HipColumn.zeros((1 << log) + k) for _ in range(5)]
+        L.call("tstwo_air_wide_fib_trace", C.c_void_p(pa), C.c_void_p(pb), log, L.ptr_array([o.ptr + 4 * k for o in outs]), 5)
+        for o, want in zip(outs, M.wide_fib_trace(a, b, 5)):
+            assert np.array_equal(o.to_numpy()[k:], want.astype(np.uint32))
+
+
+@pytest.mark.parametrize("name,w,small_log", STRIDE_CASES, ids=STRIDE_IDS)
+def test_constraint_quotients_kernel_at_both_widths_and_beyond_the_grid(name, w, small_log):
+    """MUL_ADD over 3 columns, bit for bit against the model on every row."""
+    log_expand = 1
+    eval_log, k = _stride_shape("quotients", w, small_log, log_expand, 3, 1)
+    trace_log, n = eval_log - log_expand, 1 << eval_log
+    rng = np.random.default_rng(400 + eval_log)
+    cols = [rng.integers(0, P, size=n, dtype=np.uint64) for _ in range(3)]
+    coeffs, dinv = [rand_felt(rng)], M.denom_inv(trace_log, eval_log)
+    pre = rng.integers(0, P, size=(4, n), dtype=np.uint64)
+    want = M.quotients_on_domain(M.MUL_ADD, cols, trace_log, log_expand, coeffs, dinv, pre)
+    dcols, pcols = _shifted(cols, k)
+    dacc, pacc = _shifted(pre, k)
+    L.call("tstwo_air_constraint_quotients", A.AIR_MUL_ADD, L.ptr_array(pcols), 3, trace_log, log_expand, L.u32x(list(coeffs[0])), 1,
+           L.u32x([int(d) for d in dinv]), L.p4(pacc))
+    for j in range(4):
+        got = dacc[j].to_numpy()
+        assert np.array_equal(got[k:], want[j].astype(np.uint32)) and not got[:k].any(), j
+
+
+# r0 = x0, r1 = x1 one row back, r2 = r0 r1 - x2: 3 columns, 6 instructions, one constraint
+STRIDE_PROGRAM = (X.encode(X.LOAD, 0, 0, 0) + X.encode(X.LOAD, 1, 1, -1) + X.encode(X.MUL, 2, 0, 1) + X.encode(X.LOAD, 1, 2, 0)
+                  + X.encode(X.SUB, 2, 2, 1) + X.encode(X.ACC, 0, 2))
+
+
+@pytest.mark.parametrize("name,w,small_log", STRIDE_CASES[1:], ids=STRIDE_IDS[1:])
+def test_program_interpreter_beyond_the_grid_matches_the_model(name, w, small_log):
+    """k_air_program where its one-wave workgroups wrap, against the integer model (tests/air_program_model.py) on every row."""
+    log_expand = 1
+    eval_log, k = _stride_shape("eval_program", w, small_log, log_expand, 3, 1, len(STRIDE_PROGRAM) // 2, 3)
+    trace_log, n = eval_log - log_expand, 1 << eval_log
+    rng = np.random.default_rng(500 + eval_log)
+    cols = [rng.integers(0, P, size=n, dtype=np.uint64) for _ in range(3)]
+    coeffs, dinv = [rand_felt(rng)], M.denom_inv(trace_log, eval_log)
+    pre = rng.integers(0, P, size=(4, n), dtype=np.uint64)
+    want = X.eval_program_on_domain(STRIDE_PROGRAM, cols, trace_log, log_expand, coeffs, dinv, pre)
+    dcols, pcols = _shifted(cols, k)
+    dacc, pacc = _shifted(pre, k)
+    L.call("tstwo_air_eval_program", L.ptr_array(pcols), 3, trace_log, log_expand, L.u32x(STRIDE_PROGRAM), len(STRIDE_PROGRAM) // 2,
+           L.u32x(list(coeffs[0])), 1, L.u32x([int(d) for d in dinv]), L.p4(pacc))
+    for j in range(4):
+        got = dacc[j].to_numpy()
+        assert np.array_equal(got[k:], want[j].astype(np.uint32)) and not got[:k].any(), j
 
 
 # ------------------------------------------------------------------ composition polynomial

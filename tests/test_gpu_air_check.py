@@ -18,6 +18,7 @@ from conftest import P
 pytestmark = pytest.mark.gpu
 
 import air_check_model as CK  # noqa: E402
+import air_plan as AP  # noqa: E402
 import air_program_model as X  # noqa: E402
 import interaction_evals as E  # noqa: E402
 import logup_model as LM  # noqa: E402
@@ -223,7 +224,6 @@ def test_a_column_word_of_2_pow_31_minus_1_is_zero():
 # ------------------------------------------------------------------ the grid-stride wrap
 MUL_ADD = (X.encode(X.LOAD, 0, 0, 0) + X.encode(X.LOAD, 1, 1, 0) + X.encode(X.MUL, 1, 0, 1) + X.encode(X.ADD, 0, 0, 1) + X.encode(X.LOAD, 1, 2, 0)
            + X.encode(X.SUB, 0, 0, 1) + X.encode(X.ACC, 0, 0))
-WORKGROUPS_PER_CU, WAVE = 32, 64            # csrc/air.hip interpreter_grid: at most n_cus * 32 one-wave workgroups
 
 
 def n_cus():
@@ -240,12 +240,12 @@ def _raw_check(ptrs, log, words, n_constraints=1):
 
 @pytest.mark.parametrize("rows_per_lane,unaligned", [(1, True), (4, False)], ids=["one-row-unaligned", "four-rows-aligned"])
 def test_above_the_grid_cap(rows_per_lane, unaligned):
-    """The smallest log whose rows exceed the launch's cap (n_cus * 32 workgroups of 64 lanes of W rows), so that every workgroup
-    strides: log 20 at W = 1 and log 22 at W = 4 on a 256-CU part.  One changed cell in the last quarter of the rows (reached only
-    by a workgroup's later iterations), then every row changed."""
-    cap_rows = n_cus() * WORKGROUPS_PER_CU * WAVE * rows_per_lane
-    log = cap_rows.bit_length()                                       # the smallest log with 2^log > cap_rows
-    assert (1 << log) > cap_rows >= (1 << (log - 1))
+    """The smallest log whose rows exceed what the launch's grid covers (tests/air_plan.py, for this part's CUs), so that every
+    workgroup strides: log 20 at W = 1 and log 22 at W = 4 on a 256-CU part.  One changed cell in the last quarter of the rows
+    (reached only by a workgroup's later iterations), then every row changed."""
+    log = AP.first_striding_log("check", rows_per_lane, n_cus())
+    shape = AP.Input("check", 0, log, 0, 3, 1, len(MUL_ADD) // 2, 2, not unaligned, n_cus())
+    assert AP.plan(shape).w == rows_per_lane and AP.strides(shape) and not AP.strides(shape._replace(log=log - 1))
     n = 1 << log
     rng = np.random.default_rng(48)
     x0, x1 = (rng.integers(0, P, size=n, dtype=np.uint64) for _ in range(2))
@@ -325,6 +325,19 @@ def test_256_constraints():
         words += X.encode(X.CONST, 2, 0, int(cols[c % 2][c % 64])) + X.encode(X.SUB, 2, c % 2, 2) + X.encode(X.ACC, 0, 2)
     rep = against_model(words, cols, log, list(range(256)))
     assert all(n >= (1 << log) - 2 for n, _ in rep)
+
+
+@pytest.mark.parametrize("place", ["aligned", "all+4"])
+@pytest.mark.parametrize("n_regs", [1, 32])
+def test_the_tally_behind_one_register_and_behind_32(n_regs, place):
+    """REGISTER_CASES: the (count, first row) pairs lie in LDS directly behind the registers, at the smallest and at the largest
+    register file, four rows per lane and one.  Constraint 0 is the sum of every register, constraint 1 a single one."""
+    log = 5
+    words = AP.register_program(n_regs, 3, [0, 1])
+    assert 1 + max((w >> 8) & 0xff for w in words[::2] if w & 0xff != X.ACC) == n_regs
+    cols = _columns(np.random.default_rng(51 + n_regs), 3, log, "sparse")
+    rep = against_model(words, cols, log, [0, 1], place)
+    assert all(0 < n < 1 << log for n, _ in rep), rep
 
 
 # ------------------------------------------------------------------ two calls behind a plug

@@ -9,6 +9,7 @@ one wave of four-row lanes), log 9 (two workgroups), log 12 with every column on
 at a size that would vectorise), log 22 (above the grid cap of 32 workgroups per CU on a 256-CU part: the kernel strides);
 programs of 1 and of 32 registers; 1 and 64 outputs; 65 input columns (the column table in device memory)."""
 import ctypes as C
+import re
 
 import numpy as np
 import pytest
@@ -17,6 +18,7 @@ from conftest import P
 
 pytestmark = pytest.mark.gpu
 
+import air_plan as AP  # noqa: E402
 import air_program_model as X  # noqa: E402
 import columns_model as CM  # noqa: E402
 import sequence as SQ  # noqa: E402
@@ -122,8 +124,12 @@ def test_the_largest_offsets(log, offset):
 
 
 def test_above_the_grid_cap():
-    """2^22 rows are 2^20 lanes of four rows, 16384 one-wave workgroups: twice the cap of 32 per CU on a 256-CU part."""
-    log = 22
+    """The smallest log whose rows, in fours, the grid does not cover (tests/air_plan.py, for this part's CUs): on a 256-CU part
+    2^22 rows, 2^20 lanes, 16384 one-wave workgroups, twice the grid."""
+    n_cus = int(re.search(r"(\d+) CUs", L.device_name()).group(1))
+    log = AP.first_striding_log("eval_columns", 4, n_cus)
+    shape = AP.Input("eval_columns", 0, log, 0, 2, 1, 7, 3, True, n_cus)
+    assert AP.plan(shape).w == 4 and AP.strides(shape) and not AP.strides(shape._replace(log=log - 1))
     rng = np.random.default_rng(47)
     cols = [rng.integers(0, P, size=1 << log, dtype=np.uint32) for _ in range(2)]
     words = (X.encode(X.LOAD, 0, 0, 0) + X.encode(X.LOAD, 1, 1, -1) + X.encode(X.MUL, 2, 0, 1) + X.encode(X.LOAD, 1, 0, 2)

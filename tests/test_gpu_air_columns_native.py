@@ -23,6 +23,7 @@ from conftest import P
 pytestmark = pytest.mark.gpu
 
 import air_model as M  # noqa: E402
+import air_plan as AP  # noqa: E402
 import air_program_model as X  # noqa: E402
 import columns_model as CM  # noqa: E402
 import sequence as SQ  # noqa: E402
@@ -193,12 +194,16 @@ def _n_cus():
     return int(re.search(r"(\d+) CUs", L.device_name()).group(1))
 
 
-@pytest.mark.parametrize("log,aligned", [(23, True), (21, False)])
-def test_rows_beyond_the_grid_cap_match_the_interpreter(log, aligned):
-    """More rows than 16 workgroups per CU of 256 lanes cover (W rows per lane): lanes stride.  A 7-instruction program over 2
-    columns, the smallest log that gets there on 256 CUs; compared against the interpreter on the device."""
+@pytest.mark.parametrize("aligned", [True, False], ids=["23-True", "21-False"])
+def test_rows_beyond_the_grid_cap_match_the_interpreter(aligned):
+    """More rows than the compiled kernel's grid covers at W rows per lane (tests/air_plan.py, for this part's CUs): lanes stride.
+    A 7-instruction program over 2 columns, the smallest log that gets there (23 and 21 on 256 CUs); compared against the
+    interpreter on the device."""
+    log = AP.first_striding_log("eval_columns_compiled", 4 if aligned else 1, _n_cus())
+    shape = AP.Input("eval_columns_compiled", 0, log, 0, 2, 1, 0, 0, aligned, _n_cus())
+    assert AP.plan(shape).w == (4 if aligned else 1) and AP.strides(shape) and not AP.strides(shape._replace(log=log - 1))
+    assert AP.strides(shape._replace(entry="eval_columns", program_len=7, n_regs=3))      # and the interpreter beside it
     n, k = 1 << log, 0 if aligned else 1
-    assert n > _n_cus() * 16 * 256 * (4 if aligned else 1)
     words = (X.encode(X.LOAD, 0, 0, 0) + X.encode(X.LOAD, 1, 1, -1) + X.encode(X.MUL, 2, 0, 1) + X.encode(X.LOAD, 1, 0, 2)
              + X.encode(X.ADD, 2, 2, 1) + X.encode(X.NEG, 2, 2) + X.encode(STORE, 0, 2, 0))
     rng = np.random.default_rng(log)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import air_model as M
+import air_plan as AP
 import air_program_model as X
 import saturation as S
 from arena import Arena, rin, rinout
@@ -186,14 +187,17 @@ def _n_cus():
     return int(re.search(r"(\d+) CUs", L.device_name()).group(1))
 
 
-@pytest.mark.parametrize("eval_log,aligned", [(23, True), (21, False)])
-def test_rows_beyond_the_grid_cap_match_the_interpreter(eval_log, aligned):
-    """More rows than 16 workgroups per CU of 256 lanes cover (W rows per lane): lanes stride.  3 columns, the smallest log that
-    gets there on 256 CUs; compared against the interpreter on the device."""
+@pytest.mark.parametrize("aligned", [True, False], ids=["23-True", "21-False"])
+def test_rows_beyond_the_grid_cap_match_the_interpreter(aligned):
+    """More rows than the compiled kernel's grid covers at W rows per lane (tests/air_plan.py, for this part's CUs): lanes stride.
+    3 columns, the smallest log that gets there (23 and 21 on 256 CUs); compared against the interpreter on the device."""
     log_expand = 2
+    eval_log = AP.first_striding_log("eval_compiled", 4 if aligned else 1, _n_cus())
+    shape = AP.Input("eval_compiled", 0, eval_log, log_expand, 3, 2, 0, 0, aligned, _n_cus())
+    assert AP.plan(shape).w == (4 if aligned else 1) and AP.strides(shape) and not AP.strides(shape._replace(log=eval_log - 1))
+    assert AP.strides(shape._replace(entry="eval_program", program_len=8, n_regs=5))      # and the interpreter beside it
     trace_log = eval_log - log_expand
     n, k = 1 << eval_log, 0 if aligned else 1
-    assert n > _n_cus() * 16 * 256 * (4 if aligned else 1)
     words = (X.encode(X.LOAD, 0, 0, 0) + X.encode(X.LOAD, 1, 1, 1) + X.encode(X.LOAD, 2, 2, -1) + X.encode(X.MUL, 3, 0, 1)
              + X.encode(X.SUB, 3, 3, 2) + X.encode(X.SQR, 4, 2) + X.encode(X.ACC, 0, 3) + X.encode(X.ACC, 0, 4))
     rng = np.random.default_rng(eval_log)

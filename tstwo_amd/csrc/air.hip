@@ -22,8 +22,9 @@
 // Row r (bit-reversed order on CanonicCoset(trace_log + log_expand).circle_domain()):
 //   row_res = sum_i coeff_i c_i(r),   accum[r] += row_res * denom_inv[r >> trace_log]
 //
-// Both: one lane owns W = 4 consecutive rows (16-byte loads: a wave reads 1 KiB of one column at a time, coalesced) when every
-// column and accumulator is 16-byte aligned, else W = 1.  The four coordinates of row_res are sums of M31 x M31 products, kept in
+// Launch shapes (W, grid, LDS, what is uploaded where) and the range checks of the arguments: csrc/air_plan.h, for every entry.
+// Both: one lane owns W = 4 consecutive rows (16-byte loads: a wave reads 1 KiB of one column at a time, coalesced) or W = 1
+// (air_plan.h says when).  The four coordinates of row_res are sums of M31 x M31 products, kept in
 // 64 bits: a product of canonical values is < 2^62, so four of them and a folded remainder (< 2^33) fit; the sum is folded
 // (and/alignbit, no reduction to canonical) after every fourth constraint and reduced once per row at the end.  The denominators
 // travel in the kernel argument segment.
@@ -45,6 +46,7 @@
 
 #include "air_codegen.h"
 #include "air_native.h"
+#include "air_plan.h"
 #include "common.h"
 
 using namespace tstwo;
@@ -53,10 +55,8 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWave = 64;
-constexpr u32 kMaxConstraints = 128;         // 4 x 128 coefficient words in the kernel argument (N <= 130 wide-Fibonacci columns)
-constexpr u32 kMaxLogExpand = 4;
-constexpr u32 kMaxDenoms = 1u << kMaxLogExpand;
-constexpr u32 kMaxLog = 28;                  // word offsets of gload*/gstore* stay below 2^30
+constexpr u32 kMaxConstraints = kAirMaxConstraints;          // 4 x 128 coefficient words in the kernel argument (N <= 130 wide-Fibonacci columns)
+constexpr u32 kMaxDenoms = 1u << kAirMaxLogExpand;
 static_assert(TSTWO_AIR_PROGRAM_MAX_COLS <= 0x10000, "the column operand is 16 bits wide");
 
 struct AirArgs {
@@ -519,24 +519,24 @@ __global__ void __launch_bounds__(kWave) k_air_check(ColPtrs cols, CheckArgs a) 
 }
 
 // ---------------------------------------------------------------- host
-unsigned grid_for(size_t work) {
-    unsigned b = ceil_div(work, kThreads);
-    const unsigned cap = (unsigned)ctx().n_cus * 16;
-    if (b > cap) b = cap;
-    return b ? b : 1;
+// Every entry: the range checks of its arguments (air_refuse), its pointer checks, the plan (air_plan), the upload, one launch.
+int bad(const std::string &msg) { return set_error(TSTWO_ERR_BAD_ARG, msg); }
+
+AirInput input_of(AirEntry entry, u32 log, u32 log_expand, size_t n_cols, size_t n_terminal, size_t program_len) {
+    AirInput in = {};
+    in.entry = entry, in.log = log, in.log_expand = log_expand, in.n_cols = n_cols, in.n_terminal = n_terminal, in.program_len = program_len;
+    in.n_cus = (u32)ctx().n_cus;
+    return in;
 }
+int refused(const AirInput &in, const char *why) { return bad(std::string(air_prefix(in.entry)) + why); }
+
+// The plan's `aligned`: every column and accumulator (for tstwo_air_eval_columns: its n_out output columns) is 16-byte aligned.
 bool table_aligned16(const u32 *const *t, size_t n) {
     for (size_t i = 0; i < n; i++) if (!aligned16(t[i])) return false;
     return true;
 }
-
-int bad(const std::string &msg) { return set_error(TSTWO_ERR_BAD_ARG, msg); }
-
-// the limits of the evaluation domain; `prefix` starts each error text
-int check_domain(const char *prefix, u32 trace_log_size, u32 log_expand) {
-    if (log_expand > kMaxLogExpand) return bad(std::string(prefix) + "log_expand too large");
-    if (trace_log_size + log_expand > kMaxLog) return bad(std::string(prefix) + "evaluation domain too large");
-    return TSTWO_OK;
+bool all_aligned16(const u32 *const *cols, size_t n_cols, u32 *const *accum, size_t n_accum) {
+    return table_aligned16(cols, n_cols) && table_aligned16((const u32 *const *)accum, n_accum);
 }
 
 // range-checks the coefficient words (copied to coeff_dst) and the 2^log_expand denominators (copied into the kernel argument)
@@ -554,28 +554,8 @@ int take_coeffs_and_denoms(const u32 *coeffs, size_t n_constraints, u32 *coeff_d
     return TSTWO_OK;
 }
 
-// W = 4 rows per lane when the rows split into fours and every column and accumulator is 16-byte aligned
-// (for tstwo_air_eval_columns: its n_out output columns)
-bool four_rows_per_lane(u32 n_rows, const u32 *const *cols, size_t n_cols, u32 *const *accum, size_t n_accum) {
-    return n_rows % 4 == 0 && table_aligned16(cols, n_cols) && table_aligned16((const u32 *const *)accum, n_accum);
-}
-
-// The launch shape of both interpreter kernels: one-wave workgroups, n_regs KiB of LDS at W = 4, at most n_cus * 32 workgroups
-// (the kernels stride over the rest).
-size_t interpreter_lds(u32 n_regs, bool vec) { return (size_t)(n_regs ? n_regs : 1) * kWave * (vec ? 4 : 1) * sizeof(u32); }
-unsigned interpreter_grid(u32 n_rows, bool vec) {
-    unsigned grid = ceil_div((size_t)n_rows / (vec ? 4 : 1), kWave);
-    const unsigned cap = (unsigned)ctx().n_cus * 32;
-    return grid > cap ? cap : grid;
-}
-
-// What tstwo_air_eval_program and tstwo_air_eval_compiled ask of everything but the program itself.
-int check_eval_args(const u32 *const *cols, size_t n_cols, u32 trace_log_size, u32 log_expand, const u32 *coeffs, size_t n_constraints,
-                    const u32 *denom_inv, u32 *const accum[4]) {
-    if (log_expand < 1) return bad("air program: log_expand must be at least 1 (the neighbour index needs eval > trace)");
-    if (int rc = check_domain("air program: ", trace_log_size, log_expand)) return rc;
-    if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return bad("air program: number of columns out of range");
-    if (n_constraints == 0 || n_constraints > TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS) return bad("air program: number of constraints out of range");
+// The pointers of tstwo_air_eval_program and tstwo_air_eval_compiled, and their refusal during capture.
+int check_eval_pointers(const u32 *const *cols, size_t n_cols, const u32 *coeffs, const u32 *denom_inv, u32 *const accum[4]) {
     if (!coeffs || !denom_inv) return bad("null host argument");
     TSTWO_REQUIRE_TABLE(cols, n_cols);
     TSTWO_REQUIRE_TABLE(accum, 4);
@@ -584,14 +564,7 @@ int check_eval_args(const u32 *const *cols, size_t n_cols, u32 trace_log_size, u
     return TSTWO_OK;
 }
 
-// What tstwo_air_eval_columns and tstwo_air_eval_columns_compiled ask of everything but the program itself: the log range and
-// the counts, then the two tables.
-int check_columns_shape(size_t n_cols, u32 log_size, size_t n_out) {
-    if (log_size < 1 || log_size > kMaxLog) return bad("air columns: log_size out of range");
-    if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return bad("air columns: number of columns out of range");
-    if (n_out == 0 || n_out > TSTWO_AIR_COLUMNS_MAX_OUT) return bad("air columns: number of outputs out of range");
-    return TSTWO_OK;
-}
+// The two tables of tstwo_air_eval_columns and tstwo_air_eval_columns_compiled.
 int check_columns_tables(const u32 *const *cols, size_t n_cols, u32 *const *out, size_t n_out) {
     TSTWO_REQUIRE_TABLE(cols, n_cols);
     TSTWO_REQUIRE_TABLE(out, n_out);
@@ -605,13 +578,23 @@ int check_columns_tables(const u32 *const *cols, size_t n_cols, u32 *const *out,
     return TSTWO_OK;
 }
 
-template <int KIND>
-int launch_quotients(const ColPtrs &cp, const AirArgs &a, bool vec) {
-    if (vec) hipLaunchKernelGGL((k_constraint_quotients<KIND, 4>), dim3(grid_for(a.n_rows / 4)), dim3(kThreads), 0, ctx().stream, cp, a);
-    else hipLaunchKernelGGL((k_constraint_quotients<KIND, 1>), dim3(grid_for(a.n_rows)), dim3(kThreads), 0, ctx().stream, cp, a);
+// The plan's upload (at most one slot of the ring: no host synchronisation) into the scratch block.
+static_assert(kAirMaxUploadWords * sizeof(u32) <= kUpSlotBytes, "an upload exceeds one ring slot");
+int upload(const AirPlan &p, const u32 *words) {
+    if (int rc = ensure_scratch(p.upload_words * sizeof(u32))) return rc;
+    return small_h2d(ctx().scratch, words, p.upload_words * sizeof(u32));
+}
+
+// One launch as the plan says: the W = 4 or the W = 1 instance of a kernel.
+template <class F, class... A>
+int launch(const AirPlan &p, F *k4, F *k1, const A &...args) {
+    F *const k = p.w == 4 ? k4 : k1;
+    hipLaunchKernelGGL(k, dim3(p.grid), dim3(p.threads), p.lds_bytes, ctx().stream, args...);
     TSTWO_LAUNCH_CHECK();
     return TSTWO_OK;
 }
+static_assert(kThreads == (int)kAirWideThreads && kWave == (int)kAirWaveThreads, "the kernels count lanes as the plan does");
+static_assert(kAirTableByValue == (size_t)kMaxColsPerLaunch, "the plan's by-value limit is fill_col_table's");
 
 }  // namespace
 
@@ -619,32 +602,22 @@ extern "C" {
 
 int tstwo_air_wide_fib_trace(const u32 *a, const u32 *b, u32 log_n, u32 *const *cols, size_t n_cols) {
     TSTWO_REQUIRE_READY();
-    if (n_cols < 2) return set_error(TSTWO_ERR_BAD_ARG, "wide Fibonacci needs at least 2 columns");
-    if (log_n > kMaxLog) return set_error(TSTWO_ERR_BAD_ARG, "trace too large");
+    AirInput in = input_of(kAirWideFibTrace, log_n, 0, n_cols, 0, 0);
+    if (const char *why = air_refuse(in)) return refused(in, why);
     TSTWO_REQUIRE_PTRS(a, b);
     TSTWO_REQUIRE_TABLE(cols, n_cols);
-    const u32 n = 1u << log_n;
     ColPtrs cp;
     if (int rc = fill_col_table(cp, (const u32 *const *)cols, n_cols, 0)) return rc;
-    const bool vec = n % 4 == 0 && aligned16(a) && aligned16(b) && table_aligned16((const u32 *const *)cols, n_cols);
-    if (vec) hipLaunchKernelGGL(k_wide_fib_trace<4>, dim3(grid_for(n / 4)), dim3(kThreads), 0, ctx().stream, cp, a, b, n, (u32)n_cols);
-    else hipLaunchKernelGGL(k_wide_fib_trace<1>, dim3(grid_for(n)), dim3(kThreads), 0, ctx().stream, cp, a, b, n, (u32)n_cols);
-    TSTWO_LAUNCH_CHECK();
-    return TSTWO_OK;
+    in.aligned = aligned16(a) && aligned16(b) && table_aligned16((const u32 *const *)cols, n_cols);
+    return launch(air_plan(in), k_wide_fib_trace<4>, k_wide_fib_trace<1>, cp, a, b, 1u << log_n, (u32)n_cols);
 }
 
 int tstwo_air_constraint_quotients(u32 kind, const u32 *const *cols, size_t n_cols, u32 trace_log_size, u32 log_expand,
                                    const u32 *coeffs, size_t n_constraints, const u32 *denom_inv, u32 *const accum[4]) {
     TSTWO_REQUIRE_READY();
-    if (kind == TSTWO_AIR_WIDE_FIB) {
-        if (n_cols < 3 || n_constraints != n_cols - 2) return bad("wide Fibonacci: N >= 3 columns, N - 2 constraints");
-    } else if (kind == TSTWO_AIR_MUL_ADD) {
-        if (n_cols != 3 || n_constraints != 1) return bad("mul-add: 3 columns, 1 constraint");
-    } else {
-        return bad("unknown constraint kind");
-    }
-    if (n_constraints > kMaxConstraints) return bad("too many constraints in one component");
-    if (int rc = check_domain("", trace_log_size, log_expand)) return rc;
+    AirInput in = input_of(kAirQuotients, trace_log_size + log_expand, log_expand, n_cols, n_constraints, 0);
+    in.kind = kind;
+    if (const char *why = air_refuse(in)) return refused(in, why);
     if (!coeffs || !denom_inv) return bad("null host argument");
     TSTWO_REQUIRE_TABLE(cols, n_cols);
     TSTWO_REQUIRE_TABLE(accum, 4);
@@ -654,46 +627,40 @@ int tstwo_air_constraint_quotients(u32 kind, const u32 *const *cols, size_t n_co
     a.n_cols = (u32)n_cols;
     a.n_constraints = (u32)n_constraints;
     a.trace_log = trace_log_size;
-    a.n_rows = 1u << (trace_log_size + log_expand);
+    a.n_rows = 1u << in.log;
     ColPtrs cp;
     if (int rc = fill_col_table(cp, cols, n_cols, 0)) return rc;
-    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, accum, 4);
-    return kind == TSTWO_AIR_WIDE_FIB ? launch_quotients<TSTWO_AIR_WIDE_FIB>(cp, a, vec) : launch_quotients<TSTWO_AIR_MUL_ADD>(cp, a, vec);
+    in.aligned = all_aligned16(cols, n_cols, accum, 4);
+    const AirPlan p = air_plan(in);
+    return kind == TSTWO_AIR_WIDE_FIB ? launch(p, k_constraint_quotients<TSTWO_AIR_WIDE_FIB, 4>, k_constraint_quotients<TSTWO_AIR_WIDE_FIB, 1>, cp, a)
+                                      : launch(p, k_constraint_quotients<TSTWO_AIR_MUL_ADD, 4>, k_constraint_quotients<TSTWO_AIR_MUL_ADD, 1>, cp, a);
 }
 
 int tstwo_air_eval_program(const u32 *const *cols, size_t n_cols, u32 trace_log_size, u32 log_expand, const u32 *program,
                            size_t program_len, const u32 *coeffs, size_t n_constraints, const u32 *denom_inv, u32 *const accum[4]) {
     TSTWO_REQUIRE_READY();
-    if (program_len == 0 || program_len > TSTWO_AIR_PROGRAM_MAX_INSTR) return bad("air program: program length out of range");
+    AirInput in = input_of(kAirEvalProgram, trace_log_size + log_expand, log_expand, n_cols, n_constraints, program_len);
+    if (const char *why = air_refuse(in)) return refused(in, why);
     if (!program) return bad("null host argument");
-    if (int rc = check_eval_args(cols, n_cols, trace_log_size, log_expand, coeffs, n_constraints, denom_inv, accum)) return rc;
-    u32 n_regs = 0;
-    if (const char *why = check_acc_program(program, program_len, n_cols, n_constraints, n_regs)) return bad(std::string("air program: ") + why);
-    // upload: program words, then coefficient words (at most 16 KiB: one slot of the ring, no host synchronisation)
-    static_assert((2 * TSTWO_AIR_PROGRAM_MAX_INSTR + 4 * TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS) * 4 <= kUpSlotBytes, "program upload exceeds one ring slot");
-    u32 staged[2 * TSTWO_AIR_PROGRAM_MAX_INSTR + 4 * TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS];
-    const size_t prog_words = 2 * program_len, words = prog_words + 4 * n_constraints;
+    if (int rc = check_eval_pointers(cols, n_cols, coeffs, denom_inv, accum)) return rc;
+    if (const char *why = check_acc_program(program, program_len, n_cols, n_constraints, in.n_regs)) return refused(in, why);
+    in.aligned = all_aligned16(cols, n_cols, accum, 4);
+    const AirPlan p = air_plan(in);
+    u32 staged[kAirMaxUploadWords];             // program words, then coefficient words
     ProgArgs a = {};
-    if (int rc = take_coeffs_and_denoms(coeffs, n_constraints, staged + prog_words, denom_inv, log_expand, a)) return rc;
-    std::copy(program, program + prog_words, staged);
-    if (int rc = ensure_scratch(words * sizeof(u32))) return rc;
-    if (int rc = small_h2d(ctx().scratch, staged, words * sizeof(u32))) return rc;
+    if (int rc = take_coeffs_and_denoms(coeffs, n_constraints, staged + p.coeff_word, denom_inv, log_expand, a)) return rc;
+    std::copy(program, program + 2 * program_len, staged);
+    if (int rc = upload(p, staged)) return rc;
     ColPtrs cp;
     if (int rc = fill_col_table(cp, cols, n_cols, 0)) return rc;
     for (int j = 0; j < 4; j++) a.acc.p[j] = accum[j];
     a.prog = ctx().scratch;
     a.n_instr = (u32)program_len;
     a.trace_log = trace_log_size;
-    a.eval_log = trace_log_size + log_expand;
+    a.eval_log = in.log;
     a.log_expand = log_expand;
-    a.n_rows = 1u << a.eval_log;
-    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, accum, 4);
-    const size_t lds = interpreter_lds(n_regs, vec);
-    const unsigned grid = interpreter_grid(a.n_rows, vec);
-    if (vec) hipLaunchKernelGGL(k_air_program<4>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, a);
-    else hipLaunchKernelGGL(k_air_program<1>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, a);
-    TSTWO_LAUNCH_CHECK();
-    return TSTWO_OK;
+    a.n_rows = 1u << in.log;
+    return launch(p, k_air_program<4>, k_air_program<1>, cp, a);
 }
 
 int tstwo_air_eval_compiled(uint64_t kernel_id, const u32 *const *cols, size_t n_cols, u32 trace_log_size, u32 log_expand,
@@ -703,45 +670,41 @@ int tstwo_air_eval_compiled(uint64_t kernel_id, const u32 *const *cols, size_t n
     u32 for_cols = 0, for_constraints = 0;
     if (int rc = air_native_shape(kernel_id, kind, for_cols, for_constraints)) return rc;
     if (kind != kAirKernelConstraints) return bad("air program: the kernel was compiled from a columns program");
-    if (int rc = check_eval_args(cols, n_cols, trace_log_size, log_expand, coeffs, n_constraints, denom_inv, accum)) return rc;
+    AirInput in = input_of(kAirEvalCompiled, trace_log_size + log_expand, log_expand, n_cols, n_constraints, 0);
+    if (const char *why = air_refuse(in)) return refused(in, why);
+    if (int rc = check_eval_pointers(cols, n_cols, coeffs, denom_inv, accum)) return rc;
     if (n_cols != for_cols) return bad("air kernel: compiled for another number of columns");
     if (n_constraints != for_constraints) return bad("air kernel: compiled for another number of constraints");
-    // upload: the coefficient words (at most 4 KiB: one slot of the ring, no host synchronisation)
-    u32 staged[4 * TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS];
+    in.aligned = all_aligned16(cols, n_cols, accum, 4);
+    const AirPlan p = air_plan(in);
+    u32 staged[4 * TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS];      // the coefficient words
     NativeArgs a = {};
-    if (int rc = take_coeffs_and_denoms(coeffs, n_constraints, staged, denom_inv, log_expand, a)) return rc;
-    if (int rc = ensure_scratch(4 * n_constraints * sizeof(u32))) return rc;
-    if (int rc = small_h2d(ctx().scratch, staged, 4 * n_constraints * sizeof(u32))) return rc;
+    if (int rc = take_coeffs_and_denoms(coeffs, n_constraints, staged + p.coeff_word, denom_inv, log_expand, a)) return rc;
+    if (int rc = upload(p, staged)) return rc;
     ColPtrs cp;
     if (int rc = fill_col_table(cp, cols, n_cols, 0)) return rc;
     for (int j = 0; j < 4; j++) a.acc.p[j] = accum[j];
     a.coeff = ctx().scratch;
     a.trace_log = trace_log_size;
-    a.eval_log = trace_log_size + log_expand;
+    a.eval_log = in.log;
     a.log_expand = log_expand;
-    a.n_rows = 1u << a.eval_log;
-    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, accum, 4);
-    static_assert(kAirNativeThreads == kThreads, "grid_for counts workgroups of kThreads lanes");
-    const unsigned grid = grid_for(a.n_rows / (vec ? 4 : 1));
-    a.stride = grid * kThreads;
-    return air_native_launch(kernel_id, vec, grid, cp, a);
+    a.n_rows = 1u << in.log;
+    return air_native_launch(kernel_id, p, cp, a);
 }
 
 int tstwo_air_eval_columns(const u32 *const *cols, size_t n_cols, u32 log_size, const u32 *program, size_t program_len,
                            u32 *const *out, size_t n_out) {
     TSTWO_REQUIRE_READY();
-    if (int rc = check_columns_shape(n_cols, log_size, n_out)) return rc;
-    if (program_len == 0 || program_len > TSTWO_AIR_PROGRAM_MAX_INSTR) return bad("air columns: program length out of range");
+    AirInput in = input_of(kAirEvalColumns, log_size, 0, n_cols, n_out, program_len);
+    if (const char *why = air_refuse(in)) return refused(in, why);
     if (!program) return bad("null host argument");
     if (int rc = check_columns_tables(cols, n_cols, out, n_out)) return rc;
     // the program words travel through the small-upload ring, which a captured graph cannot replay
     if (stream_is_capturing()) return bad("host-array upload during graph capture (the air columns program cannot be recorded)");
-    u32 n_regs = 0;
-    if (const char *why = check_store_program(program, program_len, n_cols, n_out, n_regs)) return bad(std::string("air columns: ") + why);
-    const size_t bytes = 2 * program_len * sizeof(u32);
-    static_assert(2 * TSTWO_AIR_PROGRAM_MAX_INSTR * 4 <= kUpSlotBytes, "program upload exceeds one ring slot");
-    if (int rc = ensure_scratch(bytes)) return rc;
-    if (int rc = small_h2d(ctx().scratch, program, bytes)) return rc;
+    if (const char *why = check_store_program(program, program_len, n_cols, n_out, in.n_regs)) return refused(in, why);
+    in.aligned = all_aligned16(cols, n_cols, out, n_out);
+    const AirPlan p = air_plan(in);
+    if (int rc = upload(p, program)) return rc;
     ColPtrs cp, op;
     if (int rc = fill_col_table(cp, cols, n_cols, 0)) return rc;
     if (int rc = fill_col_table(op, (const u32 *const *)out, n_out, 1)) return rc;      // at most 64: by value
@@ -750,13 +713,7 @@ int tstwo_air_eval_columns(const u32 *const *cols, size_t n_cols, u32 log_size, 
     a.n_instr = (u32)program_len;
     a.log = log_size;
     a.n_rows = 1u << log_size;
-    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, out, n_out);
-    const size_t lds = interpreter_lds(n_regs, vec);
-    const unsigned grid = interpreter_grid(a.n_rows, vec);
-    if (vec) hipLaunchKernelGGL(k_air_columns<4>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, op, a);
-    else hipLaunchKernelGGL(k_air_columns<1>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, op, a);
-    TSTWO_LAUNCH_CHECK();
-    return TSTWO_OK;
+    return launch(p, k_air_columns<4>, k_air_columns<1>, cp, op, a);
 }
 
 int tstwo_air_eval_columns_compiled(uint64_t kernel_id, const u32 *const *cols, size_t n_cols, u32 log_size, u32 *const *out, size_t n_out) {
@@ -765,7 +722,8 @@ int tstwo_air_eval_columns_compiled(uint64_t kernel_id, const u32 *const *cols, 
     u32 for_cols = 0, for_out = 0;
     if (int rc = air_native_shape(kernel_id, kind, for_cols, for_out)) return rc;
     if (kind != kAirKernelColumns) return bad("air columns: the kernel was compiled from a constraint program");
-    if (int rc = check_columns_shape(n_cols, log_size, n_out)) return rc;
+    AirInput in = input_of(kAirEvalColumnsCompiled, log_size, 0, n_cols, n_out, 0);
+    if (const char *why = air_refuse(in)) return refused(in, why);
     if (int rc = check_columns_tables(cols, n_cols, out, n_out)) return rc;
     if (n_cols != for_cols) return bad("air kernel: compiled for another number of columns");
     if (n_out != for_out) return bad("air kernel: compiled for another number of outputs");
@@ -776,42 +734,26 @@ int tstwo_air_eval_columns_compiled(uint64_t kernel_id, const u32 *const *cols, 
     ColumnsArgs a = {};
     a.log = log_size;
     a.n_rows = 1u << log_size;
-    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, out, n_out);
-    const unsigned grid = grid_for(a.n_rows / (vec ? 4 : 1));
-    a.stride = grid * kThreads;
-    return air_native_launch_columns(kernel_id, vec, grid, cp, op, a);
+    in.aligned = all_aligned16(cols, n_cols, out, n_out);
+    return air_native_launch_columns(kernel_id, air_plan(in), cp, op, a);
 }
 
 int tstwo_air_check_constraints(const u32 *const *cols, size_t n_cols, u32 log_size, const u32 *program, size_t program_len,
                                 size_t n_constraints, u32 *report) {
     TSTWO_REQUIRE_READY();
-    if (log_size < 1 || log_size > kMaxLog) return bad("air check: log_size out of range");
-    if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return bad("air check: number of columns out of range");
-    if (n_constraints == 0 || n_constraints > TSTWO_AIR_PROGRAM_MAX_CONSTRAINTS) return bad("air check: number of constraints out of range");
-    if (program_len == 0 || program_len > TSTWO_AIR_PROGRAM_MAX_INSTR) return bad("air check: program length out of range");
+    AirInput in = input_of(kAirCheck, log_size, 0, n_cols, n_constraints, program_len);
+    if (const char *why = air_refuse(in)) return refused(in, why);
     if (!program) return bad("null host argument");
     TSTWO_REQUIRE_TABLE(cols, n_cols);
     if (!report || !aligned16(report)) return bad("air check: null or misaligned report");
     // the program words travel through the small-upload ring, which a captured graph cannot replay
     if (stream_is_capturing()) return bad("host-array upload during graph capture (the air check program cannot be recorded)");
-    u32 n_regs = 0;
-    if (const char *why = check_assert_program(program, program_len, n_cols, n_constraints, n_regs)) return bad(std::string("air check: ") + why);
-    // the uploaded copy marks the last ACC of every constraint in dst (ignored by every other entry): the kernel votes there
-    static_assert(2 * TSTWO_AIR_PROGRAM_MAX_INSTR * 4 <= kUpSlotBytes, "program upload exceeds one ring slot");
-    u32 staged[2 * TSTWO_AIR_PROGRAM_MAX_INSTR];
-    std::copy(program, program + 2 * program_len, staged);
-    u32 *last_acc = nullptr;
-    for (size_t pc = 0; pc < program_len; pc++) {
-        u32 *w = staged + 2 * pc;
-        if ((w[0] & 0xffu) != TSTWO_AIR_OP_ACC) continue;
-        w[0] &= ~0xff00u;
-        if (last_acc && last_acc[1] != w[1]) last_acc[0] |= 1u << 8;
-        last_acc = w;
-    }
-    last_acc[0] |= 1u << 8;                     // check_assert_program saw at least one ACC
-    const size_t bytes = 2 * program_len * sizeof(u32);
-    if (int rc = ensure_scratch(bytes)) return rc;
-    if (int rc = small_h2d(ctx().scratch, staged, bytes)) return rc;
+    if (const char *why = check_assert_program(program, program_len, n_cols, n_constraints, in.n_regs)) return refused(in, why);
+    in.aligned = table_aligned16(cols, n_cols);
+    const AirPlan p = air_plan(in);
+    u32 staged[2 * TSTWO_AIR_PROGRAM_MAX_INSTR];            // the program with the last ACC of every constraint marked: the kernel votes there
+    mark_last_acc(program, program_len, staged);
+    if (int rc = upload(p, staged)) return rc;
     ColPtrs cp;
     if (int rc = fill_col_table(cp, cols, n_cols, 0)) return rc;
     CheckArgs a = {};
@@ -821,18 +763,11 @@ int tstwo_air_check_constraints(const u32 *const *cols, size_t n_cols, u32 log_s
     a.log = log_size;
     a.n_rows = 1u << log_size;
     a.n_constraints = (u32)n_constraints;
-    const bool vec = four_rows_per_lane(a.n_rows, cols, n_cols, nullptr, 0);
-    const size_t regs_bytes = interpreter_lds(n_regs, vec);
-    a.tally = (u32)(regs_bytes / sizeof(u32));
-    const size_t lds = regs_bytes + 2 * n_constraints * sizeof(u32);
-    const unsigned grid = interpreter_grid(a.n_rows, vec);
+    a.tally = p.tally_word;
     // the report in a launch of its own: the kernel's workgroups add to it in any order, and the grid may wrap
     hipLaunchKernelGGL(k_air_check_init, dim3(1), dim3(kThreads), 0, ctx().stream, report, a.n_constraints);
     TSTWO_LAUNCH_CHECK();
-    if (vec) hipLaunchKernelGGL(k_air_check<4>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, a);
-    else hipLaunchKernelGGL(k_air_check<1>, dim3(grid), dim3(kWave), lds, ctx().stream, cp, a);
-    TSTWO_LAUNCH_CHECK();
-    return TSTWO_OK;
+    return launch(p, k_air_check<4>, k_air_check<1>, cp, a);
 }
 
 }  // extern "C"

@@ -104,6 +104,21 @@ inline const char *check_assert_program(const uint32_t *program, size_t program_
     return nullptr;
 }
 
+// The copy of a program check_assert_program accepted that tstwo_air_check_constraints uploads: dst (ignored by every other entry)
+// is cleared in every ACC and set to 1 in the last ACC of every constraint index, where k_air_check votes.
+inline void mark_last_acc(const uint32_t *program, size_t program_len, uint32_t *marked) {
+    uint32_t *last_acc = nullptr;
+    for (size_t pc = 0; pc < program_len; pc++) {
+        uint32_t *w = marked + 2 * pc;
+        w[0] = program[2 * pc], w[1] = program[2 * pc + 1];
+        if ((w[0] & 0xffu) != TSTWO_AIR_OP_ACC) continue;
+        w[0] &= ~0xff00u;
+        if (last_acc && last_acc[1] != w[1]) last_acc[0] |= 1u << 8;
+        last_acc = w;
+    }
+    if (last_acc) last_acc[0] |= 1u << 8;       // check_assert_program saw at least one ACC
+}
+
 // What tstwo_air_eval_columns and tstwo_air_columns_compile accept: the limits, every instruction, every output stored once.
 inline const char *check_store_program(const uint32_t *program, size_t program_len, size_t n_cols, size_t n_out, uint32_t &n_regs) {
     if (n_cols == 0 || n_cols > TSTWO_AIR_PROGRAM_MAX_COLS) return "number of columns out of range";

@@ -2,6 +2,8 @@
 #pragma once
 #include <cstddef>
 
+#include "air_codegen.h"
+#include "air_plan.h"
 #include "common.h"
 
 namespace tstwo {
@@ -28,11 +30,12 @@ enum AirKernelKind : u32 { kAirKernelConstraints = 0, kAirKernelColumns = 1 };
 // What kernel `id` was compiled for (n_terminal: its constraints, or its outputs); TSTWO_ERR_BAD_ARG "unknown air kernel" for an
 // id that is not in the table.
 __attribute__((visibility("hidden"))) int air_native_shape(uint64_t id, AirKernelKind &kind, u32 &n_cols, u32 &n_terminal);
-// Launches kernel `id` (W = 4 rows per lane when vec, else W = 1) with `grid` workgroups of kAirNativeThreads lanes on the
-// library's stream.
-__attribute__((visibility("hidden"))) int air_native_launch(uint64_t id, bool vec, unsigned grid, ColPtrs &cols, NativeArgs &args);
+// Launches kernel `id` on the library's stream as the plan says: its W = 4 or its W = 1 kernel, plan.grid workgroups of
+// kAirNativeThreads lanes, plan.stride into args.stride.
+static_assert(kAirNativeThreads == (int)kAirWideThreads, "the plan counts the compiled kernels' workgroups at kAirNativeThreads lanes");
+__attribute__((visibility("hidden"))) int air_native_launch(uint64_t id, const AirPlan &plan, ColPtrs &cols, NativeArgs &args);
 
 // The same for a columns kernel: (cols, out, args).
-__attribute__((visibility("hidden"))) int air_native_launch_columns(uint64_t id, bool vec, unsigned grid, ColPtrs &cols, ColPtrs &out, ColumnsArgs &args);
+__attribute__((visibility("hidden"))) int air_native_launch_columns(uint64_t id, const AirPlan &plan, ColPtrs &cols, ColPtrs &out, ColumnsArgs &args);
 
 }  // namespace tstwo

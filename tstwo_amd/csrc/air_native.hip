@@ -162,19 +162,21 @@ int air_native_shape(uint64_t id, AirKernelKind &kind, u32 &n_cols, u32 &n_termi
     return TSTWO_OK;
 }
 
-int air_native_launch(uint64_t id, bool vec, unsigned grid, ColPtrs &cols, NativeArgs &args) {
+int air_native_launch(uint64_t id, const AirPlan &plan, ColPtrs &cols, NativeArgs &args) {
     const Kernel *k = find(id);
     if (!k || k->kind != kAirKernelConstraints) return bad("unknown air kernel");
+    args.stride = plan.stride;
     void *params[] = {&cols, &args};
-    TSTWO_HIP(hipModuleLaunchKernel(k->fn[vec ? 0 : 1], grid, 1, 1, kAirNativeThreads, 1, 1, 0, ctx().stream, params, nullptr));
+    TSTWO_HIP(hipModuleLaunchKernel(k->fn[plan.w == 4 ? 0 : 1], plan.grid, 1, 1, plan.threads, 1, 1, 0, ctx().stream, params, nullptr));
     return TSTWO_OK;
 }
 
-int air_native_launch_columns(uint64_t id, bool vec, unsigned grid, ColPtrs &cols, ColPtrs &out, ColumnsArgs &args) {
+int air_native_launch_columns(uint64_t id, const AirPlan &plan, ColPtrs &cols, ColPtrs &out, ColumnsArgs &args) {
     const Kernel *k = find(id);
     if (!k || k->kind != kAirKernelColumns) return bad("unknown air kernel");
+    args.stride = plan.stride;
     void *params[] = {&cols, &out, &args};
-    TSTWO_HIP(hipModuleLaunchKernel(k->fn[vec ? 0 : 1], grid, 1, 1, kAirNativeThreads, 1, 1, 0, ctx().stream, params, nullptr));
+    TSTWO_HIP(hipModuleLaunchKernel(k->fn[plan.w == 4 ? 0 : 1], plan.grid, 1, 1, plan.threads, 1, 1, 0, ctx().stream, params, nullptr));
     return TSTWO_OK;
 }
 
