@@ -17,7 +17,8 @@ M31_P = 2**31 - 1
 R = 2**256
 N_MSGS = [1, 2, 7, 8, 9, 63, 64, 65, 513]
 MODEL_MAX_MSGS = 65                      # x at most 3 permutations: well inside what the model does in a second
-# the operands of tests/test_cpu_felt_coop.py that reach the accumulators' bounds
+# limb patterns of tests/test_cpu_felt_coop.py.  As message elements they are only the b operand of to_mont(x) = mul(R^2, x); from the
+# first round constant on every operand is pseudo-random (tests/test_gpu_poseidon_steer.py steers the operands of round 0)
 EDGE = [0, 1, 2, M.P - 1, M.P - 2, 2**251 - 1, 2**251, 2**192 * 17, 2**192 * 17 + 1, R % M.P, R * R % M.P, 2**32 - 1, 2**32, 2**224,
         2**251 + 17 * 2**192, 2**251 + 2**192 - 1, 2**224 - 1, (2**27 - 1) << 224 | (2**224 - 1), 0xFFFFFFFF << 192, 0xFFFFFFFF00000000FFFFFFFF]
 
