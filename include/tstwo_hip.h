@@ -805,6 +805,30 @@ int tstwo_logup_column(const tstwo_logup_frac *fracs, size_t n_fracs, const uint
  * the 4 words of claimed.  1 <= log_size <= 28.  Synchronous; refused during graph capture. */
 int tstwo_logup_finalize_last(uint32_t *const col[4], uint32_t log_size, uint32_t claimed_sum[4]);
 
+/* ---------------------------------------------------------------- mle_eval component (GKR input claims inside the STARK)
+ * The device steps of the AIR component that proves sum_p eq(p, r) L[p] = v for a linear form L over committed columns
+ * (tstwo_amd/mle_eval.py; the reference has no such component, Rust stwo has one as an example).  Its interaction
+ * trace is E = tstwo_gkr_gen_eq_evals(r, 1), then tstwo_mle_eval_terms, then tstwo_logup_finalize_last.
+ * The preprocessed selector columns of log size n = log_size, 2n + 2 columns of 2^n words with values 0 / 1 that depend on n only.
+ * With d = the bit reversal of the storage position p over n bits, h = 2^(n-1), d' = d mod h and t(p) = the number of trailing
+ * one bits of d' (n - 1 when d' = h - 1):
+ *   out[t]      = G_t[p] = [d <  h and t(p) = t]   t < n
+ *   out[n + t]  = K_t[p] = [d >= h and t(p) = t]   t < n
+ *   out[2n]     = F0[p]  = [d = 0]
+ *   out[2n + 1] = F1[p]  = [d = h]
+ * out: a host array of 2n + 2 device columns; every word of every column is written exactly once.  2 <= log_size <= 28
+ * ("mle eval selectors: log_size must be 2 to 28"), no null pointer, no two columns overlapping.  Asynchronous. */
+int tstwo_mle_eval_selectors(uint32_t log_size, uint32_t *const *out);
+/* out[p] = eq[p] * (constant + sum_k coeffs[4k .. 4k+4) * cols[k][p]) for p < 2^log_size: a secure column times a linear form
+ * with QM31 coefficients and constant over M31 columns (the form of a tstwo_logup_frac denominator).  Descriptor rules and
+ * limits as there (TSTWO_ERR_BAD_ARG, text "mle eval terms: ..."): 1 <= n_terms <= TSTWO_LOGUP_MAX_TERMS ("1 to 16 terms"),
+ * log_size <= 28, every host word < 2^31 - 1 ("... out of range"), no null pointer, an output column that overlaps a column of
+ * the form is refused ("an output column is also an input").  out may be eq itself, column for column (out[j] == eq[j]); any
+ * other overlap of out with eq is refused ("out may alias eq only column for column").  Nothing is inverted: the zero flag is
+ * not touched.  Everything travels as kernel arguments: the call may be captured into a graph.  Asynchronous. */
+int tstwo_mle_eval_terms(const uint32_t *const eq[4], const uint32_t *const *cols, const uint32_t *coeffs, size_t n_terms,
+                         const uint32_t constant[4], uint32_t log_size, uint32_t *const out[4]);
+
 /* ---------------------------------------------------------------- Lookup multiplicities
  * The multiplicity column of a lookup table, counted on the device: a histogram of M31 columns into a column of 2^log_range
  * words (tstwo_amd/logup.py lookup_multiplicities; the host version is constraint_framework.range_check_multiplicities). */

@@ -146,6 +146,8 @@ const lib = dlopen(process.env.TSTWO_HIP_LIB ?? "libtstwo_hip.so", {
   tstwo_air_check_constraints: { args: [P, u64, u32, P, u64, u64, u64], returns: i32 },
   tstwo_logup_column: { args: [P, u64, P, u32, P], returns: i32 },
   tstwo_logup_finalize_last: { args: [P, u32, P], returns: i32 },
+  tstwo_mle_eval_selectors: { args: [u32, P], returns: i32 },
+  tstwo_mle_eval_terms: { args: [P, P, P, u64, P, u32, P], returns: i32 },
   tstwo_lookup_multiplicities: { args: [P, P, u64, u32, u32, u64, u64], returns: i32 },
   tstwo_lookup_multiplicities_keyed: { args: [P, u64, u32, u32, u64, u64], returns: i32 },
   tstwo_coset_iota: { args: [u64, u32], returns: i32 },

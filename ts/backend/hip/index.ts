@@ -181,6 +181,21 @@ export class HipBackend implements Backend {
       Math.log2(cols[0]!.len()), ptr(out.ptrs())));
     return out;
   }
+  /** The 2 logSize + 2 preprocessed 0/1 columns of the mle_eval component (G_t, K_t, F0, F1: include/tstwo_hip.h).  Asynchronous. */
+  mleEvalSelectors(logSize: number): HipColumn[] {
+    const out = Array.from({ length: 2 * logSize + 2 }, () => HipColumn.uninitialized(1 << logSize));
+    check(hip.tstwo_mle_eval_selectors(logSize, ptr(ptrs(out.map((c) => c.dev)))));
+    return out;
+  }
+  /** out[p] = eq[p] * (constant + sum_k coeffs[k] * cols[k][p]): the summand of a claim on a GKR input layer (the mle_eval
+   *  component's interaction trace: genEqEvals, this, then the coset-order prefix sum).  out defaults to eq (in place).  Asynchronous. */
+  mleEvalTerms(eq: HipSecureColumn, cols: readonly HipColumn[], coeffs: readonly QM31[], constant: QM31, out: HipSecureColumn = eq): HipSecureColumn {
+    const words = new Uint32Array(4 * coeffs.length);
+    coeffs.forEach((c, t) => words.set(q4(c), 4 * t));
+    check(hip.tstwo_mle_eval_terms(ptr(eq.ptrs()), ptr(ptrs(cols.map((c) => c.dev))), ptr(words), BigInt(cols.length), ptr(q4(constant)),
+      Math.log2(cols[0]!.len()), ptr(out.ptrs())));
+    return out;
+  }
   // AIR (constraint_framework/index.ts, examples/fibonacci.ts; the prover around them: tstwo_amd/air.py and tstwo_amd/prover.py)
   /** generateTrace of wide Fibonacci on the device: x_0 = a, x_1 = b, x_k = x_{k-2}^2 + x_{k-1}^2, nColumns columns of a.len(). */
   generateWideFibTrace(a: HipColumn, b: HipColumn, nColumns: number): HipColumn[] {

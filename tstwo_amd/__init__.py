@@ -17,7 +17,8 @@ from .fri_verifier import (CirclePolyDegreeBound, FriVerificationError, FriVerif
 from .gkr import (EqEvals, GkrInputClaimMismatch, GkrMultivariatePolyOracle, HipGkrOps, HipMleOps, Layer, Mle,  # noqa: F401
                   check_logup_sum, eval_mles_at_point, logup_denominators, logup_input_layer, verify_input_claims,
                   prove_batch as gkr_prove_batch)
-from .gkr_lookup import gkr_range_check_layers, gkr_range_check_prove, gkr_range_check_verify  # noqa: F401
+from .gkr_lookup import (GkrStarkProof, gkr_range_check_layers, gkr_range_check_prove, gkr_range_check_stark_prove,  # noqa: F401
+                         gkr_range_check_stark_verify, gkr_range_check_verify)
 from .gkr_verifier import (Gate, GkrArtifact, GkrBatchProof, GkrError, GkrErrorType, GkrMask,  # noqa: F401
                            partially_verify_batch)
 from .sumcheck import SumcheckError, SumcheckProof, UnivariatePoly  # noqa: F401
@@ -48,6 +49,8 @@ from .logup import (INTERACTION_TRACE_IDX, LogupColGenerator, LogupTraceGenerato
                     lookup_multiplicities_keyed)
 from .prover import (ConstraintsNotSatisfied, ConstraintViolation, InvalidLogupSum, InvalidStructure, OodsNotMatching,  # noqa: F401
                      StarkProof, diagnose, prove, verify)
+from .mle_eval import (MleEvalEval, MleEvalForm, batched_form, mle_eval_constants, mle_eval_interaction_trace,  # noqa: F401
+                       mle_eval_selector_columns, mle_eval_terms)
 
 __all__ = [n for n in dir() if not n.startswith("_")]
 from .semantics import get_semantics, set_semantics  # noqa: F401,E402

@@ -214,6 +214,8 @@ _SIGS = {
     "tstwo_air_check_constraints": [C.POINTER(vp), C.c_size_t, C.c_uint32, u32p, C.c_size_t, C.c_size_t, vp],
     "tstwo_logup_column": [C.POINTER(LogupFrac), C.c_size_t, C.POINTER(vp), C.c_uint32, P4],
     "tstwo_logup_finalize_last": [P4, C.c_uint32, u32p],
+    "tstwo_mle_eval_selectors": [C.c_uint32, C.POINTER(vp)],
+    "tstwo_mle_eval_terms": [P4, C.POINTER(vp), u32p, C.c_size_t, u32p, C.c_uint32, P4],
     "tstwo_lookup_multiplicities": [C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp],
     "tstwo_lookup_multiplicities_keyed": [C.POINTER(LookupGroup), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp],
     "tstwo_coset_iota": [vp, C.c_uint32],

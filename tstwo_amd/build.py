@@ -22,7 +22,7 @@ OBJ = os.path.join(CSRC, "obj")
 LIB = os.path.join(HERE, "libtstwo_hip.so")
 OBJ_EXP = os.path.join(CSRC, "obj", "exp")
 LIB_EXP = os.path.join(HERE, "libtstwo_hip_exp.so")
-SOURCES = ["context.hip", "field_ops.hip", "cfft.hip", "fri.hip", "poly_eval.hip", "merkle.hip", "decommit.hip", "quotients.hip", "comm.hip", "gkr_ops.hip", "gkr_transcript.hip", "gkr_prove.hip", "poseidon.hip", "poseidon_coop.hip", "air.hip", "air_native.hip", "logup.hip", "lookup.hip", "mle_eval.hip"]
+SOURCES = ["context.hip", "field_ops.hip", "cfft.hip", "fri.hip", "poly_eval.hip", "merkle.hip", "decommit.hip", "quotients.hip", "comm.hip", "gkr_ops.hip", "gkr_transcript.hip", "gkr_prove.hip", "poseidon.hip", "poseidon_coop.hip", "air.hip", "air_native.hip", "logup.hip", "lookup.hip", "mle_eval.hip", "mle_eval_air.hip"]
 # every header under csrc/ (globbed: a new .cuh / .h / .inc marks all objects stale without having to be listed) + the public one
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".cuh", ".h", ".inc"))) + [os.path.join("..", "..", "include", "tstwo_hip.h")]
 ARCH = "gfx950"
